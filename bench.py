@@ -11,7 +11,10 @@ sequence pools.  N > 1: the SAME global batch (strong scaling: total work fixed)
 fnv1a64(target_name) % N gives it, one all-reduce of the per-record output sizes per step (ordered output) and one of the
 stat totals; row bytes never cross GPUs.  `--scaling weak` gives every rank its own shard of --records instead.
 
-Prints ONE JSON line on rank 0.  `python bench.py` defaults to N=1, 5 steps, 2 warm-up steps.
+Prints ONE JSON line on rank 0.  `python bench.py` defaults to N=1, 20 steps, 5 warm-up steps.  A plain run sets up, warms up,
+times the steps and prints the line; `--full` adds everything else the line can carry (CPU baseline, oracle spot checks, the row
+kernel on further allocations and other shapes, the file-to-file leg).  `--dump-outputs DIR` writes what the last timed step
+computed (dump_outputs()).
 """
 import argparse
 import json
@@ -134,6 +137,44 @@ def pmc_traffic(args, job):
             continue
         return t["hbm_bytes_per_launch"]
     return None
+
+
+def dump_outputs(job, totals, out_dir, budget=64 << 20, row_windows=1024, window=4096, seed=0x5747415F):
+    """What a caller of the timed path receives after its last step, as <out_dir>/<name>.npy (float64 holds every int64 value the
+    step writes exactly; the row bytes go as float32):
+      totals                      the 11 stat totals
+      counts, diag                per record: the 11 stat counters, the 3 error fields (-1 = clean)
+      t_row_off, q_row_off, rec_off  per record: where its two rows and its block start in the output
+      rows_sample                 row_windows x window bytes of the output rows at seeded offsets (the rows are ~15 GB)
+    Per-record arrays beyond what fits next to the rows sample are a seeded sample of the records (record_index.npy says which).
+    Everything depends only on the arguments: two builds of the project can be compared file by file."""
+    import numpy as np
+    torch = job.torch
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(seed)
+    dev = job.out.device
+    n_rows = int(job.out_bytes)
+    w = min(window, n_rows)
+    starts = np.sort(rng.integers(0, n_rows - w + 1, size=row_windows)) if w else np.zeros(0, dtype=np.int64)
+    idx = torch.as_tensor(starts, dtype=torch.int64, device=dev)[:, None] + torch.arange(w, dtype=torch.int64, device=dev)[None, :]
+    rows = job.out[idx.reshape(-1)].reshape(len(starts), w).cpu().numpy().astype(np.float32)
+    per_rec = {"counts": job.counts, "diag": job.diag, "t_row_off": job.t_row_off, "q_row_off": job.q_row_off,
+               "rec_off": job.rec_off[:-1]}
+    rec_bytes = sum(8 * (t[0].numel() if t.dim() > 1 else 1) for t in per_rec.values())
+    cap = max(1, (budget - rows.nbytes - (1 << 20)) // (rec_bytes + 8))   # 1 MB for the totals and the .npy headers
+    arrays = {"totals": totals.cpu().numpy().astype(np.float64), "rows_sample": rows}
+    if job.n > cap:
+        pick = np.sort(rng.choice(job.n, size=cap, replace=False))
+        arrays["record_index"] = pick.astype(np.float64)
+        pick_t = torch.as_tensor(pick, dtype=torch.int64, device=dev)
+        per_rec = {k: t[pick_t] for k, t in per_rec.items()}
+    else:   # the whole rec_off: its last entry is the rows' total
+        per_rec["rec_off"] = job.rec_off
+    for k, t in per_rec.items():
+        arrays[k] = t.cpu().numpy().astype(np.float64)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return sum(a.nbytes for a in arrays.values())
 
 
 def extra_shape(eng, synth, pipeline, torch, dev, seed, records, mean_ops, pool_mb, steps=3):
@@ -442,7 +483,17 @@ def main():
     ap.add_argument("--north-star", action="store_true", help="the 10 M x 50 kop headline shape as a stream of resident batches (N = 1)")
     ap.add_argument("--ns-records", type=int, default=400_000)
     ap.add_argument("--ns-batch-records", type=int, default=40_000)
+    ap.add_argument("--full", action="store_true", help="after the headline, also the CPU baseline and its oracle spot check, the "
+                                                        "row kernel on further allocations, the other shapes, the file-to-file "
+                                                        "leg and (N > 1) the ranks' oracle spot check; a plain run does only the "
+                                                        "timed steps and the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0) as DIR/<name>.npy, float64 / float32, <= 64 MB")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.north_star or args.plan_only):
+        ap.error("--dump-outputs writes the timed steps' outputs: not with --north-star or --plan-only")
     if args.north_star:
         return north_star(args)
     if args.plan_only:
@@ -544,6 +595,8 @@ def main():
         dist.all_reduce(nops)
     elapsed = float(el.item())
     total_ops = float(nops.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(job, totals, args.dump_outputs)
 
     ranks_seen = None
     if dist_on:   # every rank adds one: what RCCL itself saw
@@ -560,7 +613,7 @@ def main():
     # use bench.py makes of oracle/ besides the N = 1 cpu baseline), and the ranks agree on the verdict — an N-GPU line is
     # a real partition AND byte-verified
     ranks_checked = None
-    if dist_on and args.check and not args.param:
+    if args.full and dist_on and args.check and not args.param:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import parity_cases as pc
@@ -641,8 +694,8 @@ def main():
             result["parity_spot_check"] = ranks_checked
         result["metric_scope"] = ("kernel-only: K1 + layout + K2 (+ totals) on packed ops and sequence pools resident in HBM; no "
                                   "CIGAR tokenising, PAF / FASTA parsing, PCIe or file I/O — the file-to-file command line on the same "
-                                  "batch is the `e2e` object of this line")
-        if not args.no_cpu_baseline and world == 1:   # reported at N = 1 only
+                                  "batch is the `e2e` object of the `--full` line")
+        if args.full and not args.no_cpu_baseline and world == 1:   # reported at N = 1 only
             result["cpu_baseline"] = cpu_baseline(tb)
             # part of the same leg (the only place bench.py touches oracle/): a few of the rows the timed steps
             # wrote, compared with the oracle's rows for those records
@@ -656,13 +709,13 @@ def main():
                     gt, gq = job.record_rows(i)
                     assert gt == et and gq == eq, "record %d differs from the oracle" % i
                 result["cpu_baseline"]["parity_spot_check"] = "%d records bit-identical to oracle rows" % len(step_idx)
-        if world == 1 and not args.no_spread and not args.param:
+        if args.full and world == 1 and not args.no_spread and not args.param:
             try:   # additional information: never at the price of the headline line
                 result["roofline"]["allocation_spread"] = allocation_spread(eng, pipeline, torch, tb, k_expand, steps=args.steps,
                                                                             warm=args.warmup)
             except Exception as e:  # noqa: BLE001
                 result["roofline"]["allocation_spread"] = {"error": "%s: %s" % (type(e).__name__, e)}
-        if world == 1 and not args.no_extras and not args.param and args.records == 100_000 and args.mean_ops == 5000:
+        if args.full and world == 1 and not args.no_extras and not args.param and args.records == 100_000 and args.mean_ops == 5000:
             # the same kernel where the default shape flatters it: pools beyond the Infinity Cache, and the
             # north-star record length
             try:   # additional information: never at the price of the headline line
@@ -680,7 +733,7 @@ def main():
                                                          "1000000x500op": ms_s}
             except Exception as e:  # noqa: BLE001
                 result["roofline"]["extra_shapes_error"] = "%s: %s" % (type(e).__name__, e)
-        if world == 1 and not args.no_e2e and not args.param:
+        if args.full and world == 1 and not args.no_e2e and not args.param:
             try:   # additional information: never at the price of the headline line
                 try:
                     del job

@@ -6,7 +6,7 @@ OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
-BENCH="python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras --no-e2e --no-placement-probe --check 0"
+BENCH="python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extras --no-e2e --no-placement-probe --check 0"
 # another command's kernels (e.g. K5: WGA_PMC_CMD="python $R/scripts/gpu_k5_scaling.py 1" bash scripts/gpu_pmc.sh k5pmc "sq1 sq2 sq3 tcc")
 BENCH=${WGA_PMC_CMD:-$BENCH}
 PASSES=${2:-"sq1 sq2 fetch write tcc"}

@@ -9,7 +9,7 @@ cd $R
 export TMPDIR=/tmp
 timeout 900 python -m pytest tests/test_gpu_parity.py -x -q -s -k "bgzf" > $OUT/pytest_bgzf.log 2>&1; echo "pytest bgzf rc=$?"; grep -E "K18 at size|passed|failed|Error" $OUT/pytest_bgzf.log | tail -6
 timeout 900 python -m pytest tests/test_gpu_cli.py -x -q -k "paf2maf_end_to_end or gz_outputs or call_readme or stat_paf_fixture or pafcov_fixture" > $OUT/pytest_cli.log 2>&1; echo "pytest cli rc=$?"; tail -3 $OUT/pytest_cli.log
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_n1.json 2> $OUT/bench_n1.err; echo "bench rc=$?"
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_n1.json 2> $OUT/bench_n1.err; echo "bench rc=$?"
 python - <<PY
 import json
 d=json.loads(open('$OUT/bench_n1.json').readline())

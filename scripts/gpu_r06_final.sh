@@ -11,10 +11,10 @@ echo "== suite + smoke"
 timeout 2400 python -m pytest tests -q -m gpu -s > $OUT/pytest_gpu.log 2>&1; echo "pytest rc=$?"; grep -E "1e8-column|reduce_scatter_i32 over|config 4 at size|passed|failed" $OUT/pytest_gpu.log | tail -8
 timeout 200 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; echo "smoke rc=$?"; tail -1 $OUT/smoke.log
 echo "== bench (driver command)"
-timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_n1.json 2> $OUT/bench_n1.err; echo "bench rc=$?"
+timeout 1200 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_n1.json 2> $OUT/bench_n1.err; echo "bench rc=$?"
 cut -c1-600 $OUT/bench_n1.json
 echo "== the same command's kernels under rocprofv3 --kernel-trace --stats (one shape in the process: the row kernel's row = warm-up + timed launches + the allocation spread)"
-( cd /tmp && timeout 1200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o p -- python $R/bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-e2e --no-extras > $OUT/bench_n1_under_rocprof.json 2> $OUT/rocprof.err ); echo "rocprof rc=$?"
+( cd /tmp && timeout 1200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o p -- python $R/bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-e2e --no-extras > $OUT/bench_n1_under_rocprof.json 2> $OUT/rocprof.err ); echo "rocprof rc=$?"
 find $OUT/prof -name '*kernel_stats.csv' | head -1 | xargs -I{} sh -c 'head -8 {}' | cut -c1-200
 find $OUT/prof -name '*kernel_trace.csv' -delete
 echo "== counter passes: the row kernel"

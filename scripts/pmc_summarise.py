@@ -24,7 +24,7 @@ for d in ("sq1", "sq2", "sq3", "fetch", "write", "tcc"):
                 agg_all[(k, c)] = x
 with open(dst + "_pmc.txt", "w") as f:
     f.write("# rocprofv3 --kernel-trace --pmc <counters>, one pass per line group (scripts/gpu_pmc.sh), summed over the\n"
-            "# %d launches of `bench.py --steps 2 --warmup 1 --no-cpu-baseline --check 0` (our kernels only)\n" % launches)
+            "# %d launches of `bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --check 0` (our kernels only)\n" % launches)
     f.write("%-6s %-28s %-24s %s\n" % ("pass", "kernel", "counter", "sum over launches"))
     for d, k, c, x in rows:
         f.write("%-6s %-28s %-24s %.6g\n" % (d, k, c, x))

@@ -74,3 +74,64 @@ def test_traffic_comes_from_the_newest_rounds_counter_passes():
         assert got is None or got != newest["hbm_bytes_per_launch"]
     Job.n_ops += 1
     assert bench.pmc_traffic(Args, Job) is None
+
+
+def _cpu_job(n, row_bytes):
+    """the attributes of pipeline.Paf2MafStatJob that bench.dump_outputs reads, as CPU tensors"""
+    import torch
+
+    class Job:
+        pass
+
+    j = Job()
+    j.torch, j.n, j.out_bytes = torch, n, row_bytes
+    g = torch.Generator().manual_seed(7)
+    j.out = torch.randint(0, 256, (row_bytes + 64,), dtype=torch.uint8, generator=g)
+    j.counts = torch.randint(0, 1 << 40, (n, 11), dtype=torch.int64, generator=g)
+    j.diag = torch.full((n, 3), -1, dtype=torch.int64)
+    j.t_row_off = torch.arange(n, dtype=torch.int64) * 1000
+    j.q_row_off = j.t_row_off + 500
+    j.rec_off = torch.arange(n + 1, dtype=torch.int64) * 1000
+    return j, j.counts.sum(0)
+
+
+def test_dump_outputs_writes_the_last_steps_arrays(tmp_path):
+    """--dump-outputs: every array a caller of the timed path receives, as float64 (rows as float32), within the budget; a
+    batch whose per-record arrays do not fit is a seeded sample of its records; the same job gives the same files"""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    j, totals = _cpu_job(3000, 200_000)
+    total = bench.dump_outputs(j, totals, str(tmp_path / "a"))
+    a = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert set(a) == {"totals", "rows_sample", "counts", "diag", "t_row_off", "q_row_off", "rec_off"}
+    assert total == sum(x.nbytes for x in a.values()) <= 64 << 20
+    assert all(x.dtype in (np.float32, np.float64) for x in a.values())
+    assert np.array_equal(a["counts"], j.counts.numpy().astype(np.float64))
+    assert np.array_equal(a["totals"], a["counts"].sum(0)) and (a["diag"] == -1).all()
+    assert np.array_equal(a["rec_off"], j.rec_off.numpy().astype(np.float64))
+    rows = a["rows_sample"]
+    assert rows.shape == (1024, 4096) and rows.max() <= 255
+    src = j.out.numpy()
+    for r in rows[:16]:      # every window is a run of consecutive row bytes
+        hit = np.flatnonzero(src[: j.out_bytes - 4095] == r[0])
+        assert any(np.array_equal(src[s:s + 4096], r) for s in hit)
+
+    budget = (2 << 20) + (200 << 10)   # 3000 records do not fit beside a 1 MB rows sample (and 1 MB of slack): a sample
+    bench.dump_outputs(j, totals, str(tmp_path / "b"), budget=budget, row_windows=64)
+    bench.dump_outputs(j, totals, str(tmp_path / "c"), budget=budget, row_windows=64)
+    b = {f[:-4]: np.load(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")}
+    assert sum(x.nbytes for x in b.values()) <= budget
+    pick = b["record_index"].astype(np.int64)
+    assert 0 < len(pick) < 3000 and np.all(np.diff(pick) > 0)
+    assert np.array_equal(b["counts"], j.counts.numpy()[pick].astype(np.float64))
+    assert np.array_equal(b["rec_off"], j.rec_off.numpy()[pick].astype(np.float64))
+    for f in os.listdir(tmp_path / "b"):
+        assert np.array_equal(np.load(tmp_path / "b" / f), np.load(tmp_path / "c" / f))
+
+
+def test_dump_outputs_is_refused_where_there_are_no_timed_steps(tmp_path):
+    for mode in ("--north-star", "--plan-only"):
+        r = _bench(mode, "--dump-outputs", str(tmp_path / "d"))
+        assert r.returncode == 2 and "--dump-outputs" in r.stderr, (mode, r.stderr)
+        assert not (tmp_path / "d").exists()
