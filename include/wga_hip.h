@@ -558,6 +558,39 @@ int wga_reduce_scatter_i32(wga_ctx** ctxs, int ngpu, int32_t** d_bufs, uint64_t 
 /* ---- utility: exclusive scan of n u64 values on device (d_out[n+1], d_out[n] = total) ------- */
 int wga_exclusive_scan_u64(wga_ctx*, uint32_t n, const uint64_t* d_in, uint64_t* d_out);
 
+/* ---- K20: MAF chunk (tools/chunk.rs:20-90 with recount_align_size parser/common.rs:179-190 and the record writer
+ *      maf.rs:566-581) -----------------------------------------------------------------------------------------------------
+ * A block's columns are those of its FIRST row (chunk.rs:35): chunks [0, L), [L, 2L), ... while a chunk ends before the block
+ * does, then the rest; a block of 0 columns has one empty chunk.  Chunk k of a block is the record "a score=255\n", one line
+ * "s\t<name>\t<start>\t<size>\t<+|->\t<srcSize>\t<text[c0 .. c1)>\n" per row and an empty line; size = the bytes of the slice
+ * that are not '-', start = the row's input start plus the sizes of its chunks in front (plain addition on both strands).
+ * Every row must hold at least c1 bytes of the chunks asked for (the reference panics on the slice; the caller cuts there).
+ * A call writes a WINDOW: blocks d_blocks[0 .. n_blocks), each with the chunks [k_lo, k_hi) of it, in that order;
+ * every entry has n_rows >= 1 and k_hi > k_lo, and a block (its rows) appears at most once in a window (its entries would
+ * share d_carry: the later one's starts would be wrong).  n_lines = sum of n_rows * (k_hi - k_lo) < 2^32.  d_carry[row] = the sizes of the row's chunks written by earlier windows
+ * (zero for a block's first window); the fill call adds this window's.  d_work = wga_maf_chunk_work_bytes(n_blocks,
+ * n_lines) bytes of device memory the two calls share.  Two calls with the same arguments:
+ *   d_out == NULL: the counts, starts and line lengths; *text_bytes = the window's text length (host value; synchronises).
+ *   otherwise     : the text at d_out[0 .. text_bytes), and d_carry advanced. */
+typedef struct {
+  uint64_t seq_off;  /* the row's text: d_text[seq_off .. seq_off + seq_len) */
+  uint64_t seq_len;
+  uint64_t name_off; /* its name: d_text[name_off .. name_off + name_len) */
+  uint64_t start;    /* the input start field */
+  uint64_t src_size; /* the input srcSize field (the input size field is not used: the slices are counted) */
+  uint32_t name_len;
+  uint32_t strand_neg;
+} wga_maf_chunk_row;
+typedef struct {
+  uint64_t row0;       /* the block's first row in the row table; its rows are row0 .. row0 + n_rows - 1 */
+  uint64_t k_lo, k_hi; /* the block's chunks this window writes */
+  uint32_t n_rows, pad;
+} wga_maf_chunk_block;
+uint64_t wga_maf_chunk_work_bytes(uint32_t n_blocks, uint64_t n_lines);
+int wga_maf_chunk(wga_ctx*, const uint8_t* d_text, const wga_maf_chunk_row* d_rows, uint32_t n_blocks,
+                  const wga_maf_chunk_block* d_blocks, uint64_t n_lines, uint64_t chunk_len, uint64_t* d_carry, void* d_work,
+                  uint64_t* text_bytes, uint8_t* d_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,6 +33,7 @@
 #include "wga_k18_bgzf_deflate.h"
 #include "wga_kernels3.h"      /* K16 VCF rows of call on PAF, K17 BGZF inflate */
 #include "wga_k19_maf_call.h"  /* K19: rules and VCF rows of call on MAF */
+#include "wga_k20_maf_chunk.h" /* K20: chunk on MAF */
 
 struct wga_ctx {
   int device = 0;
@@ -1298,6 +1299,68 @@ int wga_bgzf_compress(wga_ctx* c, const uint8_t* d_in, uint64_t n_bytes, uint8_t
     if (total + tail > out_cap) return fail(WGA_E_INVALID_ARG, "output buffer smaller than the compressed stream (wga_bgzf_bound)", nullptr);
     RT_CHECK(rt_h2d(d_out + total, k_bgzf_eof, sizeof k_bgzf_eof, c->stream));
   }
+  return WGA_OK;
+}
+
+uint64_t wga_maf_chunk_work_bytes(uint32_t n_blocks, uint64_t n_lines) {
+  return 8ull * (3ull * n_lines + 2ull * (uint64_t)n_blocks + 4ull);
+}
+
+int wga_maf_chunk(wga_ctx* c, const uint8_t* d_text, const wga_maf_chunk_row* d_rows, uint32_t n_blocks,
+                  const wga_maf_chunk_block* d_blocks, uint64_t n_lines, uint64_t chunk_len, uint64_t* d_carry, void* d_work,
+                  uint64_t* text_bytes, uint8_t* d_out) {
+  int rc = ctx_bind(c);
+  if (rc) return rc;
+  if (chunk_len == 0) return fail(WGA_E_INVALID_ARG, "chunk_len must be greater than 0", nullptr);
+  if (n_lines >= 0xFFFFFFFFull) return fail(WGA_E_INVALID_ARG, "a window holds fewer than 2^32 lines", nullptr);
+  if (!text_bytes || (n_blocks && (!d_text || !d_rows || !d_blocks || !d_carry || !d_work)))
+    return fail(WGA_E_INVALID_ARG, "null array", nullptr);
+  const u32 n = (u32)n_lines, nb = n_blocks;
+  /* d_work: counts (then line lengths) [n] | their scan [n + 1] | the line offsets [n + 1] | the blocks' first lines [nb + 1] |
+   * their first granules [nb + 1] */
+  u64* A = (u64*)d_work;
+  u64* pre = A + n;
+  u64* loff = pre + n + 1u;
+  u64* bitem = loff + n + 1u;
+  u64* bgran = bitem + nb + 1u;
+  if (!d_out) {
+    *text_bytes = 0;
+    if (n == 0) return WGA_OK;
+    ScanChunkItems fi;
+    fi.blocks = d_blocks;
+    if ((rc = run_scan(c, fi, nb, bitem))) return rc;
+    ScanChunkGran fg;
+    fg.blocks = d_blocks;
+    fg.rows = d_rows;
+    fg.L = chunk_len;
+    if ((rc = run_scan(c, fg, nb, bgran))) return rc;
+    RT_CHECK(rt_memset(A, 0, (size_t)n * 8u, c->stream));
+    WGA_LAUNCH(k_maf_chunk_count, WGA_K20_GRID, WGA_BLOCK, c->stream, d_text, d_rows, d_blocks, nb, (const u64*)bitem,
+               (const u64*)bgran, (u64)chunk_len, A);
+    LAUNCH_CHECK();
+    ScanPlain f;
+    f.in = A;
+    if ((rc = run_scan(c, f, n, pre))) return rc;
+    WGA_LAUNCH(k_maf_chunk_lines, (n + 255u) / 256u, WGA_BLOCK, c->stream, d_rows, d_blocks, nb, (const u64*)bitem,
+               (const u64*)pre, (const u64*)d_carry, (u64)chunk_len, n, A);
+    LAUNCH_CHECK();
+    if ((rc = run_scan(c, f, n, loff))) return rc;
+    u64 total = 0;
+    RT_CHECK(rt_d2h(&total, loff + n, 8, c->stream));
+    *text_bytes = total;
+    return WGA_OK;
+  }
+  if (n == 0) return WGA_OK;
+  const u64 tiles = (*text_bytes + WGA_K20_TILE - 1u) / WGA_K20_TILE;
+  if (tiles >= 0x80000000ull) return fail(WGA_E_INVALID_ARG, "window text too long", nullptr);
+  if (tiles) {
+    WGA_LAUNCH(k_maf_chunk_fill, (u32)tiles, WGA_BLOCK, c->stream, d_text, d_rows, d_blocks, nb, (const u64*)bitem,
+               (const u64*)pre, (const u64*)d_carry, (u64)chunk_len, n, (const u64*)loff, d_out);
+    LAUNCH_CHECK();
+  }
+  WGA_LAUNCH(k_maf_chunk_carry, (nb + 255u) / 256u, WGA_BLOCK, c->stream, d_blocks, nb, (const u64*)bitem, (const u64*)pre,
+             (u64*)d_carry);
+  LAUNCH_CHECK();
   return WGA_OK;
 }
 

@@ -108,6 +108,10 @@ class Batch:
         self.c = _lib.CigarBatch(_p(ops), _p(op_off), _p(strand_neg), self.n_ops, self.n)
 
 
+# K20 tables (include/wga_hip.h wga_maf_chunk_row / wga_maf_chunk_block)
+MAF_CHUNK_ROW_DTYPE = np.dtype([("seq_off", "<u8"), ("seq_len", "<u8"), ("name_off", "<u8"), ("start", "<u8"),
+                                ("src_size", "<u8"), ("name_len", "<u4"), ("strand_neg", "<u4")])
+MAF_CHUNK_BLOCK_DTYPE = np.dtype([("row0", "<u8"), ("k_lo", "<u8"), ("k_hi", "<u8"), ("n_rows", "<u4"), ("pad", "<u4")])
 VCF_ERR_DTYPE = np.dtype([("item", "<u8"), ("kind", "<u4"), ("ch", "<u4")])
 MAF_VCF_REC_DTYPE = np.dtype([("t_name_off", "<u8"), ("q_name_off", "<u8"), ("t_name_len", "<u4"), ("q_name_len", "<u4"),
                               ("t_start", "<u8"), ("q_start", "<u8"), ("q_size", "<u8"), ("q_neg", "<u4"), ("pad", "<u4")])
@@ -427,6 +431,23 @@ class Engine:
         self._check(self.lib.wga_pafcov_format(self.ctx, _p(name), int(name.numel() if hasattr(name, 'numel') else name.size), _p(cov), int(p0), int(count),
                                                _p(line_off), _p(out)))
         return line_off
+
+    def maf_chunk(self, text, rows, blocks, chunk_len, carry):
+        """K20 (chunk.rs:20-90): the MAF text of one window of chunk records.  text / rows / carry: device arrays (rows of
+        MAF_CHUNK_ROW_DTYPE, carry = one u64 per row, advanced by the call); blocks: a host array of MAF_CHUNK_BLOCK_DTYPE.
+        Returns the window's text as bytes."""
+        blocks = np.ascontiguousarray(blocks, dtype=MAF_CHUNK_BLOCK_DTYPE)
+        nb = int(blocks.size)
+        n_lines = int(sum(int(b["n_rows"]) * (int(b["k_hi"]) - int(b["k_lo"])) for b in blocks))
+        d_blocks = self.upload(blocks) if nb else None
+        work = self.empty(int(self.lib.wga_maf_chunk_work_bytes(nb, n_lines)), np.uint8)
+        total = C.c_uint64(0)
+        args = (self.ctx, _p(text), _p(rows), nb, _p(d_blocks), n_lines, int(chunk_len), _p(carry), _p(work), C.byref(total))
+        self._check(self.lib.wga_maf_chunk(*args, None))
+        out = self.empty(max(int(total.value), 1), np.uint8)
+        self._check(self.lib.wga_maf_chunk(*args, _p(out)))
+        self.sync()
+        return out.numpy()[:int(total.value)].tobytes()
 
     def pafpseudo_fill(self, batch, base_mode, q_fa, q_fa_bytes, q_src_off, q_src_len, skip, out,
                        dst_off, diag=None):

@@ -122,8 +122,9 @@ struct MafInput {
   std::vector<MafRecord> recs;
   bool on_device = false;
   uint8_t* d_text = nullptr;
+  std::string error; /* keep_going: the host reader's error behind the records (they come first) */
 };
-MafInput maf_from_text(Dev& d, std::string&& whole_text) {
+MafInput maf_from_text(Dev& d, std::string&& whole_text, bool keep_going = false) {
   MafInput in;
   *in.text = std::move(whole_text);
   const std::string& text = *in.text;
@@ -174,6 +175,7 @@ MafInput maf_from_text(Dev& d, std::string&& whole_text) {
             const wga_maf_line& L = lines[i];
             MafSLine sl;
             sl.name.assign(text, (size_t)L.name_off, L.name_len);
+            sl.name_off = L.name_off;
             sl.start = L.num[0];
             sl.align_size = L.num[1];
             sl.size = L.num[2];
@@ -202,7 +204,7 @@ MafInput maf_from_text(Dev& d, std::string&& whole_text) {
     d.release(in.d_text);
     in.d_text = nullptr;
   }
-  in.recs = parse_maf(text, &in.header);
+  in.recs = keep_going ? parse_maf(text, &in.header, &in.error) : parse_maf(text, &in.header);
   return in;
 }
 MafInput load_maf(Dev& d, const std::string* input) { return maf_from_text(d, read_all(input)); }
@@ -217,6 +219,7 @@ struct MafChunks {
   bool first = true, done = false;
   std::string header;
   std::unique_ptr<BgzfDeviceSource> bgzf; /* a bgzipped input: inflated on the device */
+  bool keep_going = false; /* a piece whose host reader fails returns its records in front of the error (MafInput::error) */
   explicit MafChunks(const std::string* input) {
     bgzf.reset(new BgzfDeviceSource());
     if (bgzf->open(input))
@@ -298,10 +301,10 @@ struct MafChunks {
       if (!a.ok) return false;
       if (in.text && in.text.use_count() == 1) rd.recycle(std::move(*in.text)); /* nobody else holds the piece the caller is done with */
       read_ahead();
-      in = maf_from_text(d, std::move(a.text));
+      in = maf_from_text(d, std::move(a.text), keep_going);
       if (first_seen) header = in.header;
       first_seen = false;
-      if (!in.recs.empty()) return true;
+      if (!in.recs.empty() || !in.error.empty()) return true;
       if (in.d_text) d.release(in.d_text);
     }
   }

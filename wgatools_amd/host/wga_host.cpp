@@ -968,8 +968,11 @@ static MafSLine parse_sline(const std::string& line) { /* maf.rs:138-211 */
   return s;
 }
 
-std::vector<MafRecord> parse_maf(const std::string& text, std::string* header) {
+std::vector<MafRecord> parse_maf(const std::string& text, std::string* header) { return parse_maf(text, header, nullptr); }
+
+std::vector<MafRecord> parse_maf(const std::string& text, std::string* header, std::string* error) {
   std::vector<MafRecord> out;
+  try {
   size_t p = 0, n = text.size();
   auto next_line = [&](std::string* line) -> bool { /* BufRead::lines: strips \n and \r\n */
     if (p >= n) return false;
@@ -994,6 +997,10 @@ std::vector<MafRecord> parse_maf(const std::string& text, std::string* header) {
         break; /* the terminating line is consumed and dropped */
     }
     out.push_back(std::move(rec));
+  }
+  } catch (Error& e) {
+    if (!error) throw;
+    *error = e.msg; /* the block in progress is dropped: the reference's reader fails inside it */
   }
   return out;
 }

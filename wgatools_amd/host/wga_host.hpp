@@ -137,6 +137,7 @@ struct MafSLine { /* maf.rs:65-73 */
   std::string seq;              /* the row text (host reader) ... */
   const char* file = nullptr;   /* ... or a span of the input file, which stays in memory (device splitter) */
   uint64_t seq_off = 0, seq_len = 0;
+  uint64_t name_off = 0;         /* the name's offset in the file (device splitter only) */
   size_t seq_size() const { return file ? (size_t)seq_len : seq.size(); }
   const char* seq_data() const { return file ? file + seq_off : seq.data(); }
 };
@@ -152,6 +153,9 @@ struct MafRecord { /* maf.rs:216-220 */
 };
 /* maf.rs:25-36 + 371-421: first line is always the header; a block = maximal run of 's' lines */
 std::vector<MafRecord> parse_maf(const std::string& text, std::string* header);
+/* the same, but an s-line that does not parse ends the reading: the records in front of its block are returned and the
+ * reader's error goes to *error (the streaming commands write those records first) */
+std::vector<MafRecord> parse_maf(const std::string& text, std::string* header, std::string* error);
 
 /* `<maf>.index` (tools/index.rs:78-95, serde_json map name -> {ivls,size,isref}): the (name, size) of
  * the entries with isref, natord-sorted (caller.rs:340-357).  Missing file -> empty. */

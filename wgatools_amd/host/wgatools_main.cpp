@@ -1071,6 +1071,8 @@ uint32_t expand_batch(Dev& d, const wga_cigar_batch& cb, const ExpandJob& j, con
 
 #include "cmd_call.inc"
 
+#include "cmd_chunk.inc"
+
 /* ---- command line (cli.rs) -------------------------------------------------------------------------- */
 void log_error(const std::string& msg) {
   struct timespec ts;
@@ -1099,7 +1101,8 @@ void usage() {
           "  dotplot | dp   [FILE] [-f maf|paf] --out-format csv [-m base-level|overview] [-d] [-l CUTOFF] [-q QUERY_NAME]\n"
           "  chain2maf | c2m [CHAIN] --target TARGET.fa --query QUERY.fa   (-g / -q)\n"
           "  call    | c    [MAF] [-s] [-i] [-l SVLEN] [-n SAMPLE] [--query-name N | --query-regex R] [-c CHUNK]\n"
-          "  call    | c    -f paf [PAF] --target T.fa --query Q.fa [-s] [-l SVLEN] [-n SAMPLE]\n");
+          "  call    | c    -f paf [PAF] --target T.fa --query Q.fa [-s] [-l SVLEN] [-n SAMPLE]\n"
+          "  chunk   | ch   [MAF] -l LENGTH\n");
 }
 
 }  // namespace
@@ -1263,6 +1266,9 @@ static int run_command(int argc, char** argv) {
     const bool call = cmd == "call" || cmd == "c";
     const bool validate = cmd == "validate" || cmd == "vf";
     const bool dotp = cmd == "dotplot" || cmd == "dp";
+    const bool chunk = cmd == "chunk" || cmd == "ch";
+    std::string length_s;
+    bool has_length = false;
     std::string out_format = "html", mode = "base-level";
     bool no_identity = false, has_cutoff = false;
     uint64_t cutoff = 50; /* utils.rs:709-710 */
@@ -1299,6 +1305,12 @@ static int run_command(int argc, char** argv) {
       else if (dotp && (a == "-l" || a == "--length")) {
         cutoff = strtoull(val().c_str(), nullptr, 10);
         has_cutoff = true;
+      } else if (chunk && (a == "-l" || a == "--length")) {
+        length_s = val();
+        has_length = true;
+      } else if (chunk && (a.compare(0, 9, "--length=") == 0 || (a.size() > 2 && a.compare(0, 2, "-l") == 0))) {
+        length_s = a.substr(a[1] == '-' ? 9 : 2);
+        has_length = true;
       } else if (dotp && a == "--color")
         (void)val(); /* colours only exist in the Vega-Lite outputs */
       else if (a == "-e" || a == "--each")
@@ -1386,6 +1398,18 @@ static int run_command(int argc, char** argv) {
     if (cmd == "pafcov" || cmd == "pc") {
       out.open(outfile, rewrite);
       return cmd_pafcov(input, out, g_spread);
+    }
+    if (chunk) { /* utils.rs:656-677: the length is checked before any file is opened, then the output is created, then the input */
+      if (!has_length) fail("the following required arguments were not provided: --length <LENGTH>");
+      errno = 0;
+      char* end = nullptr;
+      const uint64_t L = strtoull(length_s.c_str(), &end, 10);
+      if (length_s.empty() || length_s.find_first_not_of("0123456789") != std::string::npos || errno == ERANGE)
+        fail("invalid value '" + length_s + "' for '--length <LENGTH>': " +
+             (errno == ERANGE ? "number too large to fit in target type" : "invalid digit found in string"));
+      if (L == 0) fail("`length` should be greater than 0");
+      out.open(outfile, rewrite);
+      return cmd_chunk(input, L, out);
     }
     fail("subcommand `" + cmd + "` is not on the CIGAR hot path and is not provided by this engine");
   } catch (Error& e) {
