@@ -312,7 +312,10 @@ int wga_paf_call_vcf(wga_ctx*, const wga_cigar_batch*, uint64_t svlen, const uin
  * run longer than `svlen` that follows an '=' / X run (:464-569).  Two calls as wga_paf_call_vcf: d_out == NULL ->
  * d_nbytes[n], d_err[n] (item == ~0: clean; kind 2 = a REF / ALT base outside ACGTN in any case, ch = the byte:
  * noodles-vcf's parse error); then d_out_off = exclusive scan of d_nbytes and the call again with d_out.  A block's text
- * ends in front of the chunk that holds its first bad base (a chunk's records are collected before any is written, :137-141). */
+ * ends in front of the chunk that holds its first bad base (a chunk's records are collected before any is written, :137-141).
+ * d_err[i].item of a bad block: only `!= ~0` is promised (today a count that goes on over the chunks' 64-run steps, not a run
+ * index); kind and ch identify the error.  The fill pass writes block i's d_nbytes[i] bytes into
+ * [d_out_off[i], d_out_off[i + 1]) and touches no other byte of d_out: d_out_off needs all n + 1 entries of the scan. */
 typedef struct {
   uint64_t t_name_off, q_name_off;
   uint32_t t_name_len, q_name_len;

@@ -8,18 +8,22 @@ import subprocess
 import numpy as np
 import pytest
 
+import maf_call_cases as k19
 import oracle_py as orc
 import parity_cases as pc
 from helpers import GOLDEN
 from wgatools_amd import build, synth
+
+_synth_maf_blocks = k19.synth_maf_blocks   # the generator K19's own battery (maf_call_cases.py) shares
 
 STAT_HEADER = ("ref_name\tref_size\tref_start\tquery_name\tquery_size\tquery_start\taligned_size\t"
                "unaligned_size\tidentity\tsimilarity\tmatched\tmismatched\tins_event\tdel_event\tins_size\t"
                "del_size\tinv_event\tinv_size\tinv_ins_event\tinv_ins_size\tinv_del_event\tinv_del_size\n")
 
 
-def run(cli, *args):
-    r = subprocess.run([cli] + list(args), stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+def run(cli, *args, env=None):
+    r = subprocess.run([cli] + list(args), stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                       env=dict(os.environ, **env) if env else None)
     return r.returncode, r.stdout, r.stderr.decode()
 
 
@@ -451,37 +455,6 @@ def test_call_readme_golden(cli):
             assert g.split("\t")[8] == "GT:QI"
 
 
-def _synth_maf_blocks(seed, n_blocks, cols):
-    """random gapped row pairs: match/mismatch stretches, insertions, deletions, both-gap columns,
-    adjacent I/D runs, lower-case and N bases, both strands"""
-    rng = np.random.default_rng(seed)
-    blocks = []
-    for k in range(n_blocks):
-        t, q = [], []
-        while len(t) < cols:
-            kind = rng.choice(5, p=[0.55, 0.12, 0.14, 0.14, 0.05])
-            ln = int(rng.integers(1, 40 if kind == 0 else 12))
-            alpha = np.frombuffer(b"ACGTacgtN", dtype=np.uint8)
-            a = alpha[rng.integers(0, 9, ln)]
-            if kind == 0:
-                t += list(a); q += list(a)
-            elif kind == 1:
-                b = alpha[rng.integers(0, 9, ln)]
-                t += list(a); q += list(b)
-            elif kind == 2:
-                t += [45] * ln; q += list(a)
-            elif kind == 3:
-                t += list(a); q += [45] * ln
-            else:
-                t += [45] * ln; q += [45] * ln
-        t, q = bytes(t[:cols]), bytes(q[:cols])
-        t_al, q_al = cols - t.count(b"-"), cols - q.count(b"-")
-        blocks.append(dict(t_name="chrT%d" % (k % 3), t_start=int(rng.integers(0, 10000)), t_align=t_al, t_size=50000,
-                           q_name="qry.%d" % (k % 2), q_start=int(rng.integers(0, 10000)), q_align=q_al,
-                           q_size=40000, neg=bool(rng.integers(0, 2)), t=t, q=q))
-    return blocks
-
-
 def _write_maf(path, blocks, extra_sline=False):
     with open(path, "wb") as f:
         f.write(b"##maf version=1\n")
@@ -561,6 +534,46 @@ def test_call_maf_bad_base_ends_in_front_of_its_chunk(cli, tmp_path):
     pos = [int(ln.split("\t")[1]) for ln in rest.splitlines()]
     t_before = b["t_start"] + sum(1 for ch in b["t"][:col] if ch != 45)
     assert all(p <= t_before + 1 for p in pos)              # nothing at or behind the bad column's chunk end is there
+
+
+def _deep_bad_base_case(tmp_path, chunk):
+    """four blocks of 6 000 columns (some 400 runs each); block 1 has an `R` as a SNP row's REF behind column 5 700, behind
+    the first 64-run step of its chunk.  -> (path, blocks, the bad block's expectation from K19's per-chunk helper)"""
+    blocks = _synth_maf_blocks(61, 4, 6000)
+    b = blocks[1]
+    t, q = bytearray(b["t"]), bytearray(b["q"])
+    col = next(k for k in range(5700, 6000) if t[k] != 45 and q[k] != 45)
+    t[col], q[col] = ord("R"), ord("A")
+    b["t"], b["q"] = bytes(t), bytes(q)
+    e = k19.expect_block(b, True, True, 2, chunk)
+    assert e["kind"] == 2 and e["ch"] == "R" and k19.steps_of(b, e)[1] > 0
+    maf = tmp_path / "deep.maf"
+    _write_maf(maf, blocks)
+    return str(maf), blocks, e
+
+
+def test_call_maf_bad_base_deep_in_a_block_at_the_default_chunk(cli, tmp_path):
+    """the default chunk of 10^6 columns: the bad block is one chunk, its bad base hundreds of runs in, clean blocks behind it.
+    The block owes no byte (wga_maf_call_vcf writes only what its count pass reported): the output is the header and the
+    block in front, to the byte"""
+    maf, blocks, e = _deep_bad_base_case(tmp_path, 1000000)
+    assert e["bad_chunk"] == 0 and len(e["text"]) == 0
+    rc, out, err = run(cli, "call", maf, "-s", "-i", "-l", "2", "-n", "smp")
+    assert rc == 1 and "invalid reference/alternate base `R`" in err, err
+    assert out.decode() == _expected_vcf(blocks[:1], "smp", True, True, 2, 1000000) + e["text"].decode()
+
+
+def test_call_maf_bad_base_in_the_last_block_of_a_piece(cli, tmp_path):
+    """the file read in pieces of one block, so the bad block ends its piece and its text ends the piece's buffer; -c 1500: the
+    block has chunks in front of the bad one.  A piece is one read of about WGA_CHUNK_BYTES up to a line end behind the s-lines
+    the piece in front left over, cut in front of its trailing s-lines (MafChunks, cmd_stat.inc): with every s-line longer
+    than the budget a read never gets past the next s-line, so no piece holds the s-lines of two blocks"""
+    maf, blocks, e = _deep_bad_base_case(tmp_path, 1500)
+    assert e["bad_chunk"] > 0 and len(e["text"]) > 0
+    assert min(len(b["t"]) for b in blocks) > 4000          # the one-block pieces rest on this
+    rc, out, err = run(cli, "call", maf, "-s", "-i", "-l", "2", "-c", "1500", "-n", "smp", env={"WGA_CHUNK_BYTES": "4000"})
+    assert rc == 1 and "invalid reference/alternate base `R`" in err, err
+    assert out.decode() == _expected_vcf(blocks[:1], "smp", True, True, 2, 1500) + e["text"].decode()
 
 
 def test_call_maf_gz_output_in_pieces(cli, tmp_path):

@@ -17,7 +17,7 @@ def cli():
 
 
 def test_dist_cli_one_rank_writes_the_command_lines_bytes(cli, tmp_path):
-    """the multi-rank driver (wgatools_amd/dist_cli.py) with one rank on libwgahip.so: same files as the `wgatools`
+    """the multi-rank driver (tests/dist_cli.py) with one rank on libwgahip.so: same files as the `wgatools`
     binary; 2 ranks run over gloo on the emulator build in test_dist_cli_gloo.py, N GPUs over RCCL are the driver's"""
     import dist_cli_cases as dc
     dc.check_paf2maf(tmp_path, None, cli, (1,), 29700)

@@ -112,6 +112,7 @@ def test_chunk_configs2_at_size_in_windows(gpu):
     exp_size, exp_start = order(sizes), order(starts)
     exp_slices = grid.view(nb, nr, nk, L).permute(0, 2, 1, 3).reshape(-1)
     del cum, sizes, starts
+    torch.cuda.synchronize()     # the rows are made on torch's stream; the library launches on a stream of its own
     n_rec = nb * nk
     cuts = [n_rec * i // 33 for i in range(34)]
     assert any(c % nk for c in cuts[1:-1])
@@ -128,6 +129,7 @@ def test_chunk_configs2_at_size_in_windows(gpu):
         args = (gpu.ctx, text.data_ptr(), d_rows.ptr, len(win), d_blocks.ptr, n_lines, L, carry.ptr, work.ptr, C.byref(tb))
         gpu._check(gpu.lib.wga_maf_chunk(*args, None))
         out = torch.zeros(int(tb.value) + 16, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize() # ... and so is the zero fill: it must not land on the text behind the fill call
         gpu._check(gpu.lib.wga_maf_chunk(*args, out.data_ptr()))
         gpu.sync()
         t = out[:int(tb.value)]

@@ -21,7 +21,9 @@
  * Text as K16 writes it (wga_kernels3.h): a step counts its rows' bytes, a wave scan places them, the fill pass assembles the
  * step in LDS and stores it in 16-byte groups.  Two-call protocol: bytes per block and the first bad base (noodles-vcf's parse
  * error: a REF / ALT character outside ACGTN in either case), then the text.  A block's text ends in front of the CHUNK that
- * holds its first bad base: the reference collects a chunk's records before it writes any of them (:137-141).
+ * holds its first bad base: the reference collects a chunk's records before it writes any of them (:137-141).  The fill pass
+ * writes block k's bytes into [out_off[k], out_off[k + 1]) and nothing else: it leaves the chunk loop when those bytes are out,
+ * in front of the first bad chunk, whose clean steps belong to no reported byte.
  */
 #ifndef WGA_K19_MAF_CALL_H
 #define WGA_K19_MAF_CALL_H
@@ -142,10 +144,13 @@ __global__ __launch_bounds__(256) void k_maf_call_vcf(u32 n, const u8* __restric
   const u64 total = cols[k];
   const u64 below = (1ull << lane) - 1ull;
   u64 written = 0;   /* bytes of the chunks in front */
+  /* FILL: the bytes the count pass gave the block = its chunks in front of the first bad one (what is left behind them has no
+   * rows or is that chunk) */
+  const u64 owed = FILL ? out_off[k + 1] - out_off[k] : 0ull;
   u64 cs = 0, rk = 0; /* the chunk's first column and the run it lies in */
   u32 bad_kind = 0, bad_ch = 0;
   u64 bad_item = 0, items_before = 0;
-  while (cs < total && nr) { /* wave-uniform */
+  while (cs < total && nr && (!FILL || written < owed)) { /* wave-uniform */
     const u64 proposed = chunk >= total - cs ? total : cs + chunk;
     /* ---- the chunk's end (find_safe_chunk_boundary on runs) ---- */
     u64 safe_end = proposed;
