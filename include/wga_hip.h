@@ -38,6 +38,12 @@ extern "C" {
  *    streams) and wga_pafcov_finalize refuses overlapping target ranges.  No struct layout changed. */
 #define WGA_ABI_VERSION 3
 
+/* The contract of every two-call protocol (count call, then fill call; also wga_maf_pair_stat / wga_maf_call_runs, whose count
+ * call leaves the table of its long blocks): the input arrays of a count call must not be rewritten outside the library before
+ * its fill call.  The context recognises the fill call by the arrays' addresses, the counts and the parameters — every input
+ * array of the call, the strand array included —, not by their contents.  Writes through wga_memcpy_h2d / wga_memset and a
+ * wga_free are seen and drop what was kept; a kernel or copy of the caller's own is not: fence it with a new count call. */
+
 /* ---- status codes (call level) ------------------------------------------------------------ */
 enum wga_status {
   WGA_OK = 0,

@@ -901,6 +901,50 @@ def check_maf_pair(eng, pairs, strands):
     assert (tx[int(to_[-1]):] == 0x23).all() and (ct[int(co[-1]):] == 0x23).all()
 
 
+def check_maf_table_other_strands(eng):
+    """the table of long blocks that a count call of K3 leaves is keyed by the strand array as well: a fill call that names
+    another strand array (at another address) does not take it, and gives the oracle's runs and — for the blocks the fill
+    call writes counters of, the ones that are not long — the oracle's counters under the strands it was given"""
+    rng = np.random.default_rng(78)
+    long_cols = 100
+    pairs = []
+    for L in (40, 99, 100, 101, 640, 2100, 64, 5000, 7):
+        pairs.append((rand_seq(rng, L, b"ACGTacgt--N"), rand_seq(rng, L, b"ACGTacgt--N")))
+    n = len(pairs)
+    buf, t_off, q_off = bytearray(b"@@@"), [], []
+    for t, q in pairs:
+        t_off.append(len(buf))
+        buf += t + b"@"
+        q_off.append(len(buf))
+        buf += q + b"@@"
+    cols = [len(t) for t, _ in pairs]
+    first = [i & 1 for i in range(n)]
+    second = [s if cols[i] > long_cols else 1 - s for i, s in enumerate(first)]   # the long blocks keep their strand
+    rows = eng.upload(np.frombuffer(bytes(buf), dtype=np.uint8))
+    d_t, d_q = eng.upload(np.array(t_off, dtype=np.uint64)), eng.upload(np.array(q_off, dtype=np.uint64))
+    d_c = eng.upload(np.array(cols, dtype=np.uint64))
+    d_s1, d_s2 = eng.upload(np.array(first, dtype=np.uint8)), eng.upload(np.array(second, dtype=np.uint8))
+    eng.set_param("maf_long_cols", long_cols)
+    eng.set_param("maf_piece_cols", 64)
+    try:
+        counts, run_cnt = eng.maf_pair_stat(n, rows, d_t, d_q, d_c, d_s1)
+        run_off = eng.exclusive_scan_u64(n, run_cnt)
+        ro = run_off.numpy()
+        runs = eng.empty(int(ro[-1]) + 1, np.uint64).fill(0)
+        counts, _ = eng.maf_pair_stat(n, rows, d_t, d_q, d_c, d_s2, counts=counts, run_cnt=run_cnt, runs=runs, run_off=run_off)
+    finally:
+        eng.set_param("maf_long_cols", 32768)
+        eng.set_param("maf_piece_cols", 16384)
+    c, rr = counts.numpy(), runs.numpy()
+    for i, (t, q) in enumerate(pairs):
+        exp_counts, exp_txt = orc.parse_maf_seq_to_cigar(t, q, second[i])
+        assert tuple(int(x) for x in c[i]) == exp_counts, (i, exp_counts, c[i])
+        mine = rr[int(ro[i]):int(ro[i + 1])]
+        starts = (mine >> np.uint64(3)).astype(np.int64).tolist() + [cols[i]]
+        txt = "".join("%d%s" % (starts[k + 1] - starts[k], "=IDX"[int(mine[k] & np.uint64(7))]) for k in range(len(mine)))
+        assert txt == exp_txt, (i, txt[:80], exp_txt[:80])
+
+
 def expected_split(length, code, cont):
     out, first = [], True
     while length:

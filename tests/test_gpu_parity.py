@@ -376,6 +376,10 @@ def test_piece_table_kept_or_rebuilt(gpu):
     pc.check_piece_table_rebuild(gpu)
 
 
+def test_maf_table_keyed_by_strands(gpu):
+    pc.check_maf_table_other_strands(gpu)
+
+
 def test_cigar_chain_long_records_in_pieces(gpu):
     pc.check_cigar_chain_long_records(gpu, mops=2)
 

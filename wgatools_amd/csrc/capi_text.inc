@@ -1,0 +1,256 @@
+/* capi_text.inc — K8 / K9 / K13 / K14 / K15 / K17 / K18: text in, text out (tokenisers, line splitters, FASTA pool, BGZF, BED lines).
+ * A part of wga_capi.cpp (included there: one translation unit). */
+/* K13 / K14 driver: delimiter lists (count, scan, fill) in the context scratch, then one thread per line.
+ * MODE 0 = PAF (wga_paf_line), 1 = MAF (wga_maf_line). */
+template <int MODE>
+static int split_lines(wga_ctx* c, const uint8_t* d_text, uint64_t n_bytes, uint64_t* n_lines, void* d_lines,
+                       uint64_t cap_lines) {
+  int rc = ctx_bind(c);
+  if (rc) return rc;
+  if (!n_lines) return fail(WGA_E_INVALID_ARG, "n_lines null", nullptr);
+  *n_lines = 0;
+  if (n_bytes == 0) return WGA_OK;
+  if (!d_text) return fail(WGA_E_INVALID_ARG, "d_text null", nullptr);
+  if (n_bytes >= 0xFFFFFFFFull) return fail(WGA_E_INVALID_ARG, "text of 4 GiB or more: split it at line ends", nullptr);
+  const u32 nb = (u32)((n_bytes + 4095u) / 4096u);
+  const size_t head = ((size_t)nb + 1 + (size_t)nb / 1024 + 4) * sizeof(u64);
+  u64 tot = 0;
+  void* ws = nullptr;
+  if ((rc = ctx_scratch(c, head, &ws))) return rc;
+  for (int attempt = 0; attempt < 2; attempt++) {
+    u64* blk = (u64*)c->scratch.mem;
+    WGA_LAUNCH((k_paf_delims<false, MODE>), nb, WGA_BLOCK, c->stream, d_text, (u64)n_bytes, blk, (const u64*)nullptr,
+               (u64*)nullptr, (u64*)nullptr);
+    LAUNCH_CHECK();
+    /* exclusive scan of the block counts in place (k_scan_final reads its four values, then writes them) */
+    ScanPlain f;
+    f.in = blk;
+    if ((rc = run_scan_ws(c, f, nb, blk, blk + nb + 1))) return rc;
+    RT_CHECK(rt_d2h(&tot, blk + nb, sizeof(u64), c->stream));
+    /* the two lists follow the block offsets; their sizes are only known now: growing the arena
+     * drops its contents, so the count pass is repeated once */
+    const size_t want = head + ((size_t)(tot & 0xFFFFFFFFull) + (size_t)(tot >> 32) + 2) * sizeof(u64);
+    if (c->scratch.cap >= want) break;
+    if ((rc = ctx_scratch(c, want, &ws))) return rc;
+  }
+  const u64 n_delims = tot & 0xFFFFFFFFull, n_newlines = tot >> 32;
+  u8 last = 0;
+  RT_CHECK(rt_d2h(&last, d_text + n_bytes - 1, 1, c->stream));
+  *n_lines = n_newlines + (last != (u8)0x0A ? 1 : 0);
+  if (!d_lines) return WGA_OK;
+  if (cap_lines < *n_lines) return fail(WGA_E_TOO_SMALL, "d_lines too small", nullptr);
+  u64* blk_off = (u64*)c->scratch.mem;
+  u64* delims = (u64*)((char*)c->scratch.mem + head);
+  u64* nl_idx = delims + n_delims + 1;
+  WGA_LAUNCH((k_paf_delims<true, MODE>), nb, WGA_BLOCK, c->stream, d_text, (u64)n_bytes, (u64*)nullptr,
+             (const u64*)blk_off, delims, nl_idx);
+  LAUNCH_CHECK();
+  if (MODE == 0) {
+    WGA_LAUNCH(k_paf_fields, (u32)((*n_lines + 255u) / 256u), WGA_BLOCK, c->stream, d_text, (u64)n_bytes,
+               (u64)*n_lines, n_newlines, n_delims, (const u64*)delims, (const u64*)nl_idx, (wga_paf_line_dev*)d_lines);
+  } else {
+    WGA_LAUNCH(k_maf_lines, (u32)((*n_lines + 255u) / 256u), WGA_BLOCK, c->stream, d_text, (u64)n_bytes,
+               (u64)*n_lines, n_newlines, n_delims, (const u64*)delims, (const u64*)nl_idx, (wga_maf_line_dev*)d_lines);
+  }
+  LAUNCH_CHECK();
+  return WGA_OK;
+}
+
+extern "C" {
+
+int wga_cigar_tokenise(wga_ctx* c, uint32_t n, const uint8_t* d_text, const uint64_t* d_text_off,
+                       uint64_t* d_op_cnt, wga_tok_err* d_err, uint32_t* d_ops,
+                       const uint64_t* d_op_off) {
+  int rc = ctx_bind(c);
+  if (rc) return rc;
+  if (n == 0) return WGA_OK;
+  if (!d_text || !d_text_off) return fail(WGA_E_INVALID_ARG, "null array", nullptr);
+  if (d_ops && !d_op_off) return fail(WGA_E_INVALID_ARG, "d_op_off null", nullptr);
+  static_assert(sizeof(wga_tok_err) == sizeof(wga_tok_err_dev), "wga_tok_err layout");
+  WGA_LAUNCH(k_cigar_tokenise, (n + 3u) / 4u, WGA_BLOCK, c->stream, n, d_text, (const u64*)d_text_off,
+             (const u64*)d_text_off + 1, (u64*)d_op_cnt, (wga_tok_err_dev*)d_err, d_ops, (const u64*)d_op_off);
+  LAUNCH_CHECK();
+  return WGA_OK;
+}
+
+int wga_cigar_tokenise_spans(wga_ctx* c, uint32_t n, const uint8_t* d_text, const uint64_t* d_beg,
+                             const uint64_t* d_end, uint64_t* d_op_cnt, wga_tok_err* d_err, uint32_t* d_ops,
+                             const uint64_t* d_op_off) {
+  int rc = ctx_bind(c);
+  if (rc) return rc;
+  if (n == 0) return WGA_OK;
+  if (!d_text || !d_beg || !d_end) return fail(WGA_E_INVALID_ARG, "null array", nullptr);
+  if (d_ops && !d_op_off) return fail(WGA_E_INVALID_ARG, "d_op_off null", nullptr);
+  WGA_LAUNCH(k_cigar_tokenise, (n + 3u) / 4u, WGA_BLOCK, c->stream, n, d_text, (const u64*)d_beg,
+             (const u64*)d_end, (u64*)d_op_cnt, (wga_tok_err_dev*)d_err, d_ops, (const u64*)d_op_off);
+  LAUNCH_CHECK();
+  return WGA_OK;
+}
+
+int wga_paf_split(wga_ctx* c, const uint8_t* d_text, uint64_t n_bytes, uint64_t* n_lines, wga_paf_line* d_lines,
+                  uint64_t cap_lines) {
+  static_assert(sizeof(wga_paf_line) == sizeof(wga_paf_line_dev), "wga_paf_line layout");
+  return split_lines<0>(c, d_text, n_bytes, n_lines, (void*)d_lines, cap_lines);
+}
+
+int wga_maf_split(wga_ctx* c, const uint8_t* d_text, uint64_t n_bytes, uint64_t* n_lines, wga_maf_line* d_lines,
+                  uint64_t cap_lines) {
+  static_assert(sizeof(wga_maf_line) == sizeof(wga_maf_line_dev), "wga_maf_line layout");
+  return split_lines<1>(c, d_text, n_bytes, n_lines, (void*)d_lines, cap_lines);
+}
+
+int wga_fasta_pool(wga_ctx* c, const uint8_t* d_text, uint64_t n_bytes, uint64_t* n_contigs, uint64_t* pool_bytes,
+                   uint8_t* d_pool, wga_fa_contig* d_contigs) {
+  static_assert(sizeof(wga_fa_contig) == sizeof(wga_fa_contig_dev), "wga_fa_contig layout");
+  int rc = ctx_bind(c);
+  if (rc) return rc;
+  if (!n_contigs || !pool_bytes) return fail(WGA_E_INVALID_ARG, "null count", nullptr);
+  if (n_bytes && !d_text) return fail(WGA_E_INVALID_ARG, "d_text null", nullptr);
+  if (n_bytes == 0) {
+    *n_contigs = *pool_bytes = 0;
+    return WGA_OK;
+  }
+  const u64 nb64 = (n_bytes + 4095u) / 4096u;
+  if (nb64 > 0x7FFFFFFFull) return fail(WGA_E_INVALID_ARG, "text too large for one call", nullptr);
+  const u32 nb = (u32)nb64;
+  /* scratch: block counts | their exclusive scan (+ total) | scan partials | (count call only) the contig table */
+  void* ws;
+  const size_t head = ((size_t)nb * 2 + 2 + (size_t)nb / 1024 + 4) * sizeof(u64);
+  if ((rc = ctx_scratch(c, head, &ws))) return rc;
+  u64* blk = (u64*)ws;
+  u64* blk_off = blk + nb;
+  u64* partial = blk_off + nb + 1;
+  ScanPlain sp;
+  sp.in = blk;
+  WGA_LAUNCH(k_fa_headers<false>, nb, WGA_BLOCK, c->stream, d_text, (u64)n_bytes, blk, (const u64*)nullptr,
+             (wga_fa_contig_dev*)nullptr);
+  LAUNCH_CHECK();
+  if ((rc = run_scan_ws(c, sp, nb, blk_off, partial))) return rc;
+  u64 nh = 0;
+  RT_CHECK(rt_d2h(&nh, blk_off + nb, sizeof nh, c->stream));
+  wga_fa_contig_dev* contigs = (wga_fa_contig_dev*)d_contigs;
+  if (!d_pool) { /* the count call keeps its own contig table in the scratch arena */
+    const size_t need = head + 64 + (size_t)nh * sizeof(wga_fa_contig_dev);
+    if (c->scratch.cap < need) { /* regrowing frees the arena: start again with room for the table */
+      if ((rc = ctx_scratch(c, need, &ws))) return rc;
+      blk = (u64*)ws;
+      blk_off = blk + nb;
+      partial = blk_off + nb + 1;
+      sp.in = blk;
+      WGA_LAUNCH(k_fa_headers<false>, nb, WGA_BLOCK, c->stream, d_text, (u64)n_bytes, blk, (const u64*)nullptr,
+                 (wga_fa_contig_dev*)nullptr);
+      LAUNCH_CHECK();
+      if ((rc = run_scan_ws(c, sp, nb, blk_off, partial))) return rc;
+    }
+    contigs = (wga_fa_contig_dev*)((char*)ws + ((head + 63) & ~(size_t)63));
+  } else if (nh && !d_contigs) {
+    return fail(WGA_E_INVALID_ARG, "d_contigs null", nullptr);
+  }
+  if (nh) {
+    WGA_LAUNCH(k_fa_headers<true>, nb, WGA_BLOCK, c->stream, d_text, (u64)n_bytes, blk, (const u64*)blk_off, contigs);
+    LAUNCH_CHECK();
+    WGA_LAUNCH(k_fa_header_ends, (u32)((nh + 255) / 256), WGA_BLOCK, c->stream, d_text, (u64)n_bytes, nh, contigs);
+    LAUNCH_CHECK();
+  }
+  WGA_LAUNCH(k_fa_bases<false>, nb, WGA_BLOCK, c->stream, d_text, (u64)n_bytes, nh, contigs, blk, (const u64*)nullptr,
+             (u8*)nullptr);
+  LAUNCH_CHECK();
+  if ((rc = run_scan_ws(c, sp, nb, blk_off, partial))) return rc;
+  u64 total = 0;
+  RT_CHECK(rt_d2h(&total, blk_off + nb, sizeof total, c->stream));
+  *n_contigs = nh;
+  *pool_bytes = total;
+  if (!d_pool) return WGA_OK;
+  WGA_LAUNCH(k_fa_bases<true>, nb, WGA_BLOCK, c->stream, d_text, (u64)n_bytes, nh, contigs, blk, (const u64*)blk_off, d_pool);
+  LAUNCH_CHECK();
+  if (nh) {
+    WGA_LAUNCH(k_fa_finish, (u32)((nh + 255) / 256), WGA_BLOCK, c->stream, (u64)n_bytes, nh, total, contigs);
+    LAUNCH_CHECK();
+    WGA_LAUNCH(k_fa_lengths, (u32)((nh + 255) / 256), WGA_BLOCK, c->stream, nh, total, contigs);
+    LAUNCH_CHECK();
+  }
+  return WGA_OK;
+}
+
+/* K18: bytes in HBM -> BGZF members (wga_k18_bgzf_deflate.h) */
+static const uint8_t k_bgzf_eof[28] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43,
+                                       0x02, 0, 0x1b, 0, 0x03, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+uint64_t wga_bgzf_bound(uint64_t n_bytes) {
+  const uint64_t members = (n_bytes + WGA_BGZF_IN - 1u) / WGA_BGZF_IN;
+  return n_bytes + members * (uint64_t)(WGA_BGZF_HDR + 5u + WGA_BGZF_TRAILER) + sizeof k_bgzf_eof;
+}
+int wga_bgzf_compress(wga_ctx* c, const uint8_t* d_in, uint64_t n_bytes, uint8_t* d_out, uint64_t out_cap,
+                      uint64_t* out_bytes, int eof_marker) {
+  int rc = ctx_bind(c);
+  if (rc) return rc;
+  if (!out_bytes) return fail(WGA_E_INVALID_ARG, "out_bytes null", nullptr);
+  if (n_bytes && !d_in) return fail(WGA_E_INVALID_ARG, "d_in null", nullptr);
+  const u64 nb64 = (n_bytes + WGA_BGZF_IN - 1u) / WGA_BGZF_IN;
+  if (nb64 > 0x7FFFFFFFull) return fail(WGA_E_INVALID_ARG, "more than 2^31 members in one call", nullptr);
+  const u32 nb = (u32)nb64;
+  const u64 tail = eof_marker ? sizeof k_bgzf_eof : 0u;
+  u64 total = 0;
+  if (nb) {
+    /* scratch: member sizes | their exclusive scan (+ total) | scan partials | crc + kind per member | code lengths */
+    void* ws;
+    const size_t words = (size_t)nb * 2 + 2 + (size_t)nb / 1024 + 4;
+    const size_t head = words * sizeof(u64);
+    const size_t need = head + (size_t)nb * sizeof(wga_bgzf_member) + (size_t)nb * WGA_BGZF_LENS;
+    if ((rc = ctx_scratch(c, need, &ws))) return rc;
+    u64* sizes = (u64*)ws;
+    u64* offs = sizes + nb;
+    u64* partial = offs + nb + 1;
+    wga_bgzf_member* members = (wga_bgzf_member*)((char*)ws + head);
+    u8* lens = (u8*)(members + nb);
+    WGA_LAUNCH(k_bgzf_plan, nb, WGA_BLOCK, c->stream, d_in, (u64)n_bytes, sizes, members, lens);
+    LAUNCH_CHECK();
+    ScanPlain sp;
+    sp.in = sizes;
+    if ((rc = run_scan_ws(c, sp, nb, offs, partial))) return rc;
+    RT_CHECK(rt_d2h(&total, offs + nb, sizeof total, c->stream));
+    *out_bytes = total + tail;
+    if (!d_out) return WGA_OK; /* the count call */
+    if (total + tail > out_cap) return fail(WGA_E_INVALID_ARG, "output buffer smaller than the compressed stream (wga_bgzf_bound)", nullptr);
+    WGA_LAUNCH(k_bgzf_emit, nb, WGA_BLOCK, c->stream, d_in, (u64)n_bytes, (const u64*)offs, (const wga_bgzf_member*)members,
+               (const u8*)lens, d_out);
+    LAUNCH_CHECK();
+  }
+  *out_bytes = total + tail;
+  if (tail && d_out) {
+    if (total + tail > out_cap) return fail(WGA_E_INVALID_ARG, "output buffer smaller than the compressed stream (wga_bgzf_bound)", nullptr);
+    RT_CHECK(rt_h2d(d_out + total, k_bgzf_eof, sizeof k_bgzf_eof, c->stream));
+  }
+  return WGA_OK;
+}
+
+int wga_bgzf_inflate(wga_ctx* c, const uint8_t* d_in, uint64_t in_bytes, uint32_t n_blocks, const wga_bgzf_block* d_blocks,
+                     uint8_t* d_out, uint32_t* d_status) {
+  int rc = ctx_bind(c);
+  if (rc) return rc;
+  if (n_blocks == 0) return WGA_OK;
+  static_assert(sizeof(wga_bgzf_block) == sizeof(wga_bgzf_block_dev) && sizeof(wga_bgzf_block) == 24, "wga_bgzf_block layout");
+  if (!d_in || !d_blocks || !d_out || !d_status) return fail(WGA_E_INVALID_ARG, "null array", nullptr);
+  WGA_LAUNCH(k_bgzf_inflate, (n_blocks + 3u) / 4u, WGA_BLOCK, c->stream, d_in, (u64)in_bytes, n_blocks,
+             (const wga_bgzf_block_dev*)d_blocks, d_out, (u32*)d_status);
+  LAUNCH_CHECK();
+  return WGA_OK;
+}
+
+int wga_pafcov_format(wga_ctx* c, const uint8_t* d_name, uint32_t name_len, const int32_t* d_cov,
+                      uint64_t p0, uint32_t count, uint64_t* d_line_off, uint8_t* d_out) {
+  int rc = ctx_bind(c);
+  if (rc) return rc;
+  if (!d_line_off || (count && !d_cov) || (name_len && !d_name)) return fail(WGA_E_INVALID_ARG, "null array", nullptr);
+  ScanCovLine f;
+  f.cov = (const int*)d_cov;
+  f.p0 = p0;
+  f.name_len = name_len;
+  if (!d_out) return run_scan(c, f, count, (u64*)d_line_off);
+  if (count == 0) return WGA_OK;
+  WGA_LAUNCH(k_pafcov_format, (count + WGA_BED_LINES - 1u) / WGA_BED_LINES, WGA_BLOCK, c->stream, f, count, d_name,
+             (const u64*)d_line_off, d_out);
+  LAUNCH_CHECK();
+  return WGA_OK;
+}
+
+} /* extern "C" */
