@@ -600,6 +600,48 @@ int wga_maf_chunk(wga_ctx*, const uint8_t* d_text, const wga_maf_chunk_row* d_ro
                   const wga_maf_chunk_block* d_blocks, uint64_t n_lines, uint64_t chunk_len, uint64_t* d_carry, void* d_work,
                   uint64_t* text_bytes, uint8_t* d_out);
 
+/* ---- K21: MAF slices for maf-ext (tools/mafextra.rs:167-232 with MAFSLine::get_col_coord parser/maf.rs:81-95,
+ *      MAFRecord::slice_block parser/maf.rs:223-248 and the record writer maf.rs:566-581) ----------------------------------
+ * A HIT is one block cut by one region.  Its rows are d_rows[row0 .. row0 + n_rows), n_rows >= 1, in the block's order.
+ *   whole != 0: the record as it was read: every row with its own start, size field and full text.
+ *   otherwise : row `ord` is the ANCHOR (the row of the region's name) and [cut_lo, cut_hi), cut_lo <= cut_hi, are bases of
+ *     the anchor counted from its start field (cut = region position - start).  col(p) = the index of the anchor's p-th
+ *     (0-based) byte that is not '-', the anchor's length when it has p or fewer such bytes (maf.rs:81-95); so gap columns
+ *     in front of base cut_lo are dropped and, once cut_hi reaches the anchor's non-gap count, every trailing gap column is
+ *     kept.  With [c0, c1) = [col(cut_lo), col(cut_hi)) every row is written with text[c0 .. c1) and start = its start +
+ *     cut_lo (plain addition whatever the row's strand and gaps: maf.rs:229, 239); size = cut_hi - cut_lo for the anchor
+ *     (maf.rs:230) and the slice's bytes that are not '-' for every other row (maf.rs:241-243).
+ * A record is "a score=255\n", one line "s\t<name>\t<start>\t<size>\t<+|->\t<srcSize>\t<text>\n" per row and an empty line.
+ * A sliced hit with a row shorter than c1 is the reference's slice panic (maf.rs:233, 240): the call's text is that of the
+ * hits in front of the first such hit, which *first_short_hit names (~0u: none).
+ * The hits are written in their order; a block may appear in any number of hits; nothing is kept between calls.
+ * Every hit's rows lie inside the table (row0 + n_rows <= n_table_rows, ord < n_rows) and n_hits <= 2^32 - 4: the caller's
+ * contract, not checked.  n_lines = the sum of n_rows over the hits < 2^32; n_cols = the sum of seq_len over the n_table_rows table rows (every
+ * table row gets a rank directory of one entry per 2048 columns: upload the rows that hits name).  d_work =
+ * wga_maf_slice_work_bytes(...) bytes of device memory the two calls share.  Two calls with the same arguments:
+ *   d_out == NULL: directories, cuts, sizes and line lengths; *text_bytes and *first_short_hit (host values; synchronises).
+ *   otherwise     : the text at d_out[0 .. text_bytes). */
+typedef struct {
+  uint64_t seq_off;  /* the row's text: d_text[seq_off .. seq_off + seq_len) */
+  uint64_t seq_len;
+  uint64_t name_off; /* its name: d_text[name_off .. name_off + name_len) */
+  uint64_t start;    /* the input start field */
+  uint64_t size;     /* the input size field (written as it is by a whole hit) */
+  uint64_t src_size; /* the input srcSize field */
+  uint32_t name_len;
+  uint32_t strand_neg;
+} wga_maf_slice_row;
+typedef struct {
+  uint64_t row0;            /* the block's first row in the row table */
+  uint64_t cut_lo, cut_hi;  /* the anchor's bases, relative to its start field */
+  uint32_t n_rows, ord;     /* the block's rows; the anchor's index among them */
+  uint32_t whole, pad;
+} wga_maf_slice_hit;
+uint64_t wga_maf_slice_work_bytes(uint32_t n_hits, uint64_t n_lines, uint64_t n_table_rows, uint64_t n_cols);
+int wga_maf_slice(wga_ctx*, const uint8_t* d_text, const wga_maf_slice_row* d_rows, uint64_t n_table_rows, uint64_t n_cols,
+                  uint32_t n_hits, const wga_maf_slice_hit* d_hits, uint64_t n_lines, void* d_work, uint64_t* text_bytes,
+                  uint32_t* first_short_hit, uint8_t* d_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,4 +1,4 @@
-/* capi_maf.inc — K3 / K4 / K19 / K20: the MAF walks, VCF rows of call on MAF, chunk on MAF.
+/* capi_maf.inc — K3 / K4 / K19 / K20 / K21: the MAF walks, VCF rows of call on MAF, chunk on MAF, maf-ext's slices.
  * A part of wga_capi.cpp (included there: one translation unit). */
 /* K3 / K4: the stream kernel over every block that is not long, then the long blocks piece by piece (wga_k3_maf.h).  Five
  * launches at most, all of them queued whatever the data holds: the table of long blocks is built and sized on the device (its
@@ -184,6 +184,85 @@ int wga_maf_chunk(wga_ctx* c, const uint8_t* d_text, const wga_maf_chunk_row* d_
   WGA_LAUNCH(k_maf_chunk_carry, (nb + 255u) / 256u, WGA_BLOCK, c->stream, d_blocks, nb, (const u64*)bitem, (const u64*)pre,
              (u64*)d_carry);
   LAUNCH_CHECK();
+  return WGA_OK;
+}
+
+/* d_work of K21 in u64 words: header [2] | rows' first directory entries [nr + 1] | stretch counts [E] | their scan [E + 1] |
+ * hits' first lines [nh + 1] | c0 [nh] | c1 [nh] | sizes [n] | line lengths [n] | line offsets [n + 1], with E bounded by
+ * n_cols / 2048 + 2 nr (a row of len columns owns ceil(len / 2048) + 1 entries) */
+static inline uint64_t maf_slice_dir_bound(uint64_t n_table_rows, uint64_t n_cols) {
+  return n_cols / WGA_K21_STRETCH + 2ull * n_table_rows;
+}
+uint64_t wga_maf_slice_work_bytes(uint32_t n_hits, uint64_t n_lines, uint64_t n_table_rows, uint64_t n_cols) {
+  return 8ull * (2ull + (n_table_rows + 1ull) + 2ull * maf_slice_dir_bound(n_table_rows, n_cols) + 1ull + 3ull * (uint64_t)n_hits + 1ull +
+                 3ull * n_lines + 1ull);
+}
+
+int wga_maf_slice(wga_ctx* c, const uint8_t* d_text, const wga_maf_slice_row* d_rows, uint64_t n_table_rows, uint64_t n_cols,
+                  uint32_t n_hits, const wga_maf_slice_hit* d_hits, uint64_t n_lines, void* d_work, uint64_t* text_bytes,
+                  uint32_t* first_short_hit, uint8_t* d_out) {
+  int rc = ctx_bind(c);
+  if (rc) return rc;
+  static_assert(sizeof(wga_maf_slice_row) == 56 && sizeof(wga_maf_slice_hit) == 40, "K21 table layouts");
+  if (n_lines >= 0xFFFFFFFFull) return fail(WGA_E_INVALID_ARG, "a window holds fewer than 2^32 lines", nullptr);
+  const u64 emax = maf_slice_dir_bound(n_table_rows, n_cols);
+  if (n_table_rows >= 0xFFFFFFFFull || emax >= 0xFFFFFFFFull) return fail(WGA_E_INVALID_ARG, "row table too long", nullptr);
+  if (!text_bytes || !first_short_hit || (n_hits && (!d_text || !d_rows || !d_hits || !d_work)))
+    return fail(WGA_E_INVALID_ARG, "null array", nullptr);
+  const u32 n = (u32)n_lines, nh = n_hits, nr = (u32)n_table_rows;
+  K21Hdr* hdr = (K21Hdr*)d_work;
+  u64* dbase = (u64*)d_work + 2;
+  u64* raw = dbase + nr + 1u;
+  u64* G = raw + emax;
+  u64* hline = G + emax + 1u;
+  u64* C0 = hline + nh + 1u;
+  u64* C1 = C0 + nh;
+  u64* sz = C1 + nh;
+  u64* len = sz + n;
+  u64* loff = len + n;
+  if (!d_out) {
+    *text_bytes = 0;
+    *first_short_hit = 0xFFFFFFFFu;
+    if (nh == 0 || n == 0) return WGA_OK;
+    RT_CHECK(rt_memset(hdr, 0xFF, sizeof(K21Hdr), c->stream));
+    ScanSliceDir fd;
+    fd.rows = d_rows;
+    if ((rc = run_scan(c, fd, nr, dbase))) return rc;
+    u64 E = 0;
+    RT_CHECK(rt_d2h(&E, dbase + nr, 8, c->stream));
+    if (E > emax) return fail(WGA_E_INVALID_ARG, "n_cols is smaller than the table rows' columns", nullptr);
+    WGA_LAUNCH(k_maf_slice_rank, WGA_K21_GRID, WGA_BLOCK, c->stream, d_text, d_rows, nr, (const u64*)dbase, raw);
+    LAUNCH_CHECK();
+    ScanPlain f;
+    f.in = raw;
+    if ((rc = run_scan(c, f, (u32)E, G))) return rc;
+    ScanSliceLines fl;
+    fl.hits = d_hits;
+    if ((rc = run_scan(c, fl, nh, hline))) return rc;
+    WGA_LAUNCH(k_maf_slice_select, (nh + 3u) / 4u, WGA_BLOCK, c->stream, d_text, d_rows, d_hits, nh, (const u64*)dbase, (const u64*)G,
+               (const u64*)hline, C0, C1, sz, hdr);
+    LAUNCH_CHECK();
+    WGA_LAUNCH(k_maf_slice_lines, (n + 255u) / 256u, WGA_BLOCK, c->stream, d_rows, d_hits, nh, (const u64*)hline, (const u64*)C0,
+               (const u64*)C1, (const u64*)sz, (const K21Hdr*)hdr, n, len);
+    LAUNCH_CHECK();
+    f.in = len;
+    if ((rc = run_scan(c, f, n, loff))) return rc;
+    u64 total = 0;
+    K21Hdr h;
+    RT_CHECK(rt_d2h(&total, loff + n, 8, c->stream));
+    RT_CHECK(rt_d2h(&h, hdr, sizeof h, c->stream));
+    *text_bytes = total;
+    *first_short_hit = h.first_short;
+    return WGA_OK;
+  }
+  if (nh == 0 || n == 0) return WGA_OK;
+  const u64 tiles = (*text_bytes + WGA_K20_TILE - 1u) / WGA_K20_TILE;
+  if (tiles >= 0x80000000ull) return fail(WGA_E_INVALID_ARG, "window text too long", nullptr);
+  if (tiles) {
+    WGA_LAUNCH(k_maf_slice_fill, (u32)tiles, WGA_BLOCK, c->stream, d_text, d_rows, d_hits, nh, (const u64*)hline, (const u64*)C0,
+               (const u64*)C1, (const u64*)sz, n, (const u64*)loff, d_out);
+    LAUNCH_CHECK();
+  }
   return WGA_OK;
 }
 

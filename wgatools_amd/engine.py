@@ -112,6 +112,11 @@ class Batch:
 MAF_CHUNK_ROW_DTYPE = np.dtype([("seq_off", "<u8"), ("seq_len", "<u8"), ("name_off", "<u8"), ("start", "<u8"),
                                 ("src_size", "<u8"), ("name_len", "<u4"), ("strand_neg", "<u4")])
 MAF_CHUNK_BLOCK_DTYPE = np.dtype([("row0", "<u8"), ("k_lo", "<u8"), ("k_hi", "<u8"), ("n_rows", "<u4"), ("pad", "<u4")])
+# K21 tables (include/wga_hip.h wga_maf_slice_row / wga_maf_slice_hit)
+MAF_SLICE_ROW_DTYPE = np.dtype([("seq_off", "<u8"), ("seq_len", "<u8"), ("name_off", "<u8"), ("start", "<u8"), ("size", "<u8"),
+                                ("src_size", "<u8"), ("name_len", "<u4"), ("strand_neg", "<u4")])
+MAF_SLICE_HIT_DTYPE = np.dtype([("row0", "<u8"), ("cut_lo", "<u8"), ("cut_hi", "<u8"), ("n_rows", "<u4"), ("ord", "<u4"),
+                                ("whole", "<u4"), ("pad", "<u4")])
 VCF_ERR_DTYPE = np.dtype([("item", "<u8"), ("kind", "<u4"), ("ch", "<u4")])
 MAF_VCF_REC_DTYPE = np.dtype([("t_name_off", "<u8"), ("q_name_off", "<u8"), ("t_name_len", "<u4"), ("q_name_len", "<u4"),
                               ("t_start", "<u8"), ("q_start", "<u8"), ("q_size", "<u8"), ("q_neg", "<u4"), ("pad", "<u4")])
@@ -448,6 +453,29 @@ class Engine:
         self._check(self.lib.wga_maf_chunk(*args, _p(out)))
         self.sync()
         return out.numpy()[:int(total.value)].tobytes()
+
+    def maf_slice(self, text, rows, hits):
+        """K21 (mafextra.rs:167-232, maf.rs:223-248): the MAF text of a window of hits.  text / rows: device arrays (rows of
+        MAF_SLICE_ROW_DTYPE, all of them get a rank directory); hits: a host array of MAF_SLICE_HIT_DTYPE.  Returns (the text
+        of the hits in front of the first hit with a short row, that hit's index or None)."""
+        hits = np.ascontiguousarray(hits, dtype=MAF_SLICE_HIT_DTYPE)
+        nh = int(hits.size)
+        n_lines = int(hits["n_rows"].astype(np.uint64).sum()) if nh else 0
+        host_rows = rows.numpy() if nh else np.zeros(0, dtype=MAF_SLICE_ROW_DTYPE)
+        nr, n_cols = int(host_rows.size), int(host_rows["seq_len"].sum()) if host_rows.size else 0
+        d_hits = self.upload(hits) if nh else None
+        work = self.empty(int(self.lib.wga_maf_slice_work_bytes(nh, n_lines, nr, n_cols)), np.uint8)
+        total, short = C.c_uint64(0), C.c_uint32(0)
+        args = (self.ctx, _p(text), _p(rows), nr, n_cols, nh, _p(d_hits), n_lines, _p(work), C.byref(total), C.byref(short))
+        self._check(self.lib.wga_maf_slice(*args, None))
+        guard = 64  # bytes around the text that the fill call must leave alone
+        out = self.upload(np.full(int(total.value) + 2 * guard, 0xA5, dtype=np.uint8))
+        self._check(self.lib.wga_maf_slice(*args, out.ptr + guard))
+        self.sync()
+        got = out.numpy()
+        if not ((got[:guard] == 0xA5).all() and (got[guard + int(total.value):] == 0xA5).all()):
+            raise _lib.WgaError("wga_maf_slice wrote outside d_out[0 .. text_bytes)")
+        return got[guard:guard + int(total.value)].tobytes(), (None if short.value == 0xFFFFFFFF else int(short.value))
 
     def pafpseudo_fill(self, batch, base_mode, q_fa, q_fa_bytes, q_src_off, q_src_len, skip, out,
                        dst_off, diag=None):

@@ -220,6 +220,7 @@ struct MafChunks {
   std::string header;
   std::unique_ptr<BgzfDeviceSource> bgzf; /* a bgzipped input: inflated on the device */
   bool keep_going = false; /* a piece whose host reader fails returns its records in front of the error (MafInput::error) */
+  std::function<void(const std::string&)> on_piece; /* sees every piece's text, the ones without a block too (maf-index: file offsets) */
   explicit MafChunks(const std::string* input) {
     bgzf.reset(new BgzfDeviceSource());
     if (bgzf->open(input))
@@ -301,6 +302,7 @@ struct MafChunks {
       if (!a.ok) return false;
       if (in.text && in.text.use_count() == 1) rd.recycle(std::move(*in.text)); /* nobody else holds the piece the caller is done with */
       read_ahead();
+      if (on_piece) on_piece(a.text);
       in = maf_from_text(d, std::move(a.text), keep_going);
       if (first_seen) header = in.header;
       first_seen = false;

@@ -1,6 +1,8 @@
 /*
  * wga_host.cpp — parsers / writers of the host layer (see wga_host.hpp for the reference map).
  */
+#include <errno.h>
+
 #include "wga_host.hpp"
 
 #include <ctype.h>
@@ -1326,38 +1328,128 @@ struct Json { /* just enough of a JSON reader for tools/index.rs:78-95 */
 };
 }  // namespace
 
+/* the whole index (tools/index.rs:78-95): any key order and white space, unknown keys ignored.  strict: as serde_json
+ * deserializes it for maf-ext — a missing key, a value of another type or a number beyond u64 is "json dese error"; otherwise
+ * (the ##contig lines of `call`) only the JSON itself has to be well formed */
+std::vector<MafIndexItem> parse_maf_index(const std::string& text, bool strict) {
+  std::vector<MafIndexItem> out;
+  auto bad_value = [strict]() {
+    if (strict) fail("json dese error");
+  };
+  auto num = [&](const std::string& v) -> uint64_t {
+    if (v.empty() || v.find_first_not_of("0123456789") != std::string::npos) bad_value();
+    errno = 0;
+    const uint64_t x = strtoull(v.c_str(), nullptr, 10);
+    if (errno == ERANGE) bad_value();
+    return x;
+  };
+  try {
+    Json j(text);
+    j.need('{');
+    if (!j.eat('}')) {
+      do {
+        MafIndexItem it;
+        it.name = j.str();
+        j.need(':');
+        j.need('{');
+        bool has_ivls = false, has_size = false, has_ref = false;
+        if (!j.eat('}')) {
+          do {
+            const std::string key = j.str();
+            j.need(':');
+            if (key == "ivls") {
+              has_ivls = true;
+              it.ivls.clear();
+              j.need('[');
+              if (!j.eat(']')) {
+                do {
+                  MafIndexIvl iv;
+                  unsigned seen = 0;
+                  j.need('{');
+                  if (!j.eat('}')) {
+                    do {
+                      const std::string k = j.str();
+                      j.need(':');
+                      j.ws();
+                      const bool quoted = j.p < text.size() && text[j.p] == '"';
+                      const std::string v = j.skip();
+                      if (k == "start") iv.start = num(quoted ? "" : v), seen |= 1u;
+                      if (k == "end") iv.end = num(quoted ? "" : v), seen |= 2u;
+                      if (k == "offset") iv.offset = num(quoted ? "" : v), seen |= 4u;
+                      if (k == "strand") {
+                        if (!quoted || (v != "+" && v != "-")) bad_value();
+                        iv.neg = v == "-", seen |= 8u;
+                      }
+                    } while (j.eat(','));
+                    j.need('}');
+                  }
+                  if (seen != 15u) bad_value();
+                  it.ivls.push_back(iv);
+                } while (j.eat(','));
+                j.need(']');
+              }
+            } else {
+              j.ws();
+              const bool quoted = j.p < text.size() && text[j.p] == '"';
+              const std::string v = j.skip();
+              if (key == "size") it.size = num(quoted ? "" : v), has_size = true;
+              if (key == "isref") {
+                if (quoted || (v != "true" && v != "false")) bad_value();
+                it.isref = v == "true", has_ref = true;
+              }
+            }
+          } while (j.eat(','));
+          j.need('}');
+        }
+        if (!has_ivls || !has_size || !has_ref) bad_value();
+        out.push_back(std::move(it));
+      } while (j.eat(','));
+      j.need('}');
+    }
+    j.ws();
+    if (j.p != text.size()) bad_value();
+  } catch (Error&) {
+    if (!strict) throw;
+    fail("json dese error");
+  }
+  return out;
+}
+
 std::vector<std::pair<std::string, uint64_t>> maf_index_ref_contigs(const std::string& path) {
   std::vector<std::pair<std::string, uint64_t>> out;
   FILE* f = fopen(path.c_str(), "rb");
   if (!f) return out;
   fclose(f);
-  std::string text = read_all(&path);
-  Json j(text);
-  j.need('{');
-  if (!j.eat('}')) {
-    do {
-      std::string name = j.str();
-      j.need(':');
-      j.need('{');
-      uint64_t size = 0;
-      bool isref = false;
-      if (!j.eat('}')) {
-        do {
-          std::string key = j.str();
-          j.need(':');
-          std::string v = j.skip();
-          if (key == "size") size = strtoull(v.c_str(), nullptr, 10);
-          if (key == "isref") isref = v == "true";
-        } while (j.eat(','));
-        j.need('}');
-      }
-      if (isref) out.emplace_back(name, size);
-    } while (j.eat(','));
-    j.need('}');
-  }
+  for (const MafIndexItem& it : parse_maf_index(read_all(&path), false))
+    if (it.isref) out.emplace_back(it.name, it.size);
   std::stable_sort(out.begin(), out.end(),
                    [](const auto& a, const auto& b) { return natord_compare(a.first, b.first) < 0; });
   return out;
+}
+
+/* a JSON string as serde_json writes it */
+void append_json_string(std::string& s, const std::string& v) {
+  s.push_back('"');
+  for (unsigned char ch : v) {
+    switch (ch) {
+      case '"': s += "\\\""; break;
+      case '\\': s += "\\\\"; break;
+      case '\n': s += "\\n"; break;
+      case '\r': s += "\\r"; break;
+      case '\t': s += "\\t"; break;
+      case '\b': s += "\\b"; break;
+      case '\f': s += "\\f"; break;
+      default:
+        if (ch < 0x20) {
+          char b[8];
+          snprintf(b, sizeof b, "\\u%04x", ch);
+          s += b;
+        } else {
+          s.push_back((char)ch);
+        }
+    }
+  }
+  s.push_back('"');
 }
 
 /* ------------------------------------------------------------------------------------------ */

@@ -161,6 +161,21 @@ std::vector<MafRecord> parse_maf(const std::string& text, std::string* header, s
  * the entries with isref, natord-sorted (caller.rs:340-357).  Missing file -> empty. */
 std::vector<std::pair<std::string, uint64_t>> maf_index_ref_contigs(const std::string& path);
 
+/* the whole index: every name's intervals in file order; unknown keys are ignored.  strict (maf-ext): "json dese error" when
+ * it does not deserialize (missing key, wrong type, a number beyond u64); otherwise only malformed JSON is an error */
+struct MafIndexIvl {
+  uint64_t start = 0, end = 0, offset = 0;
+  bool neg = false;
+};
+struct MafIndexItem {
+  std::string name;
+  std::vector<MafIndexIvl> ivls;
+  uint64_t size = 0;
+  bool isref = false;
+};
+std::vector<MafIndexItem> parse_maf_index(const std::string& text, bool strict);
+void append_json_string(std::string& s, const std::string& v); /* serde_json's escaping */
+
 /* ---- chain ---------------------------------------------------------------------------------- */
 struct ChainRecord { /* chain.rs:49-55,76-91: header fields + data lines */
   std::string target_name, query_name;

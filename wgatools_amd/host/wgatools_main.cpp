@@ -1073,8 +1073,11 @@ uint32_t expand_batch(Dev& d, const wga_cigar_batch& cb, const ExpandJob& j, con
 
 #include "cmd_chunk.inc"
 
+void log_warn(const std::string& msg);
+#include "cmd_ext.inc"
+
 /* ---- command line (cli.rs) -------------------------------------------------------------------------- */
-void log_error(const std::string& msg) {
+static void log_line(const char* level, const std::string& msg) {
   struct timespec ts;
   clock_gettime(CLOCK_REALTIME, &ts);
   struct tm tmv;
@@ -1082,8 +1085,10 @@ void log_error(const std::string& msg) {
   char d[64], z[16];
   strftime(d, sizeof d, "%Y-%m-%dT%H:%M:%S", &tmv);
   strftime(z, sizeof z, "%z", &tmv);
-  fprintf(stderr, "%s.%09ld%.3s:%.2s ERROR %s\n", d, ts.tv_nsec, z, z + 3, msg.c_str());
+  fprintf(stderr, "%s.%09ld%.3s:%.2s %s %s\n", d, ts.tv_nsec, z, z + 3, level, msg.c_str());
 }
+void log_error(const std::string& msg) { log_line("ERROR", msg); }
+void log_warn(const std::string& msg) { log_line("WARN", msg); }
 
 void usage() {
   fprintf(stderr,
@@ -1102,7 +1107,9 @@ void usage() {
           "  chain2maf | c2m [CHAIN] --target TARGET.fa --query QUERY.fa   (-g / -q)\n"
           "  call    | c    [MAF] [-s] [-i] [-l SVLEN] [-n SAMPLE] [--query-name N | --query-regex R] [-c CHUNK]\n"
           "  call    | c    -f paf [PAF] --target T.fa --query Q.fa [-s] [-l SVLEN] [-n SAMPLE]\n"
-          "  chunk   | ch   [MAF] -l LENGTH\n");
+          "  chunk   | ch   [MAF] -l LENGTH\n"
+          "  maf-index | mi <MAF>                     (writes <MAF>.index, or -o PATH)\n"
+          "  maf-ext | me   <MAF> [-r CHR:START-END,...] [-f REGIONS.tsv]   (needs <MAF>.index; -r here is the region list)\n");
 }
 
 }  // namespace
@@ -1122,7 +1129,7 @@ static int run_command(int argc, char** argv) {
         outfile = val("--outfile");
       else if (a.compare(0, 10, "--outfile=") == 0)
         outfile = a.substr(10);
-      else if (a == "-r" || a == "--rewrite")
+      else if ((a == "-r" && cmd != "maf-ext" && cmd != "me") || a == "--rewrite") /* behind maf-ext, -r is its region list */
         rewrite = true;
       else if (a == "-t" || a == "--threads")
         (void)val("--threads");
@@ -1267,6 +1274,10 @@ static int run_command(int argc, char** argv) {
     const bool validate = cmd == "validate" || cmd == "vf";
     const bool dotp = cmd == "dotplot" || cmd == "dp";
     const bool chunk = cmd == "chunk" || cmd == "ch";
+    const bool ext = cmd == "maf-ext" || cmd == "me";
+    std::vector<std::string> ext_regions;
+    std::string ext_file;
+    bool has_ext_regions = false, has_ext_file = false;
     std::string length_s;
     bool has_length = false;
     std::string out_format = "html", mode = "base-level";
@@ -1281,7 +1292,19 @@ static int run_command(int argc, char** argv) {
         return rest[++i];
       };
       bool conv = cmd == "paf2maf" || cmd == "p2m" || cmd == "chain2maf" || cmd == "c2m";
-      if (a == "-g" || a == "--target")
+      if (ext && (a == "-r" || a == "--regions")) { /* mafextra: a comma-separated list (clap value_delimiter) */
+        const std::string v = val();
+        has_ext_regions = true;
+        for (size_t b = 0;;) {
+          const size_t e = v.find(',', b);
+          ext_regions.push_back(v.substr(b, e == std::string::npos ? e : e - b));
+          if (e == std::string::npos) break;
+          b = e + 1;
+        }
+      } else if (ext && (a == "-f" || a == "--file")) {
+        ext_file = val();
+        has_ext_file = true;
+      } else if (a == "-g" || a == "--target")
         target = val();
       else if ((a == "-q" || a == "--query") && (conv || call))
         query = val();
@@ -1331,7 +1354,7 @@ static int run_command(int argc, char** argv) {
         query_regex = val();
         has_regex = true;
       }
-      else if (a[0] != '-' && !has_input) {
+      else if ((a[0] != '-' || (ext && a == "-")) && !has_input) {
         input_s = a;
         has_input = true;
       } else
@@ -1399,6 +1422,9 @@ static int run_command(int argc, char** argv) {
       out.open(outfile, rewrite);
       return cmd_pafcov(input, out, g_spread);
     }
+    if (cmd == "maf-index" || cmd == "mi") return cmd_maf_index(input, outfile);
+    if (ext)
+      return cmd_maf_ext(input, has_ext_regions ? &ext_regions : nullptr, has_ext_file ? &ext_file : nullptr, outfile, rewrite);
     if (chunk) { /* utils.rs:656-677: the length is checked before any file is opened, then the output is created, then the input */
       if (!has_length) fail("the following required arguments were not provided: --length <LENGTH>");
       errno = 0;
