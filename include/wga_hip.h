@@ -642,6 +642,42 @@ int wga_maf_slice(wga_ctx*, const uint8_t* d_text, const wga_maf_slice_row* d_ro
                   uint32_t n_hits, const wga_maf_slice_hit* d_hits, uint64_t n_lines, void* d_work, uint64_t* text_bytes,
                   uint32_t* first_short_hit, uint8_t* d_out);
 
+/* ---- K22: MAF block rewriter for filter and rename (tools/filter.rs:65-105, tools/rename.rs:7-23 with MAFRecord::rename
+ *      parser/maf.rs:250-261 and the record writer maf.rs:566-581) ----------------------------------------------------------
+ * A call works on a WINDOW: the blocks d_blocks[0 .. n_blocks) in that order, block b being the rows d_rows[row0 .. row0 +
+ * n_rows) of the row table (K21's wga_maf_slice_row; every block's rows lie inside the table: the caller's contract).  Every
+ * block that is KEPT is written as "a score=255\n", one line "s\t<prefix><name>\t<start>\t<size>\t<+|->\t<srcSize>\t<text>\n"
+ * per row and an empty line: start, size and srcSize are the table's fields in decimal (the size is not recounted from the
+ * text), the text is d_text[seq_off .. seq_off + seq_len).
+ *   filter != 0: a block is dropped when its first row's size is below min_block_size or its second row's src_size is below
+ *     min_query_size (filter.rs:96-101: both compare with `<`); a block with fewer than two rows is BAD (the reference indexes
+ *     slines[1] before it compares: maf.rs:430).
+ *   n_prefix != 0: row r's name is written behind prefix r, d_prefix_text[d_prefix_off[r] .. d_prefix_off[r + 1]) (an empty
+ *     prefix is legal); a block whose n_rows differs from n_prefix is BAD (maf.rs:252-254).
+ *   With neither set every block is kept as it is; a block of no rows is dropped.
+ * The call's text is that of the kept blocks in front of the first bad block, which *first_bad_block names (~0u: none);
+ * *n_kept counts them.  The selection is made on the device from the row table: the host does not look at a block again.
+ * n_lines = the sum of n_rows over the window's blocks < 2^32.  d_work = wga_maf_rewrite_work_bytes(n_blocks, n_lines) bytes of
+ * device memory the two calls share; d_out is 16-byte aligned.  Two calls with the same arguments, nothing else is kept:
+ *   d_out == NULL: selection, places and line lengths; *text_bytes, *n_kept, *first_bad_block (host values; synchronises).
+ *   otherwise     : the text at d_out[0 .. text_bytes); *text_bytes and *n_kept are read as the first call left them.
+ * n_blocks == 0, or nothing kept: *text_bytes = 0 and success. */
+typedef struct {
+  uint64_t row0; /* the block's first row in the row table */
+  uint32_t n_rows, pad;
+} wga_maf_rewrite_block;
+typedef struct {
+  uint64_t min_block_size, min_query_size; /* used when filter != 0 */
+  uint32_t filter;                         /* 0: keep every block (rename) */
+  uint32_t n_prefix;                       /* 0: no prefixes (filter); else every block must have n_prefix rows */
+  const uint8_t* d_prefix_text;            /* the prefixes' bytes */
+  const uint32_t* d_prefix_off;            /* n_prefix + 1 offsets into d_prefix_text */
+} wga_maf_rewrite_params;
+uint64_t wga_maf_rewrite_work_bytes(uint32_t n_blocks, uint64_t n_lines);
+int wga_maf_rewrite(wga_ctx*, const uint8_t* d_text, const wga_maf_slice_row* d_rows, uint32_t n_blocks,
+                    const wga_maf_rewrite_block* d_blocks, uint64_t n_lines, const wga_maf_rewrite_params* params, void* d_work,
+                    uint64_t* text_bytes, uint32_t* n_kept, uint32_t* first_bad_block, uint8_t* d_out);
+
 #ifdef __cplusplus
 }
 #endif

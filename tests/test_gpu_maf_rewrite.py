@@ -1,0 +1,90 @@
+"""`filter` and `rename` on a real GPU: the `wgatools` binary over libwgahip.so (K22) and the C-ABI entry, the cases of
+test_emu_maf_rewrite.py."""
+import os
+import pytest
+
+from wgatools_amd import build
+import maf_rewrite_cases as mr
+
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def cli():
+    if not os.path.exists(build.CLI_BIN):
+        build.build_cli()
+    return build.CLI_BIN
+
+
+@pytest.fixture(scope="module")
+def eng(gpu):
+    return gpu
+
+
+def test_rewrite_abi_line_ends_at_tile_edge(eng):
+    mr.check_abi_line_ends_at_tile_edge(eng)
+
+
+def test_rewrite_abi_fields_straddle_tile_edge(eng):
+    mr.check_abi_fields_straddle_tile_edge(eng)
+
+
+def test_rewrite_abi_long_row_between_short_blocks(eng):
+    mr.check_abi_long_row_between_short_blocks(eng)
+
+
+def test_rewrite_abi_many_lines_per_tile(eng):
+    mr.check_abi_many_lines_per_tile(eng)
+
+
+def test_rewrite_abi_thresholds_and_drops(eng):
+    mr.check_abi_thresholds(eng)
+
+
+def test_rewrite_abi_wide_numbers(eng):
+    mr.check_abi_wide_numbers(eng)
+
+
+def test_rewrite_abi_bad_blocks(eng):
+    mr.check_abi_bad_blocks(eng)
+
+
+def test_rewrite_abi_prefixes(eng):
+    mr.check_abi_prefixes(eng)
+
+
+def test_rewrite_abi_random_blocks(eng):
+    mr.check_abi_random(eng)
+
+
+def test_filter_and_rename_fixture(cli):
+    mr.check_fixture(cli)
+
+
+def test_filter_random_files_readers_pieces_windows(cli, tmp_path):
+    mr.check_filter_random_files(cli, tmp_path)
+
+
+def test_rename_random_files_readers_pieces_windows(cli, tmp_path):
+    mr.check_rename_random_files(cli, tmp_path)
+
+
+def test_filter_and_rename_empty_inputs(cli, tmp_path):
+    mr.check_empty_inputs(cli, tmp_path)
+
+
+def test_filter_and_rename_bad_blocks_and_reader_errors(cli, tmp_path):
+    mr.check_bad_blocks(cli, tmp_path)
+
+
+def test_filter_and_rename_argument_errors(cli, tmp_path):
+    mr.check_errors(cli, tmp_path)
+
+
+def test_filter_paf(cli, tmp_path):
+    mr.check_paf(cli, tmp_path)
+
+
+def test_filter_chain(cli, tmp_path):
+    mr.check_chain(cli, tmp_path)

@@ -1,4 +1,5 @@
-/* capi_maf.inc — K3 / K4 / K19 / K20 / K21: the MAF walks, VCF rows of call on MAF, chunk on MAF, maf-ext's slices.
+/* capi_maf.inc — K3 / K4 / K19 / K20 / K21 / K22: the MAF walks, VCF rows of call on MAF, chunk on MAF, maf-ext's slices, the
+ * block rewriter of filter and rename.
  * A part of wga_capi.cpp (included there: one translation unit). */
 /* K3 / K4: the stream kernel over every block that is not long, then the long blocks piece by piece (wga_k3_maf.h).  Five
  * launches at most, all of them queued whatever the data holds: the table of long blocks is built and sized on the device (its
@@ -263,6 +264,79 @@ int wga_maf_slice(wga_ctx* c, const uint8_t* d_text, const wga_maf_slice_row* d_
                (const u64*)C1, (const u64*)sz, n, (const u64*)loff, d_out);
     LAUNCH_CHECK();
   }
+  return WGA_OK;
+}
+
+/* d_work of K22 in u64 words: header [2] | kept blocks' places [nb + 1] | their first lines [nb + 1] | line lengths [n] | line
+ * offsets [n + 1] | keep flags, u32 [nb] | the list of kept blocks, u32 [nb] */
+uint64_t wga_maf_rewrite_work_bytes(uint32_t n_blocks, uint64_t n_lines) {
+  return 8ull * (2ull + 2ull * ((uint64_t)n_blocks + 1ull) + 2ull * n_lines + 1ull + (uint64_t)n_blocks + 1ull);
+}
+
+int wga_maf_rewrite(wga_ctx* c, const uint8_t* d_text, const wga_maf_slice_row* d_rows, uint32_t n_blocks,
+                    const wga_maf_rewrite_block* d_blocks, uint64_t n_lines, const wga_maf_rewrite_params* params, void* d_work,
+                    uint64_t* text_bytes, uint32_t* n_kept, uint32_t* first_bad_block, uint8_t* d_out) {
+  int rc = ctx_bind(c);
+  if (rc) return rc;
+  static_assert(sizeof(wga_maf_rewrite_block) == 16 && sizeof(wga_maf_rewrite_params) == 40, "K22 table layouts");
+  if (n_lines >= 0xFFFFFFFFull) return fail(WGA_E_INVALID_ARG, "a window holds fewer than 2^32 lines", nullptr);
+  if (!params || !text_bytes || !n_kept || !first_bad_block || (n_blocks && (!d_text || !d_rows || !d_blocks || !d_work)))
+    return fail(WGA_E_INVALID_ARG, "null array", nullptr);
+  if (params->n_prefix && (!params->d_prefix_text || !params->d_prefix_off))
+    return fail(WGA_E_INVALID_ARG, "prefixes without their text", nullptr);
+  const u32 n = (u32)n_lines, nb = n_blocks;
+  const wga_maf_rewrite_params P = *params;
+  K22Hdr* hdr = (K22Hdr*)d_work;
+  u64* kidx = (u64*)d_work + 2;
+  u64* kline = kidx + nb + 1u;
+  u64* len = kline + nb + 1u;
+  u64* loff = len + n;
+  u32* keep = (u32*)(loff + n + 1u);
+  u32* klist = keep + nb;
+  if (!d_out) {
+    *text_bytes = 0;
+    *n_kept = 0;
+    *first_bad_block = 0xFFFFFFFFu;
+    if (nb == 0) return WGA_OK;
+    RT_CHECK(rt_memset(hdr, 0xFF, sizeof(K22Hdr), c->stream));
+    WGA_LAUNCH(k_maf_rewrite_select, (nb + 255u) / 256u, WGA_BLOCK, c->stream, d_rows, d_blocks, nb, P, keep, hdr);
+    LAUNCH_CHECK();
+    ScanRewriteKept fk;
+    fk.keep = keep;
+    fk.hdr = hdr;
+    if ((rc = run_scan(c, fk, nb, kidx))) return rc;
+    WGA_LAUNCH(k_maf_rewrite_compact, (nb + 255u) / 256u, WGA_BLOCK, c->stream, (const u64*)kidx, nb, klist);
+    LAUNCH_CHECK();
+    ScanRewriteRows fr;
+    fr.blocks = d_blocks;
+    fr.klist = klist;
+    fr.n_kept = kidx + nb;
+    if ((rc = run_scan(c, fr, nb, kline))) return rc;
+    if (n) {
+      WGA_LAUNCH(k_maf_rewrite_lines, (n + 255u) / 256u, WGA_BLOCK, c->stream, d_rows, d_blocks, nb, (const u32*)klist,
+                 (const u64*)kidx, (const u64*)kline, P, n, len);
+      LAUNCH_CHECK();
+    }
+    ScanPlain f;
+    f.in = len;
+    if ((rc = run_scan(c, f, n, loff))) return rc;
+    u64 total = 0, nk = 0;
+    K22Hdr h;
+    RT_CHECK(rt_d2h(&total, loff + n, 8, c->stream));
+    RT_CHECK(rt_d2h(&nk, kidx + nb, 8, c->stream));
+    RT_CHECK(rt_d2h(&h, hdr, sizeof h, c->stream));
+    *text_bytes = total;
+    *n_kept = (u32)nk;
+    *first_bad_block = h.first_bad;
+    return WGA_OK;
+  }
+  if (nb == 0 || *n_kept == 0 || *text_bytes == 0) return WGA_OK;
+  if (*n_kept > nb) return fail(WGA_E_INVALID_ARG, "n_kept is not the count call's", nullptr);
+  const u64 tiles = (*text_bytes + WGA_K20_TILE - 1u) / WGA_K20_TILE;
+  if (tiles >= 0x80000000ull) return fail(WGA_E_INVALID_ARG, "window text too long", nullptr);
+  WGA_LAUNCH(k_maf_rewrite_fill, (u32)tiles, WGA_BLOCK, c->stream, d_text, d_rows, d_blocks, nb, (const u32*)klist, *n_kept,
+             (const u64*)kline, P, (const u64*)loff, (u64)*text_bytes, d_out);
+  LAUNCH_CHECK();
   return WGA_OK;
 }
 

@@ -241,6 +241,34 @@ struct K20Clip { /* writes into the tile image, dropping what falls outside it *
     for (u32 e = 0; e < nd; e++) put(d[e]);
   }
 };
+/* the slices of a tile's lines into its image, 16-byte group by group (line j's slice is [lo[j], hi[j]) of the tile, its bytes
+ * start at text + src[j]): the first line whose slice ends behind the group's start, then the lines from there; one unaligned
+ * 16-byte load + one aligned LDS store when a group lies inside one slice, bytes at slice ends */
+__device__ __forceinline__ void k20_tile_slices(u8* tbuf, u32 tl, u32 nl, const u32* s_lo, const u32* s_hi, const u64* s_src,
+                                                const u8* __restrict__ text, u32 tid) {
+  const u32 ng = (tl + 15u) >> 4;
+  for (u32 gi = tid; gi < ng; gi += 256u) {
+    const u32 a = 16u * gi, e = a + 16u < tl ? a + 16u : tl;
+    u32 lo = 0u, hi = nl; /* first j with s_hi[j] > a */
+    while (lo < hi) {
+      const u32 mid = (lo + hi) >> 1;
+      if (s_hi[mid] > a)
+        hi = mid;
+      else
+        lo = mid + 1u;
+    }
+    u32 j = lo;
+    if (j < nl && s_lo[j] <= a && s_hi[j] >= a + 16u) {
+      *(u32x4_a16*)(tbuf + a) = *(const u32x4_a1*)(text + s_src[j] + (a - s_lo[j]));
+      continue;
+    }
+    for (; j < nl && s_lo[j] < e; j++) {
+      const u32 x0 = s_lo[j] > a ? s_lo[j] : a, x1 = s_hi[j] < e ? s_hi[j] : e;
+      const u8* src = text + s_src[j] - s_lo[j];
+      for (u32 x = x0; x < x1; x++) tbuf[x] = src[x];
+    }
+  }
+}
 __global__ __launch_bounds__(256) void k_maf_chunk_fill(const u8* __restrict__ text, const wga_maf_chunk_row* __restrict__ rows,
                                                         const wga_maf_chunk_block* __restrict__ blocks, u32 nb,
                                                         const u64* __restrict__ bitem, const u64* __restrict__ pre,
@@ -306,29 +334,7 @@ __global__ __launch_bounds__(256) void k_maf_chunk_fill(const u8* __restrict__ t
     if (l.r + 1u == l.k.n_rows) c.put((u8)'\n');
   }
   __syncthreads();
-  /* the slices, 16-byte group by group: the first line whose slice ends behind the group's start, then the lines from there */
-  const u32 ng = (tl + 15u) >> 4;
-  for (u32 gi = tid; gi < ng; gi += 256u) {
-    const u32 a = 16u * gi, e = a + 16u < tl ? a + 16u : tl;
-    u32 lo = 0u, hi = nl; /* first j with s_hi[j] > a */
-    while (lo < hi) {
-      const u32 mid = (lo + hi) >> 1;
-      if (s_hi[mid] > a)
-        hi = mid;
-      else
-        lo = mid + 1u;
-    }
-    u32 j = lo;
-    if (j < nl && s_lo[j] <= a && s_hi[j] >= a + 16u) {
-      *(u32x4_a16*)(tbuf + a) = *(const u32x4_a1*)(text + s_src[j] + (a - s_lo[j]));
-      continue;
-    }
-    for (; j < nl && s_lo[j] < e; j++) {
-      const u32 x0 = s_lo[j] > a ? s_lo[j] : a, x1 = s_hi[j] < e ? s_hi[j] : e;
-      const u8* src = text + s_src[j] - s_lo[j];
-      for (u32 x = x0; x < x1; x++) tbuf[x] = src[x];
-    }
-  }
+  k20_tile_slices(tbuf, tl, nl, s_lo, s_hi, s_src, text, tid);
   __syncthreads();
   lds_text_flush(tbuf, 0u, tl, out + T0, tid, 256u);
 }

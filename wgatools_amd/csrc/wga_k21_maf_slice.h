@@ -25,7 +25,7 @@
 #ifndef WGA_K21_MAF_SLICE_H
 #define WGA_K21_MAF_SLICE_H
 
-#include "wga_k20_maf_chunk.h" /* k20_find, k20_find_in, K20Clip, WGA_K20_TILE, WGA_K20_TILE_LINES */
+#include "wga_k20_maf_chunk.h" /* k20_find, k20_find_in, K20Clip, k20_tile_slices, WGA_K20_TILE, WGA_K20_TILE_LINES */
 
 #define WGA_K21_STRETCH 2048u /* columns of one directory entry = one wave step */
 #ifndef WGA_K21_GRID
@@ -277,29 +277,7 @@ __global__ __launch_bounds__(256) void k_maf_slice_fill(const u8* __restrict__ t
     if (l.r + 1u == l.n_rows) c.put((u8)'\n');
   }
   __syncthreads();
-  /* the slices, 16-byte group by group: the first line whose slice ends behind the group's start, then the lines from there */
-  const u32 ng = (tl + 15u) >> 4;
-  for (u32 gi = tid; gi < ng; gi += 256u) {
-    const u32 a = 16u * gi, e = a + 16u < tl ? a + 16u : tl;
-    u32 lo = 0u, hi = nl; /* first j with s_hi[j] > a */
-    while (lo < hi) {
-      const u32 mid = (lo + hi) >> 1;
-      if (s_hi[mid] > a)
-        hi = mid;
-      else
-        lo = mid + 1u;
-    }
-    u32 j = lo;
-    if (j < nl && s_lo[j] <= a && s_hi[j] >= a + 16u) {
-      *(u32x4_a16*)(tbuf + a) = *(const u32x4_a1*)(text + s_src[j] + (a - s_lo[j]));
-      continue;
-    }
-    for (; j < nl && s_lo[j] < e; j++) {
-      const u32 x0 = s_lo[j] > a ? s_lo[j] : a, x1 = s_hi[j] < e ? s_hi[j] : e;
-      const u8* src = text + s_src[j] - s_lo[j];
-      for (u32 x = x0; x < x1; x++) tbuf[x] = src[x];
-    }
-  }
+  k20_tile_slices(tbuf, tl, nl, s_lo, s_hi, s_src, text, tid);
   __syncthreads();
   lds_text_flush(tbuf, 0u, tl, out + T0, tid, 256u);
 }

@@ -117,6 +117,10 @@ MAF_SLICE_ROW_DTYPE = np.dtype([("seq_off", "<u8"), ("seq_len", "<u8"), ("name_o
                                 ("src_size", "<u8"), ("name_len", "<u4"), ("strand_neg", "<u4")])
 MAF_SLICE_HIT_DTYPE = np.dtype([("row0", "<u8"), ("cut_lo", "<u8"), ("cut_hi", "<u8"), ("n_rows", "<u4"), ("ord", "<u4"),
                                 ("whole", "<u4"), ("pad", "<u4")])
+# K22 tables (include/wga_hip.h wga_maf_rewrite_block / wga_maf_rewrite_params; the rows are K21's)
+MAF_REWRITE_BLOCK_DTYPE = np.dtype([("row0", "<u8"), ("n_rows", "<u4"), ("pad", "<u4")])
+MAF_REWRITE_PARAMS_DTYPE = np.dtype([("min_block_size", "<u8"), ("min_query_size", "<u8"), ("filter", "<u4"), ("n_prefix", "<u4"),
+                                     ("d_prefix_text", "<u8"), ("d_prefix_off", "<u8")])
 VCF_ERR_DTYPE = np.dtype([("item", "<u8"), ("kind", "<u4"), ("ch", "<u4")])
 MAF_VCF_REC_DTYPE = np.dtype([("t_name_off", "<u8"), ("q_name_off", "<u8"), ("t_name_len", "<u4"), ("q_name_len", "<u4"),
                               ("t_start", "<u8"), ("q_start", "<u8"), ("q_size", "<u8"), ("q_neg", "<u4"), ("pad", "<u4")])
@@ -476,6 +480,39 @@ class Engine:
         if not ((got[:guard] == 0xA5).all() and (got[guard + int(total.value):] == 0xA5).all()):
             raise _lib.WgaError("wga_maf_slice wrote outside d_out[0 .. text_bytes)")
         return got[guard:guard + int(total.value)].tobytes(), (None if short.value == 0xFFFFFFFF else int(short.value))
+
+    def maf_rewrite(self, text, rows, blocks, min_block_size=None, min_query_size=None, prefixes=None):
+        """K22 (filter.rs:65-105, rename.rs, maf.rs:250-261): the MAF text of a window of blocks.  text / rows: device arrays
+        (rows of MAF_SLICE_ROW_DTYPE); blocks: a host array of MAF_REWRITE_BLOCK_DTYPE.  The filter is on when either threshold
+        is given (the other one is 0); prefixes: a list of bytes, one per row of every block.  Returns (the text of the kept
+        blocks in front of the first bad block, the number of them, that block's index or None)."""
+        blocks = np.ascontiguousarray(blocks, dtype=MAF_REWRITE_BLOCK_DTYPE)
+        nb = int(blocks.size)
+        n_lines = int(blocks["n_rows"].astype(np.uint64).sum()) if nb else 0
+        d_blocks = self.upload(blocks) if nb else None
+        par = np.zeros(1, dtype=MAF_REWRITE_PARAMS_DTYPE)
+        if min_block_size is not None or min_query_size is not None:
+            par["filter"] = 1
+            par["min_block_size"], par["min_query_size"] = int(min_block_size or 0), int(min_query_size or 0)
+        if prefixes:
+            off = np.cumsum([0] + [len(p) for p in prefixes]).astype(np.uint32)
+            d_ptext = self.upload(np.frombuffer(b"".join(prefixes) + b"\0" * 16, dtype=np.uint8))
+            d_poff = self.upload(off)
+            par["n_prefix"], par["d_prefix_text"], par["d_prefix_off"] = len(prefixes), d_ptext.ptr, d_poff.ptr
+        work = self.empty(int(self.lib.wga_maf_rewrite_work_bytes(nb, n_lines)), np.uint8)
+        total, kept, bad = C.c_uint64(0), C.c_uint32(0), C.c_uint32(0)
+        args = (self.ctx, _p(text), _p(rows), nb, _p(d_blocks), n_lines, par.ctypes.data, _p(work), C.byref(total), C.byref(kept),
+                C.byref(bad))
+        self._check(self.lib.wga_maf_rewrite(*args, None))
+        guard = 64  # bytes around the text that the fill call must leave alone
+        out = self.upload(np.full(int(total.value) + 2 * guard, 0xA5, dtype=np.uint8))
+        self._check(self.lib.wga_maf_rewrite(*args, out.ptr + guard))
+        self.sync()
+        got = out.numpy()
+        if not ((got[:guard] == 0xA5).all() and (got[guard + int(total.value):] == 0xA5).all()):
+            raise _lib.WgaError("wga_maf_rewrite wrote outside d_out[0 .. text_bytes)")
+        return (got[guard:guard + int(total.value)].tobytes(), int(kept.value),
+                None if bad.value == 0xFFFFFFFF else int(bad.value))
 
     def pafpseudo_fill(self, batch, base_mode, q_fa, q_fa_bytes, q_src_off, q_src_len, skip, out,
                        dst_off, diag=None):

@@ -695,6 +695,14 @@ std::string format_f64(double f) {
   return out;
 }
 
+std::string format_chain_score(double f) {
+  if (std::isnan(f)) return "NaN";
+  if (std::isinf(f)) return f < 0 ? "-inf" : "inf";
+  char buf[400]; /* 1.8e308 in positional notation is 309 digits */
+  const std::to_chars_result r = std::to_chars(buf, buf + sizeof buf, f, std::chars_format::fixed);
+  return std::string(buf, r.ptr);
+}
+
 void append_csv_field(std::string& s, const std::string& f, char delim) {
   bool need = false;
   for (char c : f)
@@ -1087,6 +1095,7 @@ std::vector<ChainRecord> parse_chain(const std::string& text, std::string* err) 
           *err = "Parse `" + f[0] + "` Into Float Error";
           return out;
         }
+        r.score = strtod(f[0].c_str(), nullptr); /* correctly rounded, as f64::from_str; the syntax is valid_f64's */
       } else if (k == 1) {
         r.target_name = f[1];
       } else if (k == 6) {

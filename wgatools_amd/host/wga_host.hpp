@@ -183,6 +183,7 @@ struct ChainRecord { /* chain.rs:49-55,76-91: header fields + data lines */
   uint64_t query_size = 0, query_start = 0, query_end = 0;
   bool target_neg = false, query_neg = false;
   uint64_t chain_id = 0;
+  double score = 0.0; /* the header's first field (filter writes it back; the converters do not use it) */
   std::vector<uint64_t> lines; /* 3 per data line: size, 2nd column (query_diff), 3rd column (target_diff) */
 };
 /* ChainRecords::next + chain_parser (chain.rs:58-73,206-383) with nom's behaviour: records start at
@@ -211,6 +212,9 @@ void append_u64(std::string& s, uint64_t v);
 /* ryu::Buffer::format(f32) as used by csv's serializer */
 std::string format_f32(float f);
 std::string format_f64(double f);
+/* f64's Display (a chain header's score, chain.rs:185-203): the shortest digits that read back as the same value, positional,
+ * never an exponent; `255` for 255.0, `inf` / `-inf` / `NaN` */
+std::string format_chain_score(double f);
 /* csv writer, QuoteStyle::Necessary */
 void append_csv_field(std::string& s, const std::string& f, char delim);
 /* natord::compare (natural order, digit runs numeric) */

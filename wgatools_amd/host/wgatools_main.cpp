@@ -1076,6 +1076,10 @@ uint32_t expand_batch(Dev& d, const wga_cigar_batch& cb, const ExpandJob& j, con
 void log_warn(const std::string& msg);
 #include "cmd_ext.inc"
 
+#include "cmd_filter.inc"
+
+#include "cmd_rename.inc"
+
 /* ---- command line (cli.rs) -------------------------------------------------------------------------- */
 static void log_line(const char* level, const std::string& msg) {
   struct timespec ts;
@@ -1109,7 +1113,9 @@ void usage() {
           "  call    | c    -f paf [PAF] --target T.fa --query Q.fa [-s] [-l SVLEN] [-n SAMPLE]\n"
           "  chunk   | ch   [MAF] -l LENGTH\n"
           "  maf-index | mi <MAF>                     (writes <MAF>.index, or -o PATH)\n"
-          "  maf-ext | me   <MAF> [-r CHR:START-END,...] [-f REGIONS.tsv]   (needs <MAF>.index; -r here is the region list)\n");
+          "  maf-ext | me   <MAF> [-r CHR:START-END,...] [-f REGIONS.tsv]   (needs <MAF>.index; -r here is the region list)\n"
+          "  filter  | fl   [FILE] [-f maf|paf|chain] [-b MIN_BLOCK_SIZE] [-q MIN_QUERY_SIZE] [-a MIN_ALIGN_SIZE]   (-a: paf only)\n"
+          "  rename  | rn   [MAF] -p PREFIX1,PREFIX2,...\n");
 }
 
 }  // namespace
@@ -1275,6 +1281,20 @@ static int run_command(int argc, char** argv) {
     const bool dotp = cmd == "dotplot" || cmd == "dp";
     const bool chunk = cmd == "chunk" || cmd == "ch";
     const bool ext = cmd == "maf-ext" || cmd == "me";
+    const bool filt = cmd == "filter" || cmd == "fl";
+    const bool ren = cmd == "rename" || cmd == "rn";
+    uint64_t min_block = 0, min_query = 0, min_align = 0;
+    bool has_min_align = false, has_prefixes = false;
+    std::vector<std::string> prefixes;
+    auto u64_flag = [](const std::string& name, const std::string& v) -> uint64_t { /* clap's u64 value parser */
+      errno = 0;
+      const uint64_t x = strtoull(v.c_str(), nullptr, 10);
+      const bool digits = !v.empty() && v.find_first_not_of("0123456789", v[0] == '+' ? 1 : 0) == std::string::npos && v != "+";
+      if (!digits || errno == ERANGE)
+        fail("invalid value '" + v + "' for '" + name + "': " +
+             (digits ? "number too large to fit in target type" : v.empty() ? "cannot parse integer from empty string" : "invalid digit found in string"));
+      return x;
+    };
     std::vector<std::string> ext_regions;
     std::string ext_file;
     bool has_ext_regions = false, has_ext_file = false;
@@ -1304,6 +1324,22 @@ static int run_command(int argc, char** argv) {
       } else if (ext && (a == "-f" || a == "--file")) {
         ext_file = val();
         has_ext_file = true;
+      } else if (filt && (a == "-b" || a == "--min-block-size"))
+        min_block = u64_flag("--min-block-size <MIN_BLOCK_SIZE>", val());
+      else if (filt && (a == "-q" || a == "--min-query-size"))
+        min_query = u64_flag("--min-query-size <MIN_QUERY_SIZE>", val());
+      else if (filt && (a == "-a" || a == "--min-align-size")) {
+        min_align = u64_flag("--min-align-size <MIN_ALIGN_SIZE>", val());
+        has_min_align = true;
+      } else if (ren && (a == "-p" || a == "--prefixs" || a.compare(0, 10, "--prefixs=") == 0)) { /* clap value_delimiter ',' */
+        const std::string v = a.size() > 10 && a[9] == '=' ? a.substr(10) : val();
+        has_prefixes = true;
+        for (size_t b = 0;;) {
+          const size_t e = v.find(',', b);
+          prefixes.push_back(v.substr(b, e == std::string::npos ? e : e - b));
+          if (e == std::string::npos) break;
+          b = e + 1;
+        }
       } else if (a == "-g" || a == "--target")
         target = val();
       else if ((a == "-q" || a == "--query") && (conv || call))
@@ -1425,6 +1461,19 @@ static int run_command(int argc, char** argv) {
     if (cmd == "maf-index" || cmd == "mi") return cmd_maf_index(input, outfile);
     if (ext)
       return cmd_maf_ext(input, has_ext_regions ? &ext_regions : nullptr, has_ext_file ? &ext_file : nullptr, outfile, rewrite);
+    if (filt) { /* utils.rs:540-576 */
+      if (format != "maf" && format != "paf" && format != "chain")
+        fail("format `" + format + "` is not supported by this engine (maf | paf | chain)");
+      out.open(outfile, rewrite);
+      if (format == "paf") return cmd_filter_paf(input, min_block, min_query, has_min_align ? &min_align : nullptr, out);
+      if (format == "chain") return cmd_filter_chain(input, min_block, min_query, out);
+      return cmd_filter_maf(input, min_block, min_query, out); /* -a is ignored, as in the reference */
+    }
+    if (ren) { /* utils.rs:579-591 */
+      if (!has_prefixes) fail("the following required arguments were not provided: --prefixs <PREFIXS>");
+      out.open(outfile, rewrite);
+      return cmd_rename(input, prefixes, out);
+    }
     if (chunk) { /* utils.rs:656-677: the length is checked before any file is opened, then the output is created, then the input */
       if (!has_length) fail("the following required arguments were not provided: --length <LENGTH>");
       errno = 0;
