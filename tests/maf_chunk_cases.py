@@ -130,6 +130,62 @@ def check_abi_long_rows(eng, cols=40000, L=9000):
     assert abi_chunk(eng, blocks, L, 1000) == text
 
 
+TILE = 8192                                                              # bytes of text per fill block (WGA_MAF_TILE)
+U64 = (1 << 64) - 1
+
+
+def check_one_window(eng, blocks, L, window_records=10 ** 9):
+    text, panic = ref.chunk_text(blocks, L)
+    assert panic is None
+    got = abi_chunk(eng, blocks, L, window_records)
+    assert got == text, (L, window_records, len(got), len(text))
+    return text
+
+
+def lead(nbytes, name=b"L"):
+    """a one-row block whose only record (L >= its columns) is exactly nbytes long"""
+    for n in range(max(nbytes - 40, 0), nbytes):
+        blk = [(name, 0, 0, b"+", 0, b"A" * n)]
+        if len(ref.chunk_text([blk], 10 ** 6)[0]) == nbytes:
+            return blk
+    raise AssertionError(nbytes)
+
+
+def short(i, rows=2):
+    return [(b"s%d.%d" % (i, r), 10 * i + r, 0, b"-" if (i + r) % 3 == 0 else b"+", 1000 + i, b"AC-GT-A") for r in range(rows)]
+
+
+def check_abi_record_ends_at_tile_edge(eng):
+    """the lead block's record ends with byte 8190 .. 8193 of the window's text (8191, 8192 and 8193 counted from 0 or from
+    1); two short two-row blocks follow"""
+    for nbytes in (TILE - 1, TILE, TILE + 1, TILE + 2):
+        blocks = [lead(nbytes), short(1), short(2)]
+        text = check_one_window(eng, blocks, 10 ** 6)
+        assert text[nbytes - 2:nbytes + 12] == b"\n\na score=255\n"
+        check_one_window(eng, blocks, 10 ** 6, window_records=2)          # ... and with the window's end behind the edge
+
+
+def check_abi_fields_straddle_tile_edge(eng):
+    """the second block's first line starts 120 .. 0 bytes in front of byte 8192: the edge falls into `a score`, the name, each
+    number (start and srcSize hold 20 digits), the strand and the slice in turn"""
+    two = [(b"chrStraddle", U64 - 1, 0, b"-", U64 - 2, b"ACGT" * 9), (b"chrStraddlf", U64 - 37, 0, b"-", U64, b"-" * 36)]
+    for gap in range(0, 121):
+        blocks = [lead(TILE - gap), two, short(3)]
+        text = check_one_window(eng, blocks, 10 ** 6)
+        assert text[TILE - gap:TILE - gap + 12] == b"a score=255\n"
+
+
+def check_abi_many_lines_per_tile(eng, n=700):
+    """L = 1 over n one-column two-row blocks with empty names: 13-byte lines, the most a tile meets.  A one-column block is
+    one record, so one three-column block stands in the middle and the windows are cut after its first record: the boundary
+    lies inside it and its rows' carries cross it"""
+    one = [[(b"", b, 0, b"+", 0, b"A"), (b"", 0, 0, b"-", 9, b"-")] for b in range(n)]
+    mid = [(b"", 5, 0, b"+", 0, b"A-C"), (b"", 6, 0, b"+", 0, b"GT-")]
+    blocks = one[:n // 2] + [mid] + one[n // 2:]
+    check_one_window(eng, blocks, 1)
+    check_one_window(eng, blocks, 1, window_records=n // 2 + 1)
+
+
 # ---- command line ----------------------------------------------------------------------------------------------------------
 def fixture_expected():
     return open(os.path.join(GOLDEN, "test_chunk_l300.maf"), "rb").read()

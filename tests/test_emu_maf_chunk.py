@@ -69,3 +69,15 @@ def test_chunk_abi_windows(eng):
 
 def test_chunk_abi_long_rows(eng):
     mc.check_abi_long_rows(eng)
+
+
+def test_chunk_abi_record_ends_at_tile_edge(eng):
+    mc.check_abi_record_ends_at_tile_edge(eng)
+
+
+def test_chunk_abi_fields_straddle_tile_edge(eng):
+    mc.check_abi_fields_straddle_tile_edge(eng)
+
+
+def test_chunk_abi_many_lines_per_tile(eng):
+    mc.check_abi_many_lines_per_tile(eng)

@@ -51,6 +51,18 @@ def test_chunk_abi_long_rows(gpu):
     mc.check_abi_long_rows(gpu, cols=300000, L=70000)
 
 
+def test_chunk_abi_record_ends_at_tile_edge(gpu):
+    mc.check_abi_record_ends_at_tile_edge(gpu)
+
+
+def test_chunk_abi_fields_straddle_tile_edge(gpu):
+    mc.check_abi_fields_straddle_tile_edge(gpu)
+
+
+def test_chunk_abi_many_lines_per_tile(gpu):
+    mc.check_abi_many_lines_per_tile(gpu)
+
+
 def _parse_on_device(t, n_lines, width, name_len):
     """the s-lines of chunk text `t` (a uint8 tensor on the GPU) with the slice widths known: their start and size fields
     (int64) and the slices put together; checks that every s-line has its six tabs, the name length and the line end"""

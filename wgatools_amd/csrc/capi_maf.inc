@@ -175,7 +175,7 @@ int wga_maf_chunk(wga_ctx* c, const uint8_t* d_text, const wga_maf_chunk_row* d_
     return WGA_OK;
   }
   if (n == 0) return WGA_OK;
-  const u64 tiles = (*text_bytes + WGA_K20_TILE - 1u) / WGA_K20_TILE;
+  const u64 tiles = (*text_bytes + WGA_MAF_TILE - 1u) / WGA_MAF_TILE;
   if (tiles >= 0x80000000ull) return fail(WGA_E_INVALID_ARG, "window text too long", nullptr);
   if (tiles) {
     WGA_LAUNCH(k_maf_chunk_fill, (u32)tiles, WGA_BLOCK, c->stream, d_text, d_rows, d_blocks, nb, (const u64*)bitem,
@@ -257,7 +257,7 @@ int wga_maf_slice(wga_ctx* c, const uint8_t* d_text, const wga_maf_slice_row* d_
     return WGA_OK;
   }
   if (nh == 0 || n == 0) return WGA_OK;
-  const u64 tiles = (*text_bytes + WGA_K20_TILE - 1u) / WGA_K20_TILE;
+  const u64 tiles = (*text_bytes + WGA_MAF_TILE - 1u) / WGA_MAF_TILE;
   if (tiles >= 0x80000000ull) return fail(WGA_E_INVALID_ARG, "window text too long", nullptr);
   if (tiles) {
     WGA_LAUNCH(k_maf_slice_fill, (u32)tiles, WGA_BLOCK, c->stream, d_text, d_rows, d_hits, nh, (const u64*)hline, (const u64*)C0,
@@ -332,7 +332,7 @@ int wga_maf_rewrite(wga_ctx* c, const uint8_t* d_text, const wga_maf_slice_row* 
   }
   if (nb == 0 || *n_kept == 0 || *text_bytes == 0) return WGA_OK;
   if (*n_kept > nb) return fail(WGA_E_INVALID_ARG, "n_kept is not the count call's", nullptr);
-  const u64 tiles = (*text_bytes + WGA_K20_TILE - 1u) / WGA_K20_TILE;
+  const u64 tiles = (*text_bytes + WGA_MAF_TILE - 1u) / WGA_MAF_TILE;
   if (tiles >= 0x80000000ull) return fail(WGA_E_INVALID_ARG, "window text too long", nullptr);
   WGA_LAUNCH(k_maf_rewrite_fill, (u32)tiles, WGA_BLOCK, c->stream, d_text, d_rows, d_blocks, nb, (const u32*)klist, *n_kept,
              (const u64*)kline, P, (const u64*)loff, (u64)*text_bytes, d_out);

@@ -17,15 +17,15 @@
  *           popcounts, a wave prefix, a bit select inside the lane's mask); every other row's non-gap bytes over [c0, c1) = two
  *           ranks, each a directory difference plus one partial-stretch wave step.  The cost of a hit depends on its rows, not
  *           on the block's or the slice's length.  The short-row test is here (a global atomic min of the hit index).
- *   lines   line lengths in output order (0 from the first short hit on), their exclusive scan = every line's place.
- *   fill    as K20's: 8 KiB LDS tiles, short fields by dec_write, slices in 16-byte groups, lds_text_flush.
+ *   lines, fill   the record writer of wga_maf_write.h over the lines in hit order.
  * Traffic: the table rows once (rank), 2 x 2 KiB per row of a hit at most (select), the slices once and the text once (fill),
  * 8 bytes per stretch and 24 per line of tables.
  */
 #ifndef WGA_K21_MAF_SLICE_H
 #define WGA_K21_MAF_SLICE_H
 
-#include "wga_k20_maf_chunk.h" /* k20_find, k20_find_in, K20Clip, k20_tile_slices, WGA_K20_TILE, WGA_K20_TILE_LINES */
+#include "wga_k3_maf.h" /* maf_nongap_mask32, maf_cols_from, popc32 */
+#include "wga_maf_write.h"
 
 #define WGA_K21_STRETCH 2048u /* columns of one directory entry = one wave step */
 #ifndef WGA_K21_GRID
@@ -51,27 +51,6 @@ struct ScanSliceLines {
   __device__ u64 operator()(u32 h) const { return hits[h].n_rows; }
 };
 
-/* the non-gap mask (K3's bit order: bit 8e + d = column 4d + e) of the lane's columns [col, col + 32) of a row of `len`
- * columns at p: columns past the row's end count as gaps and no byte behind the row is read */
-__device__ __forceinline__ u32 k21_mask(const u8* __restrict__ p, u64 len, u64 col) {
-  if (col >= len) return 0u;
-  const u32 ncols = (u32)(len - col < 32u ? len - col : 32u);
-  p += col;
-  u32 y[8];
-  if (ncols == 32u) {
-    const u32x4_a1 a0 = *(const u32x4_a1*)p, a1 = *(const u32x4_a1*)(p + 16);
-#pragma unroll
-    for (int d = 0; d < 4; d++) y[d] = a0[d], y[4 + d] = a1[d];
-  } else {
-    u8 t[32];
-    for (u32 e = 0; e < 32u; e++) t[e] = e < ncols ? p[e] : (u8)'-';
-    for (int d = 0; d < 8; d++) y[d] = (u32)t[4 * d] | ((u32)t[4 * d + 1] << 8) | ((u32)t[4 * d + 2] << 16) | ((u32)t[4 * d + 3] << 24);
-  }
-#pragma unroll
-  for (int d = 0; d < 8; d++) y[d] = maf_nonzero7(y[d] ^ 0x2D2D2D2Du);
-  return maf_gather8(y);
-}
-
 /* ---- rank: the non-gap count of every stretch --------------------------------------------------------------------------- */
 __global__ __launch_bounds__(256) void k_maf_slice_rank(const u8* __restrict__ text, const wga_maf_slice_row* __restrict__ rows,
                                                         u32 n_rows, const u64* __restrict__ dbase, u64* __restrict__ raw) {
@@ -79,12 +58,12 @@ __global__ __launch_bounds__(256) void k_maf_slice_rank(const u8* __restrict__ t
   const u64 E = dbase[n_rows], nwaves = (u64)gridDim.x * 4u, wid = (u64)blockIdx.x * 4u + w;
   const u64 x0 = E * wid / nwaves, x1 = E * (wid + 1u) / nwaves;
   if (x0 >= x1) return;
-  u32 r = k20_find(dbase, n_rows, x0); /* the entry's row; later entries are reached by walking forward */
+  u32 r = maf_find(dbase, n_rows, x0); /* the entry's row; later entries are reached by walking forward */
   for (u64 x = x0; x < x1; x++) {
     while (x >= dbase[r + 1u]) r++;
     const u64 j = x - dbase[r];
     const wga_maf_slice_row row = rows[r];
-    const u32 c = popc32(k21_mask(text + row.seq_off, row.seq_len, j * WGA_K21_STRETCH + 32u * lane)); /* 0 for the row's last entry */
+    const u32 c = popc32(maf_nongap_mask32(text + row.seq_off, row.seq_len, j * WGA_K21_STRETCH + 32u * lane)); /* 0 for the row's last entry */
     const u32 s = wave_sum_u32(c);
     if (lane == 0u) raw[x] = s;
   }
@@ -96,7 +75,7 @@ __device__ __forceinline__ u64 k21_rank(const u8* __restrict__ text, const wga_m
   const u64 j = c / WGA_K21_STRETCH, s0 = j * WGA_K21_STRETCH, lc = s0 + 32u * lane;
   u32 m = 0u;
   if (lc < c) {
-    m = k21_mask(text + row.seq_off, row.seq_len, lc);
+    m = maf_nongap_mask32(text + row.seq_off, row.seq_len, lc);
     if (c - lc < 32u) m &= ~maf_cols_from((u32)(c - lc));
   }
   return dir[j] - dir[0] + wave_sum_u32(popc32(m));
@@ -106,10 +85,10 @@ __device__ __forceinline__ u64 k21_select(const u8* __restrict__ text, const wga
                                           u32 nent, u64 p, u32 lane) {
   if (p >= dir[nent - 1u] - dir[0]) return row.seq_len;
   const u64 target = p + dir[0];
-  const u32 j = k20_find(dir, nent - 1u, target); /* the last stretch whose rank is <= p: it holds the byte */
+  const u32 j = maf_find(dir, nent - 1u, target); /* the last stretch whose rank is <= p: it holds the byte */
   const u32 rem = (u32)(target - dir[j]);
   const u64 lc = (u64)j * WGA_K21_STRETCH + 32u * lane;
-  const u32 m = k21_mask(text + row.seq_off, row.seq_len, lc), cnt = popc32(m);
+  const u32 m = maf_nongap_mask32(text + row.seq_off, row.seq_len, lc), cnt = popc32(m);
   const u32 incl = wave_incl_scan_u32(cnt);
   const u64 ball = __ballot(incl > rem);
   const u32 src = (u32)__builtin_ctzll(ball); /* the lane that holds it (the stretch holds more than rem non-gap bytes) */
@@ -168,38 +147,44 @@ __global__ __launch_bounds__(256) void k_maf_slice_select(const u8* __restrict__
   if (is_short && lane == 0u) atomicMin(&hdr->first_short, h);
 }
 
-/* the line at output index x: its hit and row, start, size and slice */
-struct K21Line {
-  u32 h, r, n_rows;
-  u64 start, size, c0, width;
-  wga_maf_slice_row row;
-};
-__device__ __forceinline__ K21Line k21_line(const wga_maf_slice_row* rows, const wga_maf_slice_hit* hits, u32 hlo, u32 hhi,
-                                            const u64* hline, const u64* C0, const u64* C1, const u64* sz, u64 x) {
-  K21Line l; /* x's hit lies in [hlo, hhi); hits without rows share their successor's first line: the last one owns it */
-  l.h = k20_find_in(hline, hlo, hhi, x);
-  const wga_maf_slice_hit H = hits[l.h];
-  l.r = (u32)(x - hline[l.h]);
-  l.n_rows = H.n_rows;
-  l.row = rows[H.row0 + l.r];
-  if (H.whole) { /* mafextra.rs:205-208: the record as it was read */
-    l.start = l.row.start;
-    l.size = l.row.size;
-    l.c0 = 0u;
-    l.width = l.row.seq_len;
-  } else {
-    l.start = l.row.start + H.cut_lo; /* maf.rs:229 for the anchor (= the region's start), maf.rs:239 for the others */
-    l.size = l.r == H.ord ? H.cut_hi - H.cut_lo : sz[x];
-    l.c0 = C0[l.h];
-    l.width = C1[l.h] - l.c0;
+/* the window's lines in hit order: line x is row x - hline[h] of its hit h (the owner).  Hits without rows share their
+ * successor's first line: the last one owns it */
+struct K21Lines {
+  const wga_maf_slice_row* rows;
+  const wga_maf_slice_hit* hits;
+  const u64 *hline, *C0, *C1, *sz;
+  u32 n_hits;
+  __device__ __forceinline__ MafOwners owners(u32 l0, u32 l1) const { return maf_owners(hline, n_hits, l0, l1, false); }
+  __device__ __forceinline__ MafLine line(MafOwners o, u64 x) const {
+    const u32 h = maf_find_in(hline, o.lo, o.hi, x);
+    const wga_maf_slice_hit H = hits[h];
+    MafLine l;
+    l.r = (u32)(x - hline[h]);
+    l.n_rows = H.n_rows;
+    const wga_maf_slice_row row = rows[H.row0 + l.r];
+    l.prefix = nullptr;
+    l.prefix_len = 0u;
+    l.name_off = row.name_off;
+    l.name_len = row.name_len;
+    l.src_size = row.src_size;
+    l.strand_neg = row.strand_neg;
+    if (H.whole) { /* mafextra.rs:205-208: the record as it was read */
+      l.start = row.start;
+      l.size = row.size;
+      l.src = row.seq_off;
+      l.width = row.seq_len;
+    } else {
+      l.start = row.start + H.cut_lo; /* maf.rs:229 for the anchor (= the region's start), maf.rs:239 for the others */
+      l.size = l.r == H.ord ? H.cut_hi - H.cut_lo : sz[x];
+      l.src = row.seq_off + C0[h];
+      l.width = C1[h] - C0[h];
+    }
+    return l;
   }
-  return l;
-}
-__device__ __forceinline__ u64 k21_line_len(const K21Line& l) {
-  return (l.r == 0u ? 12u : 0u) + 2u + l.row.name_len + 1u + dec_digits(l.start) + 1u + dec_digits(l.size) + 3u +
-         dec_digits(l.row.src_size) + 1u + l.width + (l.r + 1u == l.n_rows ? 2u : 1u);
-}
+};
 
+/* lengths of the window's n lines: 0 from the first short hit on (the lines behind the panic hold no text, so they start at the
+ * text's end) */
 __global__ __launch_bounds__(256) void k_maf_slice_lines(const wga_maf_slice_row* __restrict__ rows,
                                                          const wga_maf_slice_hit* __restrict__ hits, u32 n_hits,
                                                          const u64* __restrict__ hline, const u64* __restrict__ C0,
@@ -208,78 +193,21 @@ __global__ __launch_bounds__(256) void k_maf_slice_lines(const wga_maf_slice_row
   const u32 x = blockIdx.x * 256u + threadIdx.x;
   if (x >= n) return;
   const u32 fs = hdr->first_short;
-  if (fs != 0xFFFFFFFFu && x >= hline[fs]) { /* behind the panic: no text */
+  if (fs != 0xFFFFFFFFu && x >= hline[fs]) {
     len[x] = 0u;
     return;
   }
-  len[x] = k21_line_len(k21_line(rows, hits, 0u, n_hits, hline, C0, C1, sz, x));
+  const K21Lines src = {rows, hits, hline, C0, C1, sz, n_hits};
+  len[x] = maf_line_len(src.line(MafOwners{0u, n_hits}, x));
 }
 
-/* ---- fill: one 8 KiB tile of the text per block (k_maf_chunk_fill's scheme) ----------------------------------------------- */
 __global__ __launch_bounds__(256) void k_maf_slice_fill(const u8* __restrict__ text, const wga_maf_slice_row* __restrict__ rows,
                                                         const wga_maf_slice_hit* __restrict__ hits, u32 n_hits,
                                                         const u64* __restrict__ hline, const u64* __restrict__ C0,
                                                         const u64* __restrict__ C1, const u64* __restrict__ sz, u32 n,
                                                         const u64* __restrict__ line_off, u8* __restrict__ out) {
-  __shared__ u32x4_a16 s_tile[WGA_K20_TILE / 16u];
-  __shared__ u32 s_lo[WGA_K20_TILE_LINES], s_hi[WGA_K20_TILE_LINES];
-  __shared__ u64 s_src[WGA_K20_TILE_LINES];
-  __shared__ u32 s_first, s_count, s_hlo, s_hhi;
-  u8* const tbuf = (u8*)s_tile;
-  const u32 tid = threadIdx.x;
-  const u64 total = line_off[n];
-  const u64 T0 = (u64)blockIdx.x * WGA_K20_TILE;
-  const u32 tl = (u32)(total - T0 < WGA_K20_TILE ? total - T0 : WGA_K20_TILE);
-  if (tid == 0u) { /* the tile's lines [l0, l1] (the empty lines behind a panic start at `total`: never among them) and their hits */
-    const u32 l0 = k20_find(line_off, n, T0);
-    const u32 lim = n - l0 < WGA_K20_TILE_LINES ? n : l0 + WGA_K20_TILE_LINES;
-    const u32 l1 = k20_find_in(line_off, l0, lim, T0 + tl - 1u);
-    s_first = l0;
-    s_count = l1 - l0 + 1u;
-    s_hlo = k20_find(hline, n_hits, l0);
-    s_hhi = k20_find_in(hline, s_hlo, n_hits, l1) + 1u;
-  }
-  __syncthreads();
-  const u32 l0 = s_first, nl = s_count, hlo = s_hlo, hhi = s_hhi; /* nl <= WGA_K20_TILE_LINES: a line holds 12 bytes or more */
-  for (u32 j = tid; j < nl; j += 256u) {
-    const K21Line l = k21_line(rows, hits, hlo, hhi, hline, C0, C1, sz, (u64)l0 + j);
-    K20Clip c;
-    c.buf = tbuf;
-    c.at = (long long)(line_off[l0 + j] - T0);
-    c.tl = tl;
-    if (l.r == 0u) {
-      const char* a = "a score=255\n";
-      for (u32 e = 0; e < 12u; e++) c.put((u8)a[e]);
-    }
-    c.put((u8)'s');
-    c.put((u8)'\t');
-    const u8* name = text + l.row.name_off;
-    const long long name_end = c.at + (long long)l.row.name_len;
-    for (u32 e = 0; e < l.row.name_len && c.at < (long long)tl; e++) c.put(name[e]);
-    c.at = name_end;
-    c.put((u8)'\t');
-    c.num(l.start);
-    c.put((u8)'\t');
-    c.num(l.size);
-    c.put((u8)'\t');
-    c.put(l.row.strand_neg ? (u8)'-' : (u8)'+');
-    c.put((u8)'\t');
-    c.num(l.row.src_size);
-    c.put((u8)'\t');
-    const long long s0 = c.at, s1 = c.at + (long long)l.width;
-    const long long lo = s0 < 0 ? 0 : s0 > (long long)tl ? (long long)tl : s0;
-    const long long hi = s1 < 0 ? 0 : s1 > (long long)tl ? (long long)tl : s1;
-    s_lo[j] = (u32)lo;
-    s_hi[j] = (u32)hi;
-    s_src[j] = l.row.seq_off + l.c0 + (u64)(lo - s0);
-    c.at = s1;
-    c.put((u8)'\n');
-    if (l.r + 1u == l.n_rows) c.put((u8)'\n');
-  }
-  __syncthreads();
-  k20_tile_slices(tbuf, tl, nl, s_lo, s_hi, s_src, text, tid);
-  __syncthreads();
-  lds_text_flush(tbuf, 0u, tl, out + T0, tid, 256u);
+  const K21Lines src = {rows, hits, hline, C0, C1, sz, n_hits};
+  maf_fill_tile(src, text, line_off, n, line_off[n], out);
 }
 
 #endif /* WGA_K21_MAF_SLICE_H */

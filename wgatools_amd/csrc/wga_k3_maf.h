@@ -81,6 +81,26 @@ __device__ __forceinline__ u32 maf_cols_from(u32 k) {
   if (k >= 32u) return 0u;
   return ~maf_cols_before(((k & 3u) << 3) | (k >> 2));
 }
+/* the non-gap mask (bit 8e + d = column 4d + e) of columns [col, col + 32) of a row of `len` columns at p: columns at or past
+ * `len` count as gaps and no byte behind the row is read (an unaligned 2 x 16-byte load, or a guarded byte tail) */
+__device__ __forceinline__ u32 maf_nongap_mask32(const u8* __restrict__ p, u64 len, u64 col) {
+  if (col >= len) return 0u;
+  const u32 ncols = (u32)(len - col < 32u ? len - col : 32u);
+  p += col;
+  u32 y[8];
+  if (ncols == 32u) {
+    const u32x4_a1 a0 = *(const u32x4_a1*)p, a1 = *(const u32x4_a1*)(p + 16);
+#pragma unroll
+    for (int d = 0; d < 4; d++) y[d] = a0[d], y[4 + d] = a1[d];
+  } else {
+    u8 t[32];
+    for (u32 e = 0; e < 32u; e++) t[e] = e < ncols ? p[e] : (u8)'-';
+    for (int d = 0; d < 8; d++) y[d] = (u32)t[4 * d] | ((u32)t[4 * d + 1] << 8) | ((u32)t[4 * d + 2] << 16) | ((u32)t[4 * d + 3] << 24);
+  }
+#pragma unroll
+  for (int d = 0; d < 8; d++) y[d] = maf_nonzero7(y[d] ^ 0x2D2D2D2Du);
+  return maf_gather8(y);
+}
 __device__ __forceinline__ u32 maf_col_class(u8 tc, u8 qc, bool caller) {
   const bool tg = tc == (u8)'-', qg = qc == (u8)'-';
   if (caller) return (tg && qg) ? 4u : tg ? 1u : qg ? 2u : (tc == qc ? 0u : 3u);

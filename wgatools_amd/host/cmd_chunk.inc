@@ -31,62 +31,29 @@ static uint32_t chunk_plan(const MafRecord* const* recs, uint32_t n, uint64_t L,
   return n;
 }
 
-/* the records of blocks recs[0 .. n) (kc[b] chunks each) on device d, window by window; sink(dev, text, bytes) takes every
- * window's text in order */
+/* the records of blocks recs[0 .. n) (kc[b] chunks each) on device d, window by window */
 static void chunk_blocks(Dev& d, const MafInput& in, bool in_place, const MafRecord* const* recs, uint32_t n, const uint64_t* kc,
-                         uint64_t L, size_t budget, const std::function<void(Dev&, const uint8_t*, size_t)>& sink) {
+                         uint64_t L, size_t budget, const MafSink& sink) {
   d.init();
-  std::vector<wga_maf_chunk_row> rows;
-  std::vector<uint64_t> row0(n), bound(n);
-  std::string blob;
+  const MafRowTable<wga_maf_chunk_row> t = maf_row_table<wga_maf_chunk_row>(d, in, in_place, recs, n);
+  std::vector<uint64_t> bound(n); /* of a record's text: name, three 20-digit numbers and the slice width per row */
   for (uint32_t b = 0; b < n; b++) {
-    const MafRecord& r = *recs[b];
-    row0[b] = rows.size();
-    const uint64_t w = std::min<uint64_t>(L, r.slines[0].seq_size());
-    uint64_t rb = 13;
-    for (const MafSLine& s : r.slines) {
-      wga_maf_chunk_row x;
-      if (in_place) {
-        x.seq_off = s.seq_off;
-        x.name_off = s.name_off;
-      } else { /* the rows gathered from the host copy of the text (the host reader, or a device other than the reader's) */
-        x.name_off = blob.size();
-        blob += s.name;
-        x.seq_off = blob.size();
-        blob.append(s.seq_data(), s.seq_size());
-      }
-      x.seq_len = s.seq_size();
-      x.start = s.start;
-      x.src_size = s.size;
-      x.name_len = (uint32_t)s.name.size();
-      x.strand_neg = s.neg ? 1u : 0u;
-      rows.push_back(x);
-      rb += s.name.size() + 70u + w;
-    }
-    bound[b] = rb;
+    const uint64_t w = std::min<uint64_t>(L, recs[b]->slines[0].seq_size());
+    bound[b] = 13;
+    for (const MafSLine& s : recs[b]->slines) bound[b] += s.name.size() + 70u + w;
   }
-  const uint8_t* d_text = in_place ? in.d_text : nullptr;
-  if (!in_place) {
-    blob.append(16, '\0');
-    d_text = d.upload((const uint8_t*)blob.data(), blob.size());
-  }
-  auto* d_rows = d.upload(rows);
-  auto* d_carry = (uint64_t*)d.alloc(std::max<size_t>(rows.size(), 1) * 8);
-  d.check(wga_memset(d.ctx, d_carry, 0, std::max<size_t>(rows.size(), 1) * 8));
+  auto* d_carry = (uint64_t*)d.alloc(std::max<size_t>(t.rows.size(), 1) * 8);
+  d.check(wga_memset(d.ctx, d_carry, 0, std::max<size_t>(t.rows.size(), 1) * 8));
   g_timer.mark("host rows + upload");
   std::vector<wga_maf_chunk_block> win;
   uint64_t used = 0, lines = 0;
   auto flush = [&]() {
     if (win.empty()) return;
     auto* d_blocks = d.upload(win);
-    void* d_work = d.alloc((size_t)wga_maf_chunk_work_bytes((uint32_t)win.size(), lines));
-    uint64_t bytes = 0;
-    d.check(wga_maf_chunk(d.ctx, d_text, d_rows, (uint32_t)win.size(), d_blocks, lines, L, d_carry, d_work, &bytes, nullptr));
-    auto* d_out = (uint8_t*)d.alloc((size_t)bytes + 16);
-    d.check(wga_maf_chunk(d.ctx, d_text, d_rows, (uint32_t)win.size(), d_blocks, lines, L, d_carry, d_work, &bytes, d_out));
-    d.release(d_work);
-    d.release(d_blocks);
-    sink(d, d_out, (size_t)bytes); /* the sink releases d_out or keeps it */
+    const uint32_t nb = (uint32_t)win.size();
+    maf_window_call(d, (size_t)wga_maf_chunk_work_bytes(nb, lines), d_blocks, [&](void* d_work, uint64_t* bytes, uint8_t* d_out) {
+      return wga_maf_chunk(d.ctx, t.d_text, t.d_rows, nb, d_blocks, lines, L, d_carry, d_work, bytes, d_out);
+    }, sink);
     win.clear();
     used = lines = 0;
   };
@@ -103,7 +70,7 @@ static void chunk_blocks(Dev& d, const MafInput& in, bool in_place, const MafRec
         }
         take = 1; /* one record above the budget: a window of its own */
       }
-      win.push_back(wga_maf_chunk_block{row0[b], k, k + take, nr, 0});
+      win.push_back(wga_maf_chunk_block{t.row0[b], k, k + take, nr, 0});
       used += take * bound[b];
       lines += take * nr;
       k += take;
@@ -154,73 +121,27 @@ static std::string chunk_host(const std::vector<MafRecord>& recs, uint64_t L, st
 }
 
 int cmd_chunk(const std::string* input, uint64_t L, Output& out) {
-  Dev d;
-  MafDevices md(d); /* --gpus N: a piece's blocks in contiguous ranges over the devices, the text written in block order */
-  size_t budget = (size_t)1 << 28;
-  if (const char* e = getenv("WGA_MAF_CHUNK_OUT_BYTES")) budget = std::max<size_t>(1, (size_t)strtoull(e, nullptr, 10));
-  std::string pending_error;
-  MafChunks chunks(input);
-  chunks.keep_going = true;
-  out.write("#maf version=1.6 split_length=" + std::to_string(L) + "\n"); /* chunk.rs:29-30: the input's header is dropped */
-  MafInput min;
-  g_timer.mark("host");
-  for (;;) {
-    bool more = false;
-    try {
-      more = chunks.next(d, min);
-    } catch (Error& e) {
-      pending_error = e.msg;
-    }
-    g_timer.mark("read + upload + split");
-    if (!more) break;
-    const std::vector<const MafRecord*> all = all_records(min.recs);
-    bool non_ascii = false;
-    if (!min.on_device)
-      for (const MafRecord* r : all)
-        for (const MafSLine& s : r->slines)
-          for (size_t x = 0; x < s.seq_size() && !non_ascii; x++) non_ascii = (unsigned char)s.seq_data()[x] >= 0x80u;
-    if (non_ascii) {
-      std::string panic;
-      out.write(chunk_host(min.recs, L, panic));
-      if (!panic.empty()) pending_error = panic;
-    } else {
-      std::vector<uint64_t> kc;
-      bool panic = false;
-      const uint32_t n = chunk_plan(all.data(), (uint32_t)all.size(), L, kc, &panic);
-      const int ng = md.count();
-      if (ng == 1) {
-        chunk_blocks(d, min, min.on_device, all.data(), n, kc.data(), L, budget, [&](Dev& dg, const uint8_t* t, size_t bytes) {
-          stream_out(dg, out, t, bytes);
-          dg.release((void*)t);
-        });
-      } else {
-        /* device 0's windows are the first text of the piece: they leave as they are made (its worker thread is the only one
-         * writing while the devices work); the other devices keep their windows in HBM until the devices in front of them are done */
-        std::vector<std::vector<std::pair<const uint8_t*, size_t>>> texts(ng);
-        on_devices(ng, [&](int g) {
-          const uint32_t lo = (uint32_t)((uint64_t)n * g / ng), hi = (uint32_t)((uint64_t)n * (g + 1) / ng);
-          if (lo == hi) return;
-          chunk_blocks(md.dev(g), min, g == 0 && min.on_device, all.data() + lo, hi - lo, kc.data() + lo, L, budget,
-                       [&](Dev& dg, const uint8_t* t, size_t bytes) {
-                         if (g == 0) {
-                           stream_out(dg, out, t, bytes, false);
-                           dg.release((void*)t);
-                         } else {
-                           texts[g].emplace_back(t, bytes);
-                         }
-                       });
-        });
-        for (int g = 0; g < ng; g++)
-          for (const auto& t : texts[g]) stream_out(md.dev(g), out, t.first, t.second);
-      }
-      if (panic) pending_error = kChunkShortRow;
-    }
-    md.release_all();
-    if (pending_error.empty() && !min.error.empty()) pending_error = min.error;
-    if (!pending_error.empty()) break;
-  }
-  out.close();
-  g_timer.mark("write");
-  if (!pending_error.empty()) fail(pending_error);
-  return leave(0);
+  std::vector<uint64_t> kc; /* of the piece at hand */
+  return maf_pieces(
+      input, "#maf version=1.6 split_length=" + std::to_string(L), "WGA_MAF_CHUNK_OUT_BYTES", out, /* chunk.rs:29-30 */
+      [&](const MafPiece& p, int, Dev& dg, bool in_place, uint32_t lo, uint32_t hi, const MafSink& sink) {
+        chunk_blocks(dg, p.in, in_place, p.recs.data() + lo, hi - lo, kc.data() + lo, L, p.budget, sink);
+        return false;
+      },
+      std::string(),
+      [&](MafPiece& p, Output& o) {
+        bool non_ascii = false;
+        if (!p.in.on_device)
+          for (const MafRecord* r : p.recs)
+            for (const MafSLine& s : r->slines)
+              for (size_t x = 0; x < s.seq_size() && !non_ascii; x++) non_ascii = (unsigned char)s.seq_data()[x] >= 0x80u;
+        if (non_ascii) {
+          o.write(chunk_host(p.in.recs, L, p.error));
+          p.n = 0;
+          return;
+        }
+        bool panic = false;
+        p.n = chunk_plan(p.recs.data(), (uint32_t)p.recs.size(), L, kc, &panic);
+        if (panic) p.error = kChunkShortRow;
+      });
 }

@@ -341,35 +341,10 @@ int cmd_maf_ext(const std::string* input, const std::vector<std::string>* region
           for (const MafSLine& s : r->slines)
             for (size_t x = 0; x < s.seq_size() && !non_ascii; x++) non_ascii = (unsigned char)s.seq_data()[x] >= 0x80u;
     }
-    /* the window's hits -> K21's tables (or the host path).  The in-place table names the rows where the piece was uploaded
-     * (device 0, device splitter); every other device, and the host reader's records, get a gathered copy of the rows their hits
-     * name (the host reader's path and the non-ASCII test above are the only host loops over row text) */
-    auto make_row = [](const MafSLine& s, uint64_t seq_off, uint64_t name_off) {
-      wga_maf_slice_row x;
-      x.seq_off = seq_off;
-      x.seq_len = s.seq_size();
-      x.name_off = name_off;
-      x.start = s.start;
-      x.size = s.align_size;
-      x.src_size = s.size;
-      x.name_len = (uint32_t)s.name.size();
-      x.strand_neg = s.neg ? 1u : 0u;
-      return x;
-    };
-    std::vector<wga_maf_slice_row> rows;
-    std::vector<uint64_t> row0(block_off.size(), 0);
+    /* the window's hits -> K21's tables (or the host path; the host reader's path and the non-ASCII test above are the only
+     * host loops over row text) */
     std::string host_text;
-    uint64_t n_cols = 0;
-    if (min.on_device)
-      for (size_t b = 0; b < block_off.size(); b++) {
-        row0[b] = rows.size();
-        if (!rec_of[b]) continue;
-        for (const MafSLine& s : rec_of[b]->slines) {
-          rows.push_back(make_row(s, s.seq_off, s.name_off));
-          n_cols += s.seq_size();
-        }
-      }
-    std::vector<wga_maf_slice_hit> win; /* row0 = the block's first row in the in-place table */
+    std::vector<wga_maf_slice_hit> win; /* row0 is set where the hits' device makes its row table */
     std::vector<size_t> win_block;
     for (size_t h = h0; h < h1; h++) {
       const ExtHit& H = hits[h];
@@ -395,7 +370,7 @@ int cmd_maf_ext(const std::string* input, const std::vector<std::string>* region
         }
         continue;
       }
-      win.push_back(wga_maf_slice_hit{row0[b], cut_lo, cut_hi, (uint32_t)r.slines.size(), (uint32_t)ord, whole ? 1u : 0u, 0u});
+      win.push_back(wga_maf_slice_hit{0, cut_lo, cut_hi, (uint32_t)r.slines.size(), (uint32_t)ord, whole ? 1u : 0u, 0u});
       win_block.push_back(b);
     }
     /* hits [lo, hi) of the window on one device: their text in HBM, its length and the first short hit */
@@ -404,46 +379,43 @@ int cmd_maf_ext(const std::string* input, const std::vector<std::string>* region
       uint64_t bytes = 0;
       uint32_t first_short = 0xFFFFFFFFu;
     };
+    /* The in-place table names the rows of all the window's blocks where the piece was uploaded (device 0, device splitter);
+     * every other device, and the host reader's records, get a gathered copy of the rows their hits name. */
     auto run_part = [&](Dev& dg, bool in_place, size_t lo, size_t hi) {
       Part p;
       dg.init();
       std::vector<wga_maf_slice_hit> part(win.begin() + (ptrdiff_t)lo, win.begin() + (ptrdiff_t)hi);
-      std::vector<wga_maf_slice_row> own;
-      std::string blob;
-      const uint8_t* d_text = min.d_text;
-      uint64_t cols = n_cols, lines = 0;
+      std::vector<const MafRecord*> recs = rec_of;
+      std::vector<size_t> slot(win_block.begin() + (ptrdiff_t)lo, win_block.begin() + (ptrdiff_t)hi); /* a hit's block in recs */
       if (!in_place) {
-        std::unordered_map<size_t, uint64_t> first_row; /* block -> its first row in this device's table */
-        cols = 0;
-        for (size_t k = 0; k < part.size(); k++) {
-          const size_t b = win_block[lo + k];
-          auto it = first_row.find(b);
-          if (it == first_row.end()) {
-            it = first_row.emplace(b, own.size()).first;
-            for (const MafSLine& s : rec_of[b]->slines) {
-              const uint64_t name_off = blob.size();
-              blob += s.name;
-              own.push_back(make_row(s, blob.size(), name_off));
-              blob.append(s.seq_data(), s.seq_size());
-              cols += s.seq_size();
-            }
+        std::unordered_map<size_t, size_t> seen;
+        recs.clear();
+        for (size_t& b : slot) {
+          auto it = seen.find(b);
+          if (it == seen.end()) {
+            it = seen.emplace(b, recs.size()).first;
+            recs.push_back(rec_of[b]);
           }
-          part[k].row0 = it->second;
+          b = it->second;
         }
-        blob.append(16, '\0');
-        d_text = dg.upload((const uint8_t*)blob.data(), blob.size());
       }
-      for (const wga_maf_slice_hit& h : part) lines += h.n_rows;
-      const std::vector<wga_maf_slice_row>& table = in_place ? rows : own;
-      auto* d_rows = dg.upload(table);
+      const MafRowTable<wga_maf_slice_row> t = maf_row_table<wga_maf_slice_row>(dg, min, in_place, recs.data(), recs.size());
+      uint64_t lines = 0;
+      for (size_t k = 0; k < part.size(); k++) {
+        part[k].row0 = t.row0[slot[k]];
+        lines += part[k].n_rows;
+      }
       auto* d_hits = dg.upload(part);
-      void* d_work = dg.alloc((size_t)wga_maf_slice_work_bytes((uint32_t)part.size(), lines, table.size(), cols));
-      dg.check(wga_maf_slice(dg.ctx, d_text, d_rows, table.size(), cols, (uint32_t)part.size(), d_hits, lines, d_work, &p.bytes,
-                             &p.first_short, nullptr));
-      auto* d_out = (uint8_t*)dg.alloc((size_t)p.bytes + 16);
-      dg.check(wga_maf_slice(dg.ctx, d_text, d_rows, table.size(), cols, (uint32_t)part.size(), d_hits, lines, d_work, &p.bytes,
-                             &p.first_short, d_out));
-      p.text = d_out;
+      const uint32_t nh = (uint32_t)part.size();
+      maf_window_call(dg, (size_t)wga_maf_slice_work_bytes(nh, lines, t.rows.size(), t.n_cols), d_hits,
+                      [&](void* d_work, uint64_t* bytes, uint8_t* d_out) {
+                        return wga_maf_slice(dg.ctx, t.d_text, t.d_rows, t.rows.size(), t.n_cols, nh, d_hits, lines, d_work, bytes,
+                                             &p.first_short, d_out);
+                      },
+                      [&](Dev&, const uint8_t* text, size_t bytes) {
+                        p.text = text;
+                        p.bytes = bytes;
+                      });
       return p;
     };
     if (non_ascii) {

@@ -52,48 +52,20 @@ struct MafRewrite {
   }
 };
 
-/* blocks recs[0 .. n) on device d (device g of the run), window by window; sink(dev, text, bytes) takes every window's text in
- * order.  Returns the first bad block's index among recs, ~0u when there is none (the windows behind it are not made). */
-static uint32_t rewrite_blocks(Dev& d, int g, MafRewrite& rw, const MafInput& in, bool in_place, const MafRecord* const* recs,
-                               uint32_t n, size_t budget, const std::function<void(Dev&, const uint8_t*, size_t)>& sink) {
+/* blocks recs[0 .. n) on device d (device g of the run), window by window.  Returns whether a window met a bad block (the
+ * windows behind it are not made). */
+static bool rewrite_blocks(Dev& d, int g, MafRewrite& rw, const MafInput& in, bool in_place, const MafRecord* const* recs,
+                           uint32_t n, size_t budget, const MafSink& sink) {
   d.init();
   const wga_maf_rewrite_params par = rw.params(d, g);
-  std::vector<wga_maf_slice_row> rows;
-  std::vector<uint64_t> row0(n), bound(n);
-  std::string blob;
+  const MafRowTable<wga_maf_slice_row> t = maf_row_table<wga_maf_slice_row>(d, in, in_place, recs, n);
+  std::vector<uint64_t> bound(n); /* of a block's text: prefix, name, three 20-digit numbers and the row per line */
   for (uint32_t b = 0; b < n; b++) {
-    const MafRecord& r = *recs[b];
-    row0[b] = rows.size();
-    uint64_t rb = 13;
-    for (size_t i = 0; i < r.slines.size(); i++) {
-      const MafSLine& s = r.slines[i];
-      wga_maf_slice_row x;
-      if (in_place) {
-        x.seq_off = s.seq_off;
-        x.name_off = s.name_off;
-      } else { /* the rows gathered from the host copy of the text (the host reader, or a device other than the reader's) */
-        x.name_off = blob.size();
-        blob += s.name;
-        x.seq_off = blob.size();
-        blob.append(s.seq_data(), s.seq_size());
-      }
-      x.seq_len = s.seq_size();
-      x.start = s.start;
-      x.size = s.align_size;
-      x.src_size = s.size;
-      x.name_len = (uint32_t)s.name.size();
-      x.strand_neg = s.neg ? 1u : 0u;
-      rows.push_back(x);
-      rb += s.name.size() + (i < rw.prefixes.size() ? rw.prefixes[i].size() : 0) + 70u + s.seq_size();
-    }
-    bound[b] = rb;
+    const std::vector<MafSLine>& sl = recs[b]->slines;
+    bound[b] = 13;
+    for (size_t i = 0; i < sl.size(); i++)
+      bound[b] += sl[i].name.size() + (i < rw.prefixes.size() ? rw.prefixes[i].size() : 0) + 70u + sl[i].seq_size();
   }
-  const uint8_t* d_text = in_place ? in.d_text : nullptr;
-  if (!in_place) {
-    blob.append(16, '\0');
-    d_text = d.upload((const uint8_t*)blob.data(), blob.size());
-  }
-  auto* d_rows = d.upload(rows);
   g_timer.mark("host rows + upload");
   const uint64_t max_lines = (uint64_t)1 << 31;
   for (uint32_t b0 = 0; b0 < n;) {
@@ -103,88 +75,31 @@ static uint32_t rewrite_blocks(Dev& d, int g, MafRewrite& rw, const MafInput& in
     for (; b1 < n; b1++) {
       const uint64_t nr = recs[b1]->slines.size();
       if (b1 > b0 && (used + bound[b1] > budget || lines + nr > max_lines)) break;
-      win.push_back(wga_maf_rewrite_block{row0[b1], (uint32_t)nr, 0});
+      win.push_back(wga_maf_rewrite_block{t.row0[b1], (uint32_t)nr, 0});
       used += bound[b1];
       lines += nr;
     }
     auto* d_blocks = d.upload(win);
-    void* d_work = d.alloc((size_t)wga_maf_rewrite_work_bytes((uint32_t)win.size(), lines));
-    uint64_t bytes = 0;
+    const uint32_t nb = (uint32_t)win.size();
     uint32_t kept = 0, bad = 0xFFFFFFFFu;
-    d.check(wga_maf_rewrite(d.ctx, d_text, d_rows, (uint32_t)win.size(), d_blocks, lines, &par, d_work, &bytes, &kept, &bad, nullptr));
-    auto* d_out = (uint8_t*)d.alloc((size_t)bytes + 16);
-    d.check(wga_maf_rewrite(d.ctx, d_text, d_rows, (uint32_t)win.size(), d_blocks, lines, &par, d_work, &bytes, &kept, &bad, d_out));
-    d.release(d_work);
-    d.release(d_blocks);
-    sink(d, d_out, (size_t)bytes); /* the sink releases d_out or keeps it */
-    if (bad != 0xFFFFFFFFu) return b0 + bad;
+    maf_window_call(d, (size_t)wga_maf_rewrite_work_bytes(nb, lines), d_blocks, [&](void* d_work, uint64_t* bytes, uint8_t* d_out) {
+      return wga_maf_rewrite(d.ctx, t.d_text, t.d_rows, nb, d_blocks, lines, &par, d_work, bytes, &kept, &bad, d_out);
+    }, sink);
+    if (bad != 0xFFFFFFFFu) return true;
     b0 = b1;
   }
-  return 0xFFFFFFFFu;
+  return false;
 }
 
-/* the driver of both commands: pieces, windows and --gpus N as cmd_chunk (each device a contiguous range of a piece's blocks,
- * device 0 streams first and the others hold their text in HBM; the bytes are those of one device) */
+/* the driver of both commands: pieces, windows and --gpus N are maf_pieces' */
 static int rewrite_maf(const std::string* input, const std::string& header, MafRewrite& rw, Output& out) {
-  Dev d;
-  MafDevices md(d);
-  rw.on_dev.resize((size_t)md.count());
-  size_t budget = (size_t)1 << 28;
-  if (const char* e = getenv("WGA_MAF_REWRITE_OUT_BYTES")) budget = std::max<size_t>(1, (size_t)strtoull(e, nullptr, 10));
-  std::string pending_error;
-  MafChunks chunks(input);
-  chunks.keep_going = true;
-  out.write(header + "\n"); /* the input's header is dropped */
-  MafInput min;
-  g_timer.mark("host");
-  for (;;) {
-    bool more = false;
-    try {
-      more = chunks.next(d, min);
-    } catch (Error& e) {
-      pending_error = e.msg;
-    }
-    g_timer.mark("read + upload + split");
-    if (!more) break;
-    const std::vector<const MafRecord*> all = all_records(min.recs);
-    const uint32_t n = (uint32_t)all.size();
-    const int ng = md.count();
-    bool bad = false;
-    if (ng == 1) {
-      bad = rewrite_blocks(d, 0, rw, min, min.on_device, all.data(), n, budget, [&](Dev& dg, const uint8_t* t, size_t bytes) {
-              stream_out(dg, out, t, bytes);
-              dg.release((void*)t);
-            }) != 0xFFFFFFFFu;
-    } else {
-      std::vector<std::vector<std::pair<const uint8_t*, size_t>>> texts((size_t)ng);
-      std::vector<uint32_t> first_bad((size_t)ng, 0xFFFFFFFFu);
-      on_devices(ng, [&](int g) {
-        const uint32_t lo = (uint32_t)((uint64_t)n * g / ng), hi = (uint32_t)((uint64_t)n * (g + 1) / ng);
-        if (lo == hi) return;
-        first_bad[(size_t)g] = rewrite_blocks(md.dev(g), g, rw, min, g == 0 && min.on_device, all.data() + lo, hi - lo, budget,
-                                              [&](Dev& dg, const uint8_t* t, size_t bytes) {
-                                                if (g == 0) {
-                                                  stream_out(dg, out, t, bytes, false);
-                                                  dg.release((void*)t);
-                                                } else {
-                                                  texts[(size_t)g].emplace_back(t, bytes);
-                                                }
-                                              });
-      });
-      for (int g = 0; g < ng && !bad; g++) { /* the text ends behind the first device that met a bad block */
-        for (const auto& t : texts[(size_t)g]) stream_out(md.dev(g), out, t.first, t.second);
-        bad = first_bad[(size_t)g] != 0xFFFFFFFFu;
-      }
-    }
-    md.release_all();
-    if (bad) pending_error = rw.bad_message;
-    if (pending_error.empty() && !min.error.empty()) pending_error = min.error;
-    if (!pending_error.empty()) break;
-  }
-  out.close();
-  g_timer.mark("write");
-  if (!pending_error.empty()) fail(pending_error);
-  return leave(0);
+  rw.on_dev.resize((size_t)std::max(1, g_gpus)); /* one slot per device of the run */
+  return maf_pieces(
+      input, header, "WGA_MAF_REWRITE_OUT_BYTES", out,
+      [&](const MafPiece& p, int g, Dev& dg, bool in_place, uint32_t lo, uint32_t hi, const MafSink& sink) {
+        return rewrite_blocks(dg, g, rw, p.in, in_place, p.recs.data() + lo, hi - lo, p.budget, sink);
+      },
+      rw.bad_message);
 }
 
 /* ---- filter (tools/filter.rs, utils.rs:540-576) --------------------------------------------------------------------------------

@@ -1071,6 +1071,155 @@ uint32_t expand_batch(Dev& d, const wga_cigar_batch& cb, const ExpandJob& j, con
 
 #include "cmd_call.inc"
 
+/* ---- what the MAF text commands share (chunk: K20, maf-ext: K21, filter and rename: K22) ------------------------------------- */
+using MafSink = std::function<void(Dev&, const uint8_t*, size_t)>; /* takes every window's text in order; releases it or keeps it */
+
+/* The row table of blocks recs[0 .. n) on device d: block b's rows are rows[row0[b] ..] in its order (none for a null record).
+ * in_place: the rows name the text where the device reader uploaded it (in.d_text); otherwise names and rows are gathered
+ * from the host copy of the text (the host reader, or a device other than the reader's) into a blob with 16 zero bytes behind
+ * it.  Row is the command's ABI struct: chunk's has no size field (it counts its slices). */
+static void maf_row_size(wga_maf_chunk_row&, uint64_t) {}
+static void maf_row_size(wga_maf_slice_row& x, uint64_t v) { x.size = v; }
+template <typename Row>
+struct MafRowTable {
+  std::vector<Row> rows;
+  std::vector<uint64_t> row0;
+  uint64_t n_cols = 0; /* the rows' columns in all */
+  const uint8_t* d_text = nullptr;
+  Row* d_rows = nullptr;
+};
+template <typename Row>
+static MafRowTable<Row> maf_row_table(Dev& d, const MafInput& in, bool in_place, const MafRecord* const* recs, size_t n) {
+  MafRowTable<Row> t;
+  t.row0.resize(n);
+  std::string blob;
+  for (size_t b = 0; b < n; b++) {
+    t.row0[b] = t.rows.size();
+    if (!recs[b]) continue;
+    for (const MafSLine& s : recs[b]->slines) {
+      Row x;
+      if (in_place) {
+        x.seq_off = s.seq_off;
+        x.name_off = s.name_off;
+      } else {
+        x.name_off = blob.size();
+        blob += s.name;
+        x.seq_off = blob.size();
+        blob.append(s.seq_data(), s.seq_size());
+      }
+      x.seq_len = s.seq_size();
+      x.start = s.start;
+      maf_row_size(x, s.align_size);
+      x.src_size = s.size;
+      x.name_len = (uint32_t)s.name.size();
+      x.strand_neg = s.neg ? 1u : 0u;
+      t.rows.push_back(x);
+      t.n_cols += s.seq_size();
+    }
+  }
+  t.d_text = in.d_text;
+  if (!in_place) {
+    blob.append(16, '\0');
+    t.d_text = d.upload((const uint8_t*)blob.data(), blob.size());
+  }
+  t.d_rows = d.upload(t.rows);
+  return t;
+}
+
+/* One window through a command's two-call entry: call(d_work, &bytes, d_out) counts with d_out == nullptr and writes the text
+ * otherwise.  d_window (the window's uploaded blocks or hits) and the work area are released behind the fill call; the sink
+ * gets the text. */
+static void maf_window_call(Dev& d, size_t work_bytes, void* d_window, const std::function<int(void*, uint64_t*, uint8_t*)>& call,
+                            const MafSink& sink) {
+  void* d_work = d.alloc(work_bytes);
+  uint64_t bytes = 0;
+  d.check(call(d_work, &bytes, nullptr));
+  auto* d_out = (uint8_t*)d.alloc((size_t)bytes + 16);
+  d.check(call(d_work, &bytes, d_out));
+  d.release(d_work);
+  d.release(d_window);
+  sink(d, d_out, (size_t)bytes);
+}
+
+/* The driver of chunk, filter and rename: the input piece by piece (MafChunks: device splitter or host reader; the records in
+ * front of a reader's error are written first), every piece's text in block order behind `header`.  --gpus N: device g takes
+ * a contiguous range of the piece's blocks; device 0's windows are the first text of the piece and leave as they are made (its
+ * worker thread is the only one writing while the devices work), the others keep theirs in HBM until the devices in front of
+ * them are done.  The bytes are those of one device. */
+struct MafPiece {
+  const MafInput& in;
+  const std::vector<const MafRecord*>& recs;
+  size_t budget;      /* a window's text bound: 256 MiB, or the command's environment variable */
+  uint32_t n;         /* blocks [0, n) go to the devices: all of them unless `plan` says otherwise */
+  std::string error;  /* what `plan` found: raised behind the piece's text */
+};
+/* run: blocks [lo, hi) of the piece on device g (the rows are in place on device 0 behind the device reader); true: the text
+ * ends behind this range's windows, and end_message is the error.  plan (optional) runs on the main thread in front of a
+ * piece's device work: it may write the piece on the host and set n and error. */
+using MafPieceRun = std::function<bool(const MafPiece&, int g, Dev&, bool in_place, uint32_t lo, uint32_t hi, const MafSink&)>;
+static int maf_pieces(const std::string* input, const std::string& header, const char* budget_env, Output& out,
+                      const MafPieceRun& run, const std::string& end_message = std::string(),
+                      const std::function<void(MafPiece&, Output&)>& plan = nullptr) {
+  Dev d;
+  MafDevices md(d);
+  size_t budget = (size_t)1 << 28;
+  if (const char* e = getenv(budget_env)) budget = std::max<size_t>(1, (size_t)strtoull(e, nullptr, 10));
+  std::string pending_error;
+  MafChunks chunks(input);
+  chunks.keep_going = true;
+  out.write(header + "\n"); /* the input's header is dropped */
+  MafInput min;
+  g_timer.mark("host");
+  for (;;) {
+    bool more = false;
+    try {
+      more = chunks.next(d, min);
+    } catch (Error& e) {
+      pending_error = e.msg;
+    }
+    g_timer.mark("read + upload + split");
+    if (!more) break;
+    const std::vector<const MafRecord*> all = all_records(min.recs);
+    MafPiece piece{min, all, budget, (uint32_t)all.size(), std::string()};
+    if (plan) plan(piece, out);
+    const int ng = md.count();
+    std::vector<std::vector<std::pair<const uint8_t*, size_t>>> texts((size_t)ng);
+    std::vector<char> ends((size_t)ng, 0);
+    auto part = [&](int g) {
+      const uint32_t lo = (uint32_t)((uint64_t)piece.n * g / ng), hi = (uint32_t)((uint64_t)piece.n * (g + 1) / ng);
+      if (lo == hi) return;
+      ends[(size_t)g] = run(piece, g, md.dev(g), g == 0 && min.on_device, lo, hi, [&, g](Dev& dg, const uint8_t* t, size_t bytes) {
+        if (g == 0) {
+          stream_out(dg, out, t, bytes, ng == 1); /* the phase timer is the main thread's */
+          dg.release((void*)t);
+        } else {
+          texts[(size_t)g].emplace_back(t, bytes);
+        }
+      });
+    };
+    if (ng == 1)
+      part(0);
+    else
+      on_devices(ng, part);
+    bool ended = false;
+    for (int g = 0; g < ng && !ended; g++) { /* the text ends behind the first device that says so */
+      for (const auto& t : texts[(size_t)g]) stream_out(md.dev(g), out, t.first, t.second);
+      ended = ends[(size_t)g] != 0;
+    }
+    md.release_all();
+    if (ended)
+      pending_error = end_message;
+    else if (!piece.error.empty())
+      pending_error = piece.error;
+    if (pending_error.empty() && !min.error.empty()) pending_error = min.error;
+    if (!pending_error.empty()) break;
+  }
+  out.close();
+  g_timer.mark("write");
+  if (!pending_error.empty()) fail(pending_error);
+  return leave(0);
+}
+
 #include "cmd_chunk.inc"
 
 void log_warn(const std::string& msg);
