@@ -341,7 +341,10 @@ int wga_maf_call_vcf(wga_ctx*, uint32_t n, const uint8_t* d_rows, const uint64_t
  * blocks) into d_out + out_off.  d_status[n]: 0, or the reason a stream is corrupt (WGA_INF_* in the kernel source: the
  * input ends inside a symbol, a bad block type / stored length, bad code lengths, an unused bit pattern, a distance in front
  * of the block, a size other than ISIZE); a corrupt block never writes outside its own out_len bytes.  The CRC32 of a
- * member is not checked (neither does the host reader this replaces). */
+ * member is not part of its DEFLATE stream: wga_bgzf_crc32 computes it from the inflated bytes, for the caller to compare
+ * with the member's trailer (the four bytes in front of ISIZE) as gzread and htslib do.
+ *   wga_bgzf_crc32(d_text, n, d_blocks, d_crc)  d_crc[k] = CRC-32 of d_text[out_off .. out_off + out_len) of member k (one wave
+ *                                               per member; in_off / in_len are not read; out_len < 2^29) */
 typedef struct {
   uint64_t in_off;
   uint32_t in_len, out_len;
@@ -349,6 +352,7 @@ typedef struct {
 } wga_bgzf_block;
 int wga_bgzf_inflate(wga_ctx*, const uint8_t* d_in, uint64_t in_bytes, uint32_t n_blocks, const wga_bgzf_block* d_blocks,
                      uint8_t* d_out, uint32_t* d_status);
+int wga_bgzf_crc32(wga_ctx*, const uint8_t* d_text, uint32_t n_blocks, const wga_bgzf_block* d_blocks, uint32_t* d_crc);
 
 /* ---- paf2chain: the data lines of parse_cigar_to_chain + cigar_unit_chain
  *      (cigar.rs:251-295,460-490) and the head / tail indel trim of parse_cigar_to_trim

@@ -128,14 +128,15 @@ def test_paf2maf_end_to_end(cli, tmp_path):
     assert rc != 0 and "already exists" in (err if isinstance(err, str) else err.decode())
 
 
-def _bgzf_write(path, data, block=0xFF00):
-    """BGZF (SAM spec 4.1): gzip members of <= 64 KB with the block size in a BC extra field, then the EOF marker"""
+def _bgzf_write(path, data, block=0xFF00, level=6):
+    """BGZF (SAM spec 4.1): gzip members of <= 64 KB with the block size in a BC extra field, then the EOF marker;
+    level 0: stored blocks, the data as it is behind the member header and five bytes of block header"""
     import struct
     import zlib
     with open(path, "wb") as f:
         for a in list(range(0, len(data), block)) + [None]:
             chunk = b"" if a is None else data[a:a + block]
-            co = zlib.compressobj(6, zlib.DEFLATED, -15)
+            co = zlib.compressobj(level, zlib.DEFLATED, -15)
             cdata = co.compress(chunk) + co.flush()
             bsize = 18 + len(cdata) + 8
             f.write(b"\x1f\x8b\x08\x04\0\0\0\0\0\xff\x06\0BC\x02\0" + struct.pack("<H", bsize - 1) + cdata +
@@ -201,6 +202,49 @@ def test_paf2maf_fasta_readers(cli, tmp_path):
     open(bad, "wb").write(bytes(raw))
     rc, out, err = run(cli, "paf2maf", paf, "-g", t_fa, "-q", bad)
     assert rc == 1 and "ERROR" in err, err
+
+
+def _damage_stored_byte(src, dst, member, at, text, block, swap):
+    """the file `src` (_bgzf_write at level 0) with one byte of member `member`'s stored data, `at` bytes into it, replaced
+    through the map `swap`: the DEFLATE stream stays well formed and as long as it was, only the member's CRC-32 is wrong"""
+    raw = bytearray(open(src, "rb").read())
+    tab, _ = pc.bgzf_table(bytes(raw))
+    pos = int(tab["in_off"][member]) + 5 + at
+    assert raw[int(tab["in_off"][member])] & 7 in (0, 1)          # a stored block
+    while raw[pos] not in swap:
+        pos, at = pos + 1, at + 1
+    assert at < int(tab["out_len"][member]) and raw[pos] == text[member * block + at]
+    raw[pos] = swap[raw[pos]]
+    open(dst, "wb").write(bytes(raw))
+
+
+def test_bgzf_member_crc_is_checked(cli, tmp_path):
+    """a bgzipped FASTA or PAF whose DEFLATE streams are well formed but hold another byte than was written (stored members,
+    one base changed): the member's CRC-32 catches it — on the device path and on the host path — instead of wrong bases
+    in the MAF with exit status 0"""
+    b = synth.make_paf_batch(81, 12, 150, 40000)
+    mapq = np.arange(12)
+    t_fa, q_fa, paf = _write_paf2maf_case(tmp_path, b, mapq)
+    q_txt = open(q_fa, "rb").read()
+    qbgz, qbad = str(tmp_path / "q.bgz.fa.gz"), str(tmp_path / "q.bad.fa.gz")
+    _bgzf_write(qbgz, q_txt, block=3000, level=0)
+    _damage_stored_byte(qbgz, qbad, 5, 100, q_txt, 3000, {65: 67, 67: 71, 71: 84, 84: 65})     # a base to another base
+    for env in ({}, {"WGA_BGZF_DEVICE": "0"}):
+        rc, out, err = run(cli, "paf2maf", paf, "-g", t_fa, "-q", qbgz, env=env)
+        assert rc == 0 and out == _expected_maf(b, mapq, t_fa, qbgz, 12), (env, err)
+        rc, out, err = run(cli, "paf2maf", paf, "-g", t_fa, "-q", qbad, env=env)
+        assert rc == 1 and "corrupt BGZF block" in err, (env, rc, err)
+    # the PAF / MAF reader has checked the CRC-32 all along: the same damage in a bgzipped PAF
+    text = open(paf, "rb").read()
+    pbgz, pbad = str(tmp_path / "in.paf.bgz"), str(tmp_path / "bad.paf.bgz")
+    _bgzf_write(pbgz, text, block=700, level=0)
+    _damage_stored_byte(pbgz, pbad, 1, 50, text, 700, {48 + d: 48 + (d + 1) % 10 for d in range(10)})   # a digit to the next
+    want = run(cli, "stat", "-f", "paf", paf)
+    for env in ({}, {"WGA_BGZF_DEVICE": "0"}):
+        rc, out, err = run(cli, "stat", "-f", "paf", pbgz, env=env)
+        assert (rc, out) == want[:2] and rc == 0, (env, err)
+        rc, out, err = run(cli, "stat", "-f", "paf", pbad, env=env)
+        assert rc == 1 and out == b"" and "IO error:" in err, (env, rc, err)
 
 
 def test_paf2maf_error_is_streamed(cli, tmp_path):

@@ -2052,6 +2052,475 @@ def check_bgzf_inflate(eng):
 
 
 # ------------------------------------------------------------------------------------------------
+# K17 on hand-built DEFLATE streams (tests/deflate_craft.py): the legal streams no encoder of the suite emits, the illegal
+# ones by the status they must get, every truncation of one stream and every single-bit mutant of it.  zlib is the judge
+# (deflate_craft.zlib_verdict) of every member; where a case names a status, that status is asserted on top.
+# ------------------------------------------------------------------------------------------------
+INF_OK, INF_INPUT, INF_TYPE, INF_CODES, INF_SYMBOL, INF_DIST, INF_SIZE = range(7)    # WGA_INF_* (wga_kernels3.h)
+INF_GAP = 32                                                                         # guard bytes around every member's output
+
+
+def inflate_guarded(eng, img, rows, in_bytes=None):
+    """one wga_bgzf_inflate call over rows = [(in_off, in_len, out_len)] into `img`: every member has an output range of its
+    own with INF_GAP bytes of 0x23 in front of it and behind it, out_off takes every residue mod 8 in turn; the gaps and the
+    tail are 0x23 afterwards.  -> (status per member, bytes of every member's range)"""
+    tab = np.zeros(len(rows), dtype=[("in_off", "<u8"), ("in_len", "<u4"), ("out_len", "<u4"), ("out_off", "<u8")])
+    pos = INF_GAP
+    for k, (in_off, in_len, out_len) in enumerate(rows):
+        pos += (k - pos) % 8
+        tab[k] = (in_off, in_len, out_len, pos)
+        pos += out_len + INF_GAP
+    total = pos + INF_GAP
+    assert len(rows) < 8 or set(int(x) % 8 for x in tab["out_off"]) == set(range(8))
+    out = eng.empty(total, np.uint8).fill(0x23)
+    status = eng.empty(len(rows), np.uint32).fill(0xFF)
+    d_in = eng.upload(np.frombuffer(bytes(img) + b"\0" * 16, dtype=np.uint8))
+    eng.bgzf_inflate(d_in, len(img) if in_bytes is None else in_bytes, len(rows), eng.upload(tab.view(np.uint8)), out, status)
+    got = out.numpy()
+    guard = np.ones(total, dtype=bool)
+    for a, n in zip(tab["out_off"], tab["out_len"]):
+        guard[int(a):int(a) + int(n)] = False
+    touched = np.flatnonzero(guard & (got != 0x23))
+    assert touched.size == 0, ("bytes outside every member's range were written", touched[:8].tolist())
+    return status.numpy().copy(), [got[int(a):int(a) + int(n)].tobytes() for a, n in zip(tab["out_off"], tab["out_len"])]
+
+
+def inflate_judged(eng, cases, in_bytes_cut=0):
+    """cases = [(name, payload, out_len, status the case names or None, True if the case is meant to be legal)]: all of them
+    through one call; the kernel's verdict on every member is zlib's, and the named status where there is one"""
+    import deflate_craft as dc
+    img, rows = bytearray(), []
+    for name, payload, out_len, _, _ in cases:
+        rows.append((len(img), len(payload), out_len))
+        img += payload
+    st, outs = inflate_guarded(eng, img, rows, in_bytes=len(img) - in_bytes_cut)
+    wrong = []
+    for k, (name, payload, out_len, named, legal) in enumerate(cases):
+        want = dc.zlib_verdict(payload, out_len) if not (in_bytes_cut and k == len(cases) - 1) else None
+        assert (want is not None) == legal, ("the case is not what its name says (zlib)", name)
+        if want is not None:
+            if st[k] != 0 or outs[k] != want:
+                wrong.append((name, int(st[k]), "zlib accepts"))
+        elif st[k] == 0 or (named is not None and st[k] != named):
+            wrong.append((name, int(st[k]), "zlib rejects" if named is None else "zlib rejects, status %d named" % named))
+    assert not wrong, wrong
+    return st
+
+
+def _flat_code(n, used):
+    """code lengths over n symbols, complete over `used` (two or more symbols), as flat as a prefix code can be"""
+    used = sorted(used)
+    k = max(1, (len(used) - 1).bit_length())
+    short = (1 << k) - len(used)
+    lens = [0] * n
+    for i, s in enumerate(used):
+        lens[s] = k - 1 if i < short else k
+    return lens
+
+
+def _crafted_legal():
+    """group A: (name, payload, bytes) of legal streams"""
+    import deflate_craft as dc
+    rng = np.random.default_rng(1951)
+    A = []
+
+    def add(name, bits, data, tail=b""):
+        A.append((name, bits.bytes() + tail, bytes(data)))
+
+    # a stored block behind a Huffman block that ends at every bit position (fixed literals below 144 take 8 bits, the others
+    # 9: j of those move the end by j bits), with 0..4 bytes of stored data (the LEN / NLEN words 0..4 bytes in front of the
+    # payload's end) and 0..4 bytes of payload behind the final block; Huffman blocks of 2 to 30 bytes leave the bit reader
+    # with and without a word fetched ahead, with 0 to 7 whole bytes in its buffer
+    ends = set()
+    for a in (0, 1, 2, 3, 4, 5, 6, 9, 20):
+        for j in range(8):
+            lits = [65 + (i % 26) for i in range(a)] + [200 + i for i in range(j)]
+            for d in range(5):
+                for t in range(5):
+                    b = dc.Bits()
+                    dc.fixed(b, lits + ["eob"], False)
+                    ends.add(b.n % 8)
+                    sd = bytes(rng.integers(0, 256, d, dtype=np.uint8))
+                    dc.stored(b, sd, True)
+                    add("stored behind fixed a=%d j=%d d=%d t=%d" % (a, j, d, t), b, bytes(lits) + sd, tail=b"\xa5" * t)
+            b = dc.Bits()                          # not the final block: an empty fixed block behind it
+            dc.fixed(b, lits + ["eob"], False)
+            dc.stored(b, b"xyz", False)
+            dc.fixed(b, ["eob"], True)
+            add("stored in the middle a=%d j=%d" % (a, j), b, bytes(lits) + b"xyz")
+    assert ends == set(range(8))
+    lit2 = _flat_code(257, [97, 98, 99, 256])
+    lit1 = _flat_code(257, [97, 98, 256])          # 'a' in one bit: j of them move the end by j bits
+    ends = set()
+    for j in range(8):                             # the same behind a dynamic block
+        for d in range(5):
+            b = dc.Bits()
+            dc.dynamic(b, lit1, [0], [98, 97, 98] + [97] * j + ["eob"], False)
+            ends.add(b.n % 8)
+            dc.stored(b, b"WXYZ"[:d], True)
+            add("stored behind dynamic j=%d d=%d" % (j, d), b, b"bab" + b"a" * j + b"WXYZ"[:d])
+    assert ends == set(range(8))
+    # empty blocks
+    b = dc.Bits()
+    dc.fixed(b, [72, 105, "eob"], False)
+    dc.stored(b, b"", False)
+    dc.fixed(b, [33, "eob"], True)
+    add("empty stored block in the middle", b, b"Hi!")
+    b = dc.Bits()
+    dc.fixed(b, [72, 105, "eob"], False)
+    dc.stored(b, b"", True)
+    add("empty stored block at the end", b, b"Hi")
+    b = dc.Bits()
+    dc.stored(b, b"", True)
+    assert b.bytes() == b"\x01\x00\x00\xff\xff"
+    add("empty stored block alone", b, b"")
+    b = dc.Bits()
+    dc.fixed(b, [72, "eob"], False)
+    dc.fixed(b, ["eob"], False)
+    dc.fixed(b, [105, "eob"], True)
+    add("empty fixed block in the middle", b, b"Hi")
+    b = dc.Bits()
+    dc.fixed(b, [72, "eob"], False)
+    dc.dynamic(b, _flat_code(257, [0, 256]), [0], ["eob"], False)
+    dc.dynamic(b, _flat_code(257, [0, 256]), [0], ["eob"], False)
+    dc.fixed(b, [105, "eob"], True)
+    add("two empty dynamic blocks in a row", b, b"Hi")
+    # payloads of 2..40 bytes (10 bits is the shortest stream there is: a one-byte member is in the truncation sweep and in
+    # _crafted_illegal): the last bytes of a payload come one by one
+    for n in range(2, 41):
+        b = dc.Bits()
+        lits = [48 + (i % 75) for i in range(n - 2)]
+        dc.fixed(b, lits + ["eob"], True)
+        assert len(b.bytes()) == n
+        add("fixed payload of %d bytes" % n, b, bytes(lits))
+        if n >= 5:
+            b = dc.Bits()
+            dc.stored(b, bytes(lits[:n - 5]), True)
+            assert len(b.bytes()) == n
+            add("stored payload of %d bytes" % n, b, bytes(lits[:n - 5]))
+    # matches
+    b = dc.Bits()
+    dc.fixed(b, [97, 98, 99, 100, "eob"], False)
+    dc.fixed(b, [("match", 4, 4), "eob"], True)
+    add("match into the block in front", b, b"abcdabcd")
+    b = dc.Bits()
+    dc.fixed(b, [97, 98, 99, 100, "eob"], False)
+    dc.stored(b, b"xyz", False)
+    dc.fixed(b, [("match", 5, 7), "eob"], True)
+    add("match across a stored block", b, b"abcdxyzabcdx")
+    b = dc.Bits()
+    dc.fixed(b, [1, 2, 3, ("match", 3, 3), "eob"], True)
+    add("dist == n_out", b, bytes([1, 2, 3, 1, 2, 3]))
+    b = dc.Bits()
+    dc.stored(b, b"pqr", False)
+    dc.fixed(b, [("match", 3, 3), "eob"], True)
+    add("dist == n_out behind a stored block", b, b"pqrpqr")
+    far = bytes(rng.integers(0, 256, 32768, dtype=np.uint8))
+    b = dc.Bits()
+    dc.stored(b, far, False)
+    dc.fixed(b, [("match", 258, 32768), "eob"], True)
+    add("distance 32768, length 258", b, far + far[:258])
+    b = dc.Bits()
+    dc.fixed(b, [7, ("match", 258, 1), "eob"], True)
+    add("distance 1, length 258", b, bytes([7]) * 259)
+    b = dc.Bits()
+    dc.fixed(b, [7, ("match", 258, 1, 284), "eob"], True)
+    add("length 258 as symbol 284 with extra bits 31", b, bytes([7]) * 259)
+    # codes longer than the first-level table: lengths 1..14 and two of 15 bits, literals and distances
+    lit15 = [0] * 258
+    for i, s in enumerate(range(66, 78)):
+        lit15[s] = 1 + i
+    lit15[257], lit15[256], lit15[65], lit15[78] = 13, 14, 15, 15
+    dist15 = [15, 15] + list(range(1, 15))
+    b = dc.Bits()
+    dc.dynamic(b, lit15, dist15, [65, 78, 66, 77, 65, ("match", 3, 1), ("match", 3, 2), ("match", 3, 5), 78, "eob"], True)
+    add("15-bit literal and distance codes", b, b"ANBMA" + b"AAA" + b"AAA" + b"AAA" + b"N")
+    lit910 = [0] * 257
+    for i, s in enumerate(range(97, 105)):
+        lit910[s] = 1 + i
+    lit910[105], lit910[106], lit910[256] = 9, 10, 10
+    b = dc.Bits()
+    dc.dynamic(b, lit910, [0], [105, 106, 104, 105, 97, 106, 106, 105, "eob"], True)
+    add("9-bit and 10-bit codes", b, b"ijhiajji")
+    b = dc.Bits()
+    dc.dynamic(b, _flat_code(286, range(286)), _flat_code(30, range(30)),
+               [0, 255, 143, 144, ("match", 258, 2), ("match", 3, 4), ("match", 227, 193), 17, "eob"], True)
+    data = bytearray([0, 255, 143, 144])
+    for n, d in ((258, 2), (3, 4), (227, 193)):
+        for _ in range(n):
+            data.append(data[-d])
+    add("HLIT = 29 and HDIST = 29", b, bytes(data) + bytes([17]))
+    # a 16 that repeats the last literal/length length into the distance lengths
+    lit16 = [0] * 259
+    lit16[97], lit16[98], lit16[256], lit16[257], lit16[258] = 1, 2, 3, 4, 4
+    b = dc.Bits()
+    dc.dynamic(b, lit16, [4] * 16, [97, 98, 98] * 6 + [("match", 3, 3), ("match", 4, 16), "eob"], True,
+               cl_symbols=dc.cl_rle(lit16[:258]) + [(16, 6), (16, 6), (16, 5)])      # the first 16: symbol 258 and five distances
+    data = bytearray(b"abb" * 6)
+    for n, d in ((3, 3), (4, 16)):
+        for _ in range(n):
+            data.append(data[-d])
+    add("a 16 from the literal/length lengths into the distance lengths", b, data)
+    lit_m = _flat_code(258, [97, 256, 257, 98])
+    b = dc.Bits()
+    dc.dynamic(b, lit_m, [1], [97, ("match", 3, 1), 98, "eob"], True)
+    add("one distance code of one bit", b, b"aaaab")
+    b = dc.Bits()
+    dc.dynamic(b, lit2, [0], [97, 98, 99, "eob"], True, hdist=0)
+    add("HDIST = 0, length 0, no matches", b, b"abc")
+    only_eob = [0] * 256 + [1]
+    b = dc.Bits()
+    dc.fixed(b, [79, "eob"], False)
+    dc.dynamic(b, only_eob, [0], ["eob"], False)
+    dc.dynamic(b, only_eob, [0], ["eob"], True)
+    add("end-of-block alone under a one-bit code", b, b"O")
+    # HCLEN: with the four lengths of HCLEN = 0 (symbols 16, 17, 18 and 0) every code length is 0, which no block may have
+    # (_crafted_illegal holds that one); HCLEN = 1 adds symbol 8: 256 codes of 8 bits
+    lit8 = [0] + [8] * 256
+    b = dc.Bits()
+    dc.dynamic(b, lit8, [0], [1, 2, 255, "eob"], True, cl_symbols=[(0,)] + [(8,)] * 256 + [(0,)], cl_lengths=[1 if s in (0, 8) else 0 for s in range(19)])
+    assert (b.acc >> 13) & 15 == 1
+    add("HCLEN = 1", b, bytes([1, 2, 255]))
+    return A
+
+
+def _crafted_illegal():
+    """group B: (name, payload, out_len, the status the case names, or None) of streams zlib rejects"""
+    import deflate_craft as dc
+    B = []
+    pad = b"\0\0\0\0"      # behind the damage: a decoder that needs more bits than zlib to see it still has them
+
+    def add(name, bits, out_len, status):
+        B.append((name, bits.bytes() + pad, out_len, status))
+
+    lit2 = _flat_code(257, [97, 98, 99, 256])
+    b = dc.Bits()
+    dc.block_type(b, 3, True)
+    add("block type 3", b, 0, INF_TYPE)
+    b = dc.Bits()
+    dc.fixed(b, [97, "eob"], False)
+    dc.block_type(b, 3, False)
+    add("block type 3 behind a block", b, 1, INF_TYPE)
+    b = dc.Bits()
+    dc.stored(b, b"abc", True, nlen=0xFFFD)
+    add("stored: NLEN is not ~LEN", b, 3, INF_TYPE)
+    b = dc.Bits()
+    dc.stored(b, b"abc", True, length=10)
+    B.append(("stored: LEN past the payload", b.bytes(), 10, INF_INPUT))
+    B.append(("a payload of one byte", b"\x03", 0, None))
+    for hlit in (30, 31):
+        b = dc.Bits()
+        dc.dynamic(b, lit2, [0], [97, "eob"], True, hlit=hlit)
+        add("HLIT = %d" % hlit, b, 1, INF_CODES)
+    for hdist in (30, 31):
+        b = dc.Bits()
+        dc.dynamic(b, lit2, [0], [97, "eob"], True, hdist=hdist)
+        add("HDIST = %d" % hdist, b, 1, INF_CODES)
+    b = dc.Bits()
+    dc.dynamic(b, lit2, [0], [97, "eob"], True, cl_lengths=[2 if s in (0, 2, 18) else 0 for s in range(19)])
+    add("incomplete code-length code", b, 1, INF_CODES)
+    b = dc.Bits()
+    dc.dynamic(b, lit2, [0], [], True, cl_symbols=[], cl_lengths=[1 if s == 0 else 0 for s in range(19)])
+    add("code-length code of one code", b, 0, INF_CODES)
+    b = dc.Bits()
+    dc.dynamic(b, lit2, [0], [], True, cl_symbols=[], cl_lengths=[1 if s in (0, 2, 18) else 0 for s in range(19)])
+    add("over-subscribed code-length code", b, 0, INF_CODES)
+    b = dc.Bits()
+    dc.dynamic(b, lit2, [0], [], True, cl_symbols=[(18, 138), (18, 120)], hclen=0,
+               cl_lengths=[2 if s in (16, 17, 18, 0) else 0 for s in range(19)])
+    add("HCLEN = 0: no length but 0", b, 0, INF_CODES)
+    b = dc.Bits()
+    dc.dynamic(b, lit2, [0], [97, "eob"], True, cl_symbols=[(16, 3)] + dc.cl_rle(lit2[3:] + [0]))
+    add("a 16 as the first symbol", b, 1, INF_CODES)
+    b = dc.Bits()
+    dc.dynamic(b, lit2, [0], [97, "eob"], True, cl_symbols=dc.cl_rle(lit2) + [(18, 11)])
+    add("a repeat past nlen + ndist", b, 1, INF_CODES)
+    b = dc.Bits()
+    dc.dynamic(b, lit2, [2] * 4, [97, "eob"], True, cl_symbols=dc.cl_rle(lit2) + [(2,), (16, 4)])
+    add("a 16 past nlen + ndist", b, 1, INF_CODES)
+    b = dc.Bits()
+    dc.dynamic(b, _flat_code(257, [97, 98, 99, 100]), [0], [97, 98], True)
+    add("no end-of-block code", b, 2, INF_CODES)
+    over = [0] * 257
+    over[97], over[98], over[256] = 1, 1, 1
+    b = dc.Bits()
+    dc.dynamic(b, over, [0], [], True)
+    add("over-subscribed literal/length set", b, 0, INF_CODES)
+    b = dc.Bits()
+    dc.dynamic(b, lit2, [1, 1, 1], [], True)
+    add("over-subscribed distance set", b, 0, INF_CODES)
+    two = [0] * 257
+    two[97], two[256] = 2, 2
+    b = dc.Bits()
+    dc.dynamic(b, two, [0], [97, "eob"], True)
+    add("incomplete literal/length set of two codes", b, 1, INF_CODES)
+    three = [0] * 257
+    three[97], three[98], three[256] = 1, 3, 3
+    b = dc.Bits()
+    dc.dynamic(b, three, [0], [97, "eob"], True)
+    add("incomplete literal/length set of three codes", b, 1, INF_CODES)
+    b = dc.Bits()
+    dc.dynamic(b, lit2, [2, 2], [97, "eob"], True)
+    add("incomplete distance set of two codes", b, 1, INF_CODES)
+    b = dc.Bits()
+    dc.dynamic(b, lit2, [1, 2], [97, "eob"], True)
+    add("incomplete distance set of lengths 1 and 2", b, 1, INF_CODES)
+    # zlib's rule (inflate_table): an incomplete set passes only as ONE code of ONE bit
+    b = dc.Bits()
+    dc.dynamic(b, [0] * 256 + [2], [0], ["eob"], True)
+    add("a single literal/length code of two bits", b, 0, INF_CODES)
+    for l in (2, 15):
+        b = dc.Bits()
+        dc.dynamic(b, lit2, [l], [97, "eob"], True)
+        add("a single distance code of %d bits" % l, b, 1, INF_CODES)
+        b = dc.Bits()
+        dc.dynamic(b, lit2, [0, 0, l], [97, "eob"], True)
+        add("a single distance code of %d bits, not the first" % l, b, 1, INF_CODES)
+    for s in (286, 287):
+        b = dc.Bits()
+        dc.fixed(b, [97, ("lit", s), "eob"], True)
+        add("fixed literal/length symbol %d" % s, b, 1, INF_SYMBOL)
+    for s in (30, 31):
+        b = dc.Bits()
+        dc.fixed(b, [97, 98, 99, ("rawmatch", 257, 0, s, 0), "eob"], True)
+        add("fixed distance symbol %d" % s, b, 6, INF_SYMBOL)
+    b = dc.Bits()
+    dc.dynamic(b, _flat_code(258, [97, 98, 256, 257]), [0], [97, ("lit", 257)], True)
+    add("a match where the distance set is empty", b, 4, INF_SYMBOL)
+    b = dc.Bits()
+    dc.dynamic(b, _flat_code(258, [97, 98, 256, 257]), [1], [97, ("lit", 257)], True)
+    b.field(1, 1)
+    add("the pattern a one-bit distance code leaves free", b, 4, INF_SYMBOL)
+    b = dc.Bits()
+    dc.dynamic(b, [0] * 256 + [1], [0], [], True)
+    b.field(1, 1)
+    add("the pattern a one-bit end-of-block code leaves free", b, 0, INF_SYMBOL)
+    b = dc.Bits()
+    dc.fixed(b, [("match", 3, 1), "eob"], True)
+    add("dist == n_out + 1 at the start", b, 3, INF_DIST)
+    b = dc.Bits()
+    dc.fixed(b, [97, 98, ("match", 3, 3), "eob"], True)
+    add("dist == n_out + 1", b, 5, INF_DIST)
+    b = dc.Bits()
+    dc.stored(b, b"abc", False)
+    dc.fixed(b, [("match", 3, 4), "eob"], True)
+    add("dist == n_out + 1 behind a stored block", b, 6, INF_DIST)
+    b = dc.Bits()
+    dc.fixed(b, [97, 98, 99, "eob"], True)
+    add("one byte too many from a literal", b, 2, INF_SIZE)
+    add("one byte too few at the end of the block", b, 4, INF_SIZE)
+    b = dc.Bits()
+    dc.fixed(b, [97, ("match", 5, 1), "eob"], True)
+    add("one byte too many from a match", b, 5, INF_SIZE)
+    add("one byte too few behind a match", b, 7, INF_SIZE)
+    b = dc.Bits()
+    dc.fixed(b, [97, "eob"], False)
+    dc.stored(b, b"abc", True)
+    add("one byte too many from a stored block", b, 3, INF_SIZE)
+    add("one byte too few behind a stored block", b, 5, INF_SIZE)
+    b = dc.Bits()
+    dc.stored(b, b"", True)
+    add("one byte too few behind an empty stored block", b, 1, INF_SIZE)
+    return B
+
+
+def crafted_sweep_stream():
+    """groups C and D: one stream of at most 400 bytes — a dynamic block (literals, matches, a run-length coded header), a
+    stored block, a fixed block and a second dynamic block (another code, a match into the blocks in front) -> (payload, bytes)"""
+    import deflate_craft as dc
+    rng = np.random.default_rng(400)
+    b = dc.Bits()
+    lit_a = [0] * 260
+    for s, l in ((65, 2), (67, 2), (71, 2), (84, 3), (10, 4), (78, 6), (256, 6), (257, 6), (258, 7), (259, 7)):
+        lit_a[s] = l
+    text = [int(x) for x in rng.choice([65, 67, 71, 84], 70)]
+    syms_a = text[:30] + [("match", 4, 9), 78, 10] + text[30:60] + [("match", 5, 33), ("match", 3, 1)] + text[60:] + [10, "eob"]
+    dc.dynamic(b, lit_a, _flat_code(12, [0, 5, 6, 9, 10]), syms_a, False)
+    st = bytes(rng.choice(list(b"ACGTacgtN\n"), 150).astype(np.uint8))
+    dc.stored(b, st, False)
+    fx = [int(x) for x in rng.choice(list(b"ACGTN>chr1\n"), 60)]
+    dc.fixed(b, fx[:40] + [("match", 10, 120), ("match", 3, 2)] + fx[40:] + ["eob"], False)
+    lit_b = _flat_code(270, [97, 99, 103, 116, 256, 265, 269])
+    dc.dynamic(b, lit_b, [0, 0, 0, 0, 1], [97, 99, 103, 116] * 6 + [("match", 12, 5), 116, ("match", 20, 6), 97, "eob"], True)
+    payload = b.bytes()
+    import zlib
+    want = zlib.decompressobj(-15).decompress(payload)
+    assert dc.zlib_verdict(payload, len(want)) == want and len(payload) <= 400, len(payload)
+    return payload, want
+
+
+def check_bgzf_inflate_crafted(eng):
+    """wga_bgzf_inflate on hand-built DEFLATE streams, every member judged by zlib (deflate_craft.zlib_verdict): group A legal
+    streams, group B illegal ones (with the status each must get), group C every truncation of one stream, group D every
+    single-bit mutant of it.  Every member's output lies between guard bytes that stay as they were."""
+    import deflate_craft as dc
+    # A
+    legal = _crafted_legal()
+    for name, payload, data in legal:
+        assert dc.zlib_verdict(payload, len(data)) == data, ("the stream is not what its name says (zlib)", name)
+    st = inflate_judged(eng, [(name, payload, len(data), INF_OK, True) for name, payload, data in legal])
+    assert (st == 0).all()
+    # B; the last member's stream is whole, and the image is said to end one byte in front of its end
+    illegal = _crafted_illegal()
+    b = dc.Bits()
+    dc.fixed(b, [97, 98, 99, "eob"], True)
+    cases = [(name, payload, out_len, named, False) for name, payload, out_len, named in illegal]
+    assert dc.zlib_verdict(b.bytes(), 3) == b"abc"
+    inflate_judged(eng, cases + [("in_off + in_len > in_bytes", b.bytes(), 3, INF_INPUT, False)], in_bytes_cut=1)
+    st, _ = inflate_guarded(eng, b.bytes(), [(1 << 40, len(b.bytes()), 3), (0, len(b.bytes()), 3), (2, 1 << 31, 3)])
+    assert st.tolist() == [INF_INPUT, INF_OK, INF_INPUT], st
+    # C
+    payload, want = crafted_sweep_stream()
+    n = len(payload)
+    st, outs = inflate_guarded(eng, payload, [(0, k, len(want)) for k in range(n + 1)])
+    for k in range(n):
+        assert dc.zlib_verdict(payload[:k], len(want)) is None
+    assert (st[:n] != 0).all() and st[n] == 0 and outs[n] == want, np.flatnonzero(st[:n] == 0)
+    # D
+    img, verdicts = bytearray(), []
+    for bit in range(8 * n):
+        m = bytearray(payload)
+        m[bit >> 3] ^= 1 << (bit & 7)
+        img += m
+        verdicts.append(dc.zlib_verdict(m, len(want)))
+    share = sum(v is not None for v in verdicts) / len(verdicts)
+    print("single-bit mutants of the %d-byte stream: zlib accepts %.1f %%" % (n, 100 * share))
+    assert 0.05 <= share <= 0.95, share
+    st, outs = inflate_guarded(eng, img, [(k * n, n, len(want)) for k in range(8 * n)])
+    wrong = [(bit, int(st[bit]), verdicts[bit] is not None) for bit in range(8 * n)
+             if (st[bit] == 0) != (verdicts[bit] is not None) or (verdicts[bit] is not None and outs[bit] != verdicts[bit])]
+    assert not wrong, wrong[:20]
+
+
+def check_bgzf_crc32(eng):
+    """wga_bgzf_crc32 against zlib.crc32: members of 0 to 65 280 bytes (below, at and above the 64 lanes, a multiple of them and
+    one more or less, the largest BGZF members) of random bytes, zero bytes and 0xFF bytes, at every alignment, in one call"""
+    import zlib
+    rng = np.random.default_rng(32)
+    lengths = (0, 1, 3, 4, 5, 63, 64, 65, 127, 128, 129, 255, 4096, 32768, 65279, 65280)
+    text, rows, want = bytearray(b"\x23" * 5), [], []
+    for fill in ("random", 0x00, 0xFF):
+        for n in lengths:
+            for res in range(8):
+                if n > 4096 and res not in (0, 3, 6):   # the long members at three alignments: a megabyte of text, not four
+                    continue
+                text += b"\x23" * ((res - len(text)) % 8)
+                data = bytes(rng.integers(0, 256, n, dtype=np.uint8)) if fill == "random" else bytes([fill]) * n
+                rows.append((0, 0, n, len(text)))
+                want.append(zlib.crc32(data) & 0xFFFFFFFF)
+                text += data
+    tab = np.array(rows, dtype=[("in_off", "<u8"), ("in_len", "<u4"), ("out_len", "<u4"), ("out_off", "<u8")])
+    for n in lengths:
+        assert set(int(x) % 8 for x in tab["out_off"][tab["out_len"] == n]) >= ({0, 3, 6} if n > 4096 else set(range(8)))
+    crc = eng.empty(len(rows) + 1, np.uint32).fill(0x23232323)
+    eng.bgzf_crc32(eng.upload(np.frombuffer(bytes(text), dtype=np.uint8)), len(rows), eng.upload(tab.view(np.uint8)), crc)
+    got = crc.numpy()
+    assert got[len(rows)] == 0x23232323
+    wrong = [(int(tab["out_len"][k]), int(tab["out_off"][k]) % 8, hex(int(got[k])), hex(want[k])) for k in range(len(rows)) if got[k] != want[k]]
+    assert not wrong, wrong[:10]
+
+
+# ------------------------------------------------------------------------------------------------
 # K18 BGZF deflate on the device: zlib is the judge (the stream must inflate to the input), the member
 # structure is read by bgzf_table, and the device inflate (K17) must take it back as well
 # ------------------------------------------------------------------------------------------------

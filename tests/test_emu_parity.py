@@ -776,6 +776,14 @@ def test_bgzf_inflate(emu):
     pc.check_bgzf_inflate(emu)
 
 
+def test_bgzf_inflate_crafted(emu):
+    pc.check_bgzf_inflate_crafted(emu)
+
+
+def test_bgzf_crc32(emu):
+    pc.check_bgzf_crc32(emu)
+
+
 def test_bgzf_deflate(emu):
     pc.check_bgzf_deflate(emu)
 

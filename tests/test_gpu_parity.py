@@ -1346,6 +1346,14 @@ def test_bgzf_inflate(gpu):
     pc.check_bgzf_inflate(gpu)
 
 
+def test_bgzf_inflate_crafted(gpu):
+    pc.check_bgzf_inflate_crafted(gpu)
+
+
+def test_bgzf_crc32(gpu):
+    pc.check_bgzf_crc32(gpu)
+
+
 def test_bgzf_deflate(gpu):
     pc.check_bgzf_deflate(gpu)
 

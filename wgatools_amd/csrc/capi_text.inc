@@ -236,6 +236,17 @@ int wga_bgzf_inflate(wga_ctx* c, const uint8_t* d_in, uint64_t in_bytes, uint32_
   return WGA_OK;
 }
 
+int wga_bgzf_crc32(wga_ctx* c, const uint8_t* d_text, uint32_t n_blocks, const wga_bgzf_block* d_blocks, uint32_t* d_crc) {
+  int rc = ctx_bind(c);
+  if (rc) return rc;
+  if (n_blocks == 0) return WGA_OK;
+  if (!d_text || !d_blocks || !d_crc) return fail(WGA_E_INVALID_ARG, "null array", nullptr);
+  WGA_LAUNCH(k_bgzf_crc32, (n_blocks + 3u) / 4u, WGA_BLOCK, c->stream, d_text, n_blocks, (const wga_bgzf_block_dev*)d_blocks,
+             (u32*)d_crc);
+  LAUNCH_CHECK();
+  return WGA_OK;
+}
+
 int wga_pafcov_format(wga_ctx* c, const uint8_t* d_name, uint32_t name_len, const int32_t* d_cov,
                       uint64_t p0, uint32_t count, uint64_t* d_line_off, uint8_t* d_out) {
   int rc = ctx_bind(c);

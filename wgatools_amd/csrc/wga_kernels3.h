@@ -24,6 +24,7 @@
 
 #include "wga_k11_bridges.h"
 #include "wga_k10_chain.h"
+#include "wga_crc32.h"
 
 struct wga_vcf_rec_dev { /* = wga_vcf_rec (wga_hip.h) */
   u64 t_name_off, q_name_off; /* into `names` */
@@ -495,14 +496,15 @@ __global__ __launch_bounds__(256) void k_bgzf_inflate(const u8* __restrict__ in,
         err = WGA_INF_CODES;
         break;
       }
-      /* an incomplete set is only allowed when it holds a single code (zlib's rule) */
+      /* an incomplete set is only allowed as a single code of one bit (zlib's rule, inflate_table: an incomplete set passes
+       * when its longest code has one bit — two such codes are a complete set) */
       int left = inf_construct(lencode, length, nlen);
-      if (left < 0 || (left > 0 && nlen - lencode.count[0] != 1u)) {
+      if (left < 0 || (left > 0 && lencode.count[1] != nlen - lencode.count[0])) {
         err = WGA_INF_CODES;
         break;
       }
       left = inf_construct(distcode, length + nlen, ndist);
-      if (left < 0 || (left > 0 && ndist - distcode.count[0] != 1u)) {
+      if (left < 0 || (left > 0 && distcode.count[1] != ndist - distcode.count[0])) {
         err = WGA_INF_CODES;
         break;
       }
@@ -552,6 +554,43 @@ __global__ __launch_bounds__(256) void k_bgzf_inflate(const u8* __restrict__ in,
   if (!err) err = b.err;
   if (!err && n_out != cap) err = WGA_INF_SIZE;
   status[k] = err;
+}
+
+/* The CRC-32 of every member's inflated bytes, to be compared with the member's trailer (gzread and htslib check it; K17's
+ * status only says that the stream was well formed and ISIZE bytes long).  One wave per member: the 64 lanes take equal
+ * slices of ceil(out_len / 64) bytes — lane l the slice that ends 63 - l slices in front of the member's end, so that the
+ * bytes a short member lacks are missing in FRONT, where a zero register stays zero —, each by the byte and slicing-by-4
+ * tables in LDS with register 0 going in, and the partial values fold pairwise: (a, b) -> a x^(8 |b|) + b, |b| = 1, 2, 4 ...
+ * slices.  out_len < 2^29 (crc_shift); a BGZF member holds at most 2^16 bytes. */
+__global__ __launch_bounds__(256) void k_bgzf_crc32(const u8* __restrict__ text, u32 n_blocks,
+                                                    const wga_bgzf_block_dev* __restrict__ blocks, u32* __restrict__ crc_out) {
+  __shared__ u32 s_crc_t[4][256];
+  const u32 tid = threadIdx.x, lane = tid & 63u, wave = WGA_WAVE_ID(tid);
+  s_crc_t[0][tid] = k_crc_tables.byte[tid];
+  for (int t = 0; t < 3; t++) s_crc_t[t + 1][tid] = k_crc_tables.by4[t][tid];
+  __syncthreads();
+  const u64 k = (u64)blockIdx.x * 4 + wave;
+  if (k >= n_blocks) return;
+  const u32 n = blocks[k].out_len;
+  const u8* const p = text + blocks[k].out_off;
+  const u32 slice = (n + 63u) / 64u;
+  const long long stop = (long long)n - (long long)slice * (long long)(63u - lane);
+  u32 at = stop > (long long)slice ? (u32)(stop - (long long)slice) : 0u;
+  const u32 end = stop > 0 ? (u32)stop : 0u;
+  u32 crc = 0;
+  for (; at < end && (((uintptr_t)(p + at)) & 3u) != 0u; at++) crc = s_crc_t[0][(crc ^ (u32)p[at]) & 0xFFu] ^ (crc >> 8);
+  for (; at + 4u <= end; at += 4u) {
+    const u32 x = crc ^ *(const u32*)(p + at);
+    crc = s_crc_t[3][x & 0xFFu] ^ s_crc_t[2][(x >> 8) & 0xFFu] ^ s_crc_t[1][(x >> 16) & 0xFFu] ^ s_crc_t[0][x >> 24];
+  }
+  for (; at < end; at++) crc = s_crc_t[0][(crc ^ (u32)p[at]) & 0xFFu] ^ (crc >> 8);
+  u32 m = crc_shift(0x80000000u, slice); /* x^(8 slice) */
+  for (u32 lvl = 0; lvl < 6u; lvl++) {
+    const u32 other = __shfl_up(crc, 1u << lvl);
+    if ((lane & ((2u << lvl) - 1u)) == (2u << lvl) - 1u) crc = crc_mul(m, other) ^ crc;
+    m = crc_mul(m, m);
+  }
+  if (lane == 63u) crc_out[k] = crc ^ crc_shift(0xFFFFFFFFu, n) ^ 0xFFFFFFFFu;
 }
 
 #endif /* WGA_KERNELS3_H */

@@ -263,6 +263,10 @@ class Engine:
         """BGZF members inflated on the device (wga_bgzf_inflate); blocks: n x (in_off u64, in_len u32, out_len u32, out_off u64)"""
         self._check(self.lib.wga_bgzf_inflate(self.ctx, _p(d_in), int(in_bytes), int(n_blocks), _p(blocks), _p(out), _p(status)))
 
+    def bgzf_crc32(self, text, n_blocks, blocks, crc):
+        """CRC-32 of every member's inflated bytes (wga_bgzf_crc32); blocks as for bgzf_inflate, crc: n x u32"""
+        self._check(self.lib.wga_bgzf_crc32(self.ctx, _p(text), int(n_blocks), _p(blocks), _p(crc)))
+
     def bgzf_compress(self, d_in, n_bytes, out=None, eof_marker=True, in_offset=0, out_offset=0, out_cap=None):
         """bytes in HBM -> BGZF members (wga_bgzf_compress, K18); returns (DeviceArray of the worst-case size, bytes used).
         in_offset / out_offset: byte offsets into d_in / out (any alignment).  The capacity handed to the library is what `out`

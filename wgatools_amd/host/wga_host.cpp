@@ -74,7 +74,7 @@ std::string read_all(const std::string* path) {
 /* ---- BGZF: gzip members of <= 64 KB whose extra field carries the block size ("BC", SAM spec 4.1) ---------------- */
 namespace {
 struct BgzfBlock {
-  size_t cdata, clen; /* the raw deflate stream inside the file image */
+  size_t cdata, clen; /* the raw deflate stream inside the file image; the CRC-32 / ISIZE trailer stands behind it */
   size_t out, isize;
 };
 inline uint32_t le16(const unsigned char* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
@@ -264,6 +264,8 @@ std::string read_all_parallel(const std::string& path) {
         const int rc = inflate(&zs, Z_FINISH);
         if (rc != Z_STREAM_END || zs.avail_out != 0) bad = 1;
         inflateEnd(&zs);
+        /* a raw inflate does not look at the member's trailer: the CRC-32 as gzread and htslib check it */
+        if (gzip_crc32(&out[k.out], k.isize) != le32((const unsigned char*)img.data() + k.cdata + k.clen)) bad = 1;
       }
     }
   };

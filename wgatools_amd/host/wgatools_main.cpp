@@ -527,7 +527,7 @@ struct BgzfDeviceSource {
 };
 
 /* An indexed FASTA whose sequence pool lives in HBM.  The file — plain, gzip or BGZF (inflated on
- * all host cores) — is uploaded as text, wga_fasta_pool strips the line ends on the device and returns the contig table;
+ * the device or on all host cores, every member checked against its CRC-32) — is uploaded as text, wga_fasta_pool strips the line ends on the device and returns the contig table;
  * the drivers then address (contig, start, length) as pool offsets with htslib's clipping (Faidx::fetch) and never copy
  * a slice.  Commands that need bases on the host (VCF REF / ALT text, a target row of pafpseudo, the offending base of
  * an error message) read them back from the device.  WGA_FASTA_READER=host keeps the host line stripper (A/B, tests). */
@@ -574,6 +574,15 @@ struct DevFasta {
         if (!st.empty()) d.download(st.data(), (const uint32_t*)d_st, st.size());
         for (uint32_t v : st)
           if (v) fail("IO error:corrupt BGZF block in `" + path + "`");
+        /* a well-formed stream of ISIZE bytes may still hold other bytes than were written: every member's CRC-32
+         * (wga_bgzf_crc32, into the status array) against its trailer, the four bytes behind the deflate data */
+        d.check(wga_bgzf_crc32(d.ctx, d_text, (uint32_t)members.size(), d_mem, d_st));
+        if (!st.empty()) d.download(st.data(), (const uint32_t*)d_st, st.size());
+        for (size_t k = 0; k < members.size(); k++) {
+          const unsigned char* tr = (const unsigned char*)img.data() + members[k].in_off + members[k].in_len;
+          const uint32_t want = (uint32_t)tr[0] | (uint32_t)tr[1] << 8 | (uint32_t)tr[2] << 16 | (uint32_t)tr[3] << 24;
+          if (st[k] != want) fail("IO error:corrupt BGZF block in `" + path + "`");
+        }
         d.release(d_st);
         d.release((void*)d_mem);
         d.release((void*)d_img);
