@@ -459,6 +459,49 @@ typedef struct {
 int wga_maf_split(wga_ctx*, const uint8_t* d_text, uint64_t n_bytes, uint64_t* n_lines, wga_maf_line* d_lines,
                   uint64_t cap_lines);
 
+/* ---- K23: chain line splitter (replaces ChainRecords::next and the nom parsers chain_parser /
+ *      parse_header / the data-line fold of chain.rs:58-73,206-383 for plain files) -------------------------------------
+ * d_text = the chain file as read (n_bytes < 0xFFFFFFF0, 16 bytes of slack behind it).  Chain assembly happens on the device:
+ * which lines are headers, a header's rank (= its chain index), the compaction of the data lines and what may follow what.
+ *   d_heads[n_chains]       per chain: the eight header integers, the two strands, the two names as spans of d_text
+ *   d_lines[3 * n_lines]    all data lines back to back: size, 2nd column, 3rd column (zeros for missing columns) — the
+ *                           array wga_chain_lines_ops / wga_chain_lines_cigar_text take
+ *   d_line_off[n_chains+1]  each chain's first data line
+ * The file is taken (*status = WGA_CHAIN_OK) when all of this holds; otherwise *status = WGA_CHAIN_FALLBACK, *first_bad_line =
+ * the index of the first line that breaks a rule (WGA_NONE when none does), and the caller reads the file with its nom-semantics
+ * parser, which yields the same records or the reference's error text:
+ *   - no CR and no byte >= 0x80 anywhere; a non-empty file ends in '\n' (nom drops an unterminated last data line)
+ *   - every line is a header, a data line or empty; a line of white space only is not taken ("`size` Missing")
+ *   - a header starts at column 0 with "chain" and a white-space byte ("chain1 t .." is a header for nom: left to the host) and
+ *     has at least 12 more white-space separated tokens (surplus ones are ignored, chain.rs:206-322): the score is 1 to 15
+ *     decimal digits (exact in an f64; any other float syntax is left to the host), the strands are "+" or "-", the eight
+ *     integers parse like u64::from_str (optional '+', no overflow)
+ *   - a data line has one to three tokens "+?digits" without overflow (a fourth, which nom ignores, is left to the host)
+ *   - the first line is a header; a header is followed by a data line (header-header, header-blank and header-EOF are nom's
+ *     Many1 error); a data line follows a header or a data line (nom skips one behind a blank line up to the next 'c'); a
+ *     header may follow a data line directly; any number of blank lines may follow a chain's last data line
+ *   - an empty file is taken: no chain
+ * Two calls: with d_heads, d_lines and d_line_off all NULL the counts, the status and the first bad line are returned (host
+ * values; the call synchronises); then the arrays (cap_chains >= *n_chains heads, cap_lines >= *n_data_lines triples) are
+ * filled and the same host values returned.  With WGA_CHAIN_FALLBACK the arrays' contents mean nothing (the writes stay inside
+ * the counted extents).  Workspace (context scratch, grow-only): 8 bytes per white-space byte and 8 per newline of the text, 16
+ * bytes per byte of text at the most, plus 8 bytes per 256 lines. */
+#define WGA_CHAIN_OK 0
+#define WGA_CHAIN_FALLBACK 1
+typedef struct {
+  uint64_t num[8]; /* score, target_size, target_start, target_end, query_size, query_start, query_end, chain_id (chain.rs:76-91) */
+  uint64_t tname_off, qname_off;
+  uint32_t tname_len, qname_len;
+  uint8_t tstrand_neg, qstrand_neg, pad[6];
+} wga_chain_head;
+int wga_chain_split(wga_ctx*, const uint8_t* d_text, uint64_t n_bytes, uint64_t* n_chains, uint64_t* n_data_lines,
+                    uint32_t* status, uint64_t* first_bad_line, wga_chain_head* d_heads, uint64_t cap_chains,
+                    uint64_t* d_lines, uint64_t cap_lines, uint64_t* d_line_off);
+/* A run of chains [first, first + n) as a batch of its own for wga_chain_lines_ops / wga_chain_lines_cigar_text, which want
+ * offsets that start at 0: d_out[i] = d_line_off[i] - d_line_off[0] for i = 0 .. n (pass d_line_off + first, and d_lines +
+ * 3 * d_line_off[first] as the batch's lines).  d_out is another array than d_line_off. */
+int wga_chain_line_off_rebase(wga_ctx*, uint32_t n, const uint64_t* d_line_off, uint64_t* d_out);
+
 /* ---- stat totals: d_totals[11] = the column sums of d_counts[n] (wga_cigar_counts order).  What
  *      Statistic::merge adds up for one (ref, query) pair (stat.rs:181-223); with records sharded over
  *      GPUs these 88 bytes are the only thing `stat` has to all-reduce.  d_totals is overwritten. */

@@ -68,6 +68,9 @@ PROTOTYPES = {
     "wga_cigar_dotplot": (C.c_int, [vp, C.POINTER(CigarBatch), C.c_uint64, vp, vp, vp, vp, vp]),
     "wga_paf_split": (C.c_int, [vp, vp, C.c_uint64, C.POINTER(C.c_uint64), vp, C.c_uint64]),
     "wga_maf_split": (C.c_int, [vp, vp, C.c_uint64, C.POINTER(C.c_uint64), vp, C.c_uint64]),
+    "wga_chain_split": (C.c_int, [vp, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
+                                  C.POINTER(C.c_uint64), vp, C.c_uint64, vp, C.c_uint64, vp]),
+    "wga_chain_line_off_rebase": (C.c_int, [vp, C.c_uint32, vp, vp]),
     "wga_cigar_tokenise_spans": (C.c_int, [vp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp]),
     "wga_counts_total": (C.c_int, [vp, C.c_uint32, vp, vp]),
     "wga_host_alloc": (C.c_int, [vp, C.c_size_t, C.POINTER(C.c_void_p)]),

@@ -1,22 +1,24 @@
-/* capi_text.inc — K8 / K9 / K13 / K14 / K15 / K17 / K18: text in, text out (tokenisers, line splitters, FASTA pool, BGZF, BED lines).
+/* capi_text.inc — K8 / K9 / K13 / K14 / K15 / K17 / K18 / K23: text in, text out (tokenisers, line splitters, FASTA pool, BGZF, BED lines).
  * A part of wga_capi.cpp (included there: one translation unit). */
-/* K13 / K14 driver: delimiter lists (count, scan, fill) in the context scratch, then one thread per line.
- * MODE 0 = PAF (wga_paf_line), 1 = MAF (wga_maf_line). */
+/* K13 / K14 / K23: the two delimiter lists of a text (count, scan, fill over 4 KB blocks) in the context scratch, with `tail`
+ * bytes of the caller's own behind them (tail_per_256_lines for every 256 lines or part of them, plus tail_fixed).
+ * MODE 0 = PAF (tab, newline, '"', CR), 1 = MAF and chain (newline, white space, bytes >= 0x80). */
+struct DelimLists {
+  u64 n_delims = 0, n_newlines = 0, n_lines = 0;
+  u64* delims = nullptr;
+  u64* nl_idx = nullptr;
+  void* tail = nullptr;
+};
 template <int MODE>
-static int split_lines(wga_ctx* c, const uint8_t* d_text, uint64_t n_bytes, uint64_t* n_lines, void* d_lines,
-                       uint64_t cap_lines) {
-  int rc = ctx_bind(c);
-  if (rc) return rc;
-  if (!n_lines) return fail(WGA_E_INVALID_ARG, "n_lines null", nullptr);
-  *n_lines = 0;
-  if (n_bytes == 0) return WGA_OK;
-  if (!d_text) return fail(WGA_E_INVALID_ARG, "d_text null", nullptr);
-  if (n_bytes >= 0xFFFFFFFFull) return fail(WGA_E_INVALID_ARG, "text of 4 GiB or more: split it at line ends", nullptr);
+static int delim_lists(wga_ctx* c, const uint8_t* d_text, uint64_t n_bytes, bool fill, size_t tail_per_256_lines,
+                       size_t tail_fixed, DelimLists* L) {
+  int rc;
   const u32 nb = (u32)((n_bytes + 4095u) / 4096u);
   const size_t head = ((size_t)nb + 1 + (size_t)nb / 1024 + 4) * sizeof(u64);
   u64 tot = 0;
   void* ws = nullptr;
   if ((rc = ctx_scratch(c, head, &ws))) return rc;
+  size_t lists = 0;
   for (int attempt = 0; attempt < 2; attempt++) {
     u64* blk = (u64*)c->scratch.mem;
     WGA_LAUNCH((k_paf_delims<false, MODE>), nb, WGA_BLOCK, c->stream, d_text, (u64)n_bytes, blk, (const u64*)nullptr,
@@ -29,28 +31,47 @@ static int split_lines(wga_ctx* c, const uint8_t* d_text, uint64_t n_bytes, uint
     RT_CHECK(rt_d2h(&tot, blk + nb, sizeof(u64), c->stream));
     /* the two lists follow the block offsets; their sizes are only known now: growing the arena
      * drops its contents, so the count pass is repeated once */
-    const size_t want = head + ((size_t)(tot & 0xFFFFFFFFull) + (size_t)(tot >> 32) + 2) * sizeof(u64);
+    lists = ((size_t)(tot & 0xFFFFFFFFull) + (size_t)(tot >> 32) + 2) * sizeof(u64);
+    const size_t want = head + lists + ((size_t)(tot >> 32) / 256 + 2) * tail_per_256_lines + tail_fixed;
     if (c->scratch.cap >= want) break;
     if ((rc = ctx_scratch(c, want, &ws))) return rc;
   }
-  const u64 n_delims = tot & 0xFFFFFFFFull, n_newlines = tot >> 32;
+  L->n_delims = tot & 0xFFFFFFFFull, L->n_newlines = tot >> 32;
   u8 last = 0;
   RT_CHECK(rt_d2h(&last, d_text + n_bytes - 1, 1, c->stream));
-  *n_lines = n_newlines + (last != (u8)0x0A ? 1 : 0);
+  L->n_lines = L->n_newlines + (last != (u8)0x0A ? 1 : 0);
+  L->delims = (u64*)((char*)c->scratch.mem + head);
+  L->nl_idx = L->delims + L->n_delims + 1;
+  L->tail = (char*)c->scratch.mem + head + lists;
+  if (!fill) return WGA_OK;
+  WGA_LAUNCH((k_paf_delims<true, MODE>), nb, WGA_BLOCK, c->stream, d_text, (u64)n_bytes, (u64*)nullptr,
+             (const u64*)c->scratch.mem, L->delims, L->nl_idx);
+  LAUNCH_CHECK();
+  return WGA_OK;
+}
+
+/* K13 / K14 driver: the lists, then one thread per line.  MODE 0 = PAF (wga_paf_line), 1 = MAF (wga_maf_line). */
+template <int MODE>
+static int split_lines(wga_ctx* c, const uint8_t* d_text, uint64_t n_bytes, uint64_t* n_lines, void* d_lines,
+                       uint64_t cap_lines) {
+  int rc = ctx_bind(c);
+  if (rc) return rc;
+  if (!n_lines) return fail(WGA_E_INVALID_ARG, "n_lines null", nullptr);
+  *n_lines = 0;
+  if (n_bytes == 0) return WGA_OK;
+  if (!d_text) return fail(WGA_E_INVALID_ARG, "d_text null", nullptr);
+  if (n_bytes >= 0xFFFFFFFFull) return fail(WGA_E_INVALID_ARG, "text of 4 GiB or more: split it at line ends", nullptr);
+  DelimLists L;
+  if ((rc = delim_lists<MODE>(c, d_text, n_bytes, d_lines != nullptr, 0, 0, &L))) return rc;
+  *n_lines = L.n_lines;
   if (!d_lines) return WGA_OK;
   if (cap_lines < *n_lines) return fail(WGA_E_TOO_SMALL, "d_lines too small", nullptr);
-  u64* blk_off = (u64*)c->scratch.mem;
-  u64* delims = (u64*)((char*)c->scratch.mem + head);
-  u64* nl_idx = delims + n_delims + 1;
-  WGA_LAUNCH((k_paf_delims<true, MODE>), nb, WGA_BLOCK, c->stream, d_text, (u64)n_bytes, (u64*)nullptr,
-             (const u64*)blk_off, delims, nl_idx);
-  LAUNCH_CHECK();
   if (MODE == 0) {
     WGA_LAUNCH(k_paf_fields, (u32)((*n_lines + 255u) / 256u), WGA_BLOCK, c->stream, d_text, (u64)n_bytes,
-               (u64)*n_lines, n_newlines, n_delims, (const u64*)delims, (const u64*)nl_idx, (wga_paf_line_dev*)d_lines);
+               (u64)*n_lines, L.n_newlines, L.n_delims, (const u64*)L.delims, (const u64*)L.nl_idx, (wga_paf_line_dev*)d_lines);
   } else {
     WGA_LAUNCH(k_maf_lines, (u32)((*n_lines + 255u) / 256u), WGA_BLOCK, c->stream, d_text, (u64)n_bytes,
-               (u64)*n_lines, n_newlines, n_delims, (const u64*)delims, (const u64*)nl_idx, (wga_maf_line_dev*)d_lines);
+               (u64)*n_lines, L.n_newlines, L.n_delims, (const u64*)L.delims, (const u64*)L.nl_idx, (wga_maf_line_dev*)d_lines);
   }
   LAUNCH_CHECK();
   return WGA_OK;
@@ -97,6 +118,72 @@ int wga_maf_split(wga_ctx* c, const uint8_t* d_text, uint64_t n_bytes, uint64_t*
                   uint64_t cap_lines) {
   static_assert(sizeof(wga_maf_line) == sizeof(wga_maf_line_dev), "wga_maf_line layout");
   return split_lines<1>(c, d_text, n_bytes, n_lines, (void*)d_lines, cap_lines);
+}
+
+int wga_chain_split(wga_ctx* c, const uint8_t* d_text, uint64_t n_bytes, uint64_t* n_chains, uint64_t* n_data_lines,
+                    uint32_t* status, uint64_t* first_bad_line, wga_chain_head* d_heads, uint64_t cap_chains, uint64_t* d_lines,
+                    uint64_t cap_lines, uint64_t* d_line_off) {
+  static_assert(sizeof(wga_chain_head) == sizeof(wga_chain_head_dev) && sizeof(wga_chain_head) == 96, "wga_chain_head layout");
+  int rc = ctx_bind(c);
+  if (rc) return rc;
+  if (!n_chains || !n_data_lines || !status || !first_bad_line) return fail(WGA_E_INVALID_ARG, "null count", nullptr);
+  *n_chains = *n_data_lines = 0;
+  *status = WGA_CHAIN_OK;
+  *first_bad_line = WGA_NONE;
+  const bool fill = d_heads != nullptr || d_lines != nullptr || d_line_off != nullptr;
+  if (fill && !d_line_off) return fail(WGA_E_INVALID_ARG, "d_line_off null", nullptr);
+  if (n_bytes == 0) { /* an empty file: no chain */
+    static const u64 zero = 0;
+    if (fill) RT_CHECK(rt_h2d(d_line_off, &zero, sizeof zero, c->stream));
+    return WGA_OK;
+  }
+  if (!d_text) return fail(WGA_E_INVALID_ARG, "d_text null", nullptr);
+  if (n_bytes >= 0xFFFFFFF0ull) return fail(WGA_E_INVALID_ARG, "text of 4 GiB or more: the host reader takes it", nullptr);
+  /* behind the lists: the line blocks' counts (then offsets, + total) | scan partials | the first bad line */
+  DelimLists L;
+  if ((rc = delim_lists<1>(c, d_text, n_bytes, true, 16, 128, &L))) return rc;
+  const u32 nlb = (u32)((L.n_lines + 255u) / 256u);
+  u64* blk = (u64*)L.tail;
+  u64* partial = blk + nlb + 1;
+  u64* first_bad = partial + (size_t)nlb / 1024 + 4;
+  WGA_LAUNCH(k_chain_kinds, nlb, WGA_BLOCK, c->stream, d_text, (u64)n_bytes, L.n_lines, L.n_newlines, (const u64*)L.delims,
+             (const u64*)L.nl_idx, blk);
+  LAUNCH_CHECK();
+  ScanPlain f;
+  f.in = blk;
+  if ((rc = run_scan_ws(c, f, nlb, blk, partial))) return rc;
+  u64 tot = 0;
+  RT_CHECK(rt_d2h(&tot, blk + nlb, sizeof tot, c->stream));
+  const u64 nc = tot & 0xFFFFFFFFull, nd = tot >> 32;
+  *n_chains = nc;
+  *n_data_lines = nd;
+  if (fill) {
+    if ((nc && !d_heads) || (nd && !d_lines)) return fail(WGA_E_INVALID_ARG, "null array", nullptr);
+    if (cap_chains < nc) return fail(WGA_E_TOO_SMALL, "d_heads too small", nullptr);
+    if (cap_lines < nd) return fail(WGA_E_TOO_SMALL, "d_lines too small", nullptr);
+    RT_CHECK(rt_h2d(d_line_off + nc, &nd, sizeof nd, c->stream));
+  }
+  RT_CHECK(rt_memset(first_bad, 0xFF, sizeof(u64), c->stream));
+  WGA_LAUNCH(k_chain_parse, nlb, WGA_BLOCK, c->stream, d_text, (u64)n_bytes, L.n_lines, L.n_newlines, L.n_delims,
+             (const u64*)L.delims, (const u64*)L.nl_idx, (const u64*)blk, first_bad,
+             fill ? (wga_chain_head_dev*)d_heads : (wga_chain_head_dev*)nullptr, fill ? (u64*)d_lines : (u64*)nullptr,
+             fill ? (u64*)d_line_off : (u64*)nullptr);
+  LAUNCH_CHECK();
+  u64 bad = WGA_NONE;
+  RT_CHECK(rt_d2h(&bad, first_bad, sizeof bad, c->stream));
+  *first_bad_line = bad;
+  *status = bad == WGA_NONE ? WGA_CHAIN_OK : WGA_CHAIN_FALLBACK;
+  return WGA_OK;
+}
+
+int wga_chain_line_off_rebase(wga_ctx* c, uint32_t n, const uint64_t* d_line_off, uint64_t* d_out) {
+  int rc = ctx_bind(c);
+  if (rc) return rc;
+  if (!d_line_off || !d_out) return fail(WGA_E_INVALID_ARG, "null array", nullptr);
+  if (d_line_off == d_out) return fail(WGA_E_INVALID_ARG, "d_out must not be d_line_off", nullptr);
+  WGA_LAUNCH(k_chain_rebase, (u32)(((u64)n + 1u + 255u) / 256u), WGA_BLOCK, c->stream, n, (const u64*)d_line_off, (u64*)d_out);
+  LAUNCH_CHECK();
+  return WGA_OK;
 }
 
 int wga_fasta_pool(wga_ctx* c, const uint8_t* d_text, uint64_t n_bytes, uint64_t* n_contigs, uint64_t* pool_bytes,

@@ -37,6 +37,7 @@
 #include "wga_k20_maf_chunk.h" /* K20: chunk on MAF */
 #include "wga_k21_maf_slice.h" /* K21: maf-ext's slices */
 #include "wga_k22_maf_rewrite.h" /* K22: filter and rename on MAF */
+#include "wga_k23_chain_split.h" /* K23: the chain line splitter */
 
 /* A grow-only device buffer of a context.  reserve() leaves it with room for `need` bytes: one that is too small is freed
  * behind the work of the context's stream and allocated anew with `grow` (>= need) bytes — every site has its own growth rule —,

@@ -24,8 +24,10 @@ __device__ __forceinline__ u32 csr_find_rec(const u64* __restrict__ off, u32 n, 
   return lo;
 }
 
-__device__ __forceinline__ u32 split_pieces(u64 len) { /* pieces of at most WGA_OP_MAX_LEN, none for 0 */
-  return (u32)((len + (u64)WGA_OP_MAX_LEN - 1ull) / (u64)WGA_OP_MAX_LEN);
+/* pieces of at most WGA_OP_MAX_LEN, none for 0: exactly as many as put_split writes, for every u64 (a chain data line may hold
+ * 2^64 - 1: rounding up by adding first would wrap, and 2^36 pieces do not fit 32 bits) */
+__device__ __forceinline__ u64 split_pieces(u64 len) {
+  return len / (u64)WGA_OP_MAX_LEN + (len % (u64)WGA_OP_MAX_LEN ? 1ull : 0ull);
 }
 __device__ __forceinline__ u32* put_split(u32* p, u64 len, u32 code, u32 cont) {
   bool first = true;
@@ -94,7 +96,7 @@ struct ChainLineOps {
   typedef u32 out_t;
   ChainLineSrc s;
   __device__ u64 size(u64 x, u32) const {
-    return (u64)split_pieces(s.size_(x)) + split_pieces(s.ins_(x)) + split_pieces(s.del_(x));
+    return split_pieces(s.size_(x)) + split_pieces(s.ins_(x)) + split_pieces(s.del_(x));
   }
   __device__ void write(u64 x, u32, u32* p) const {
     p = put_split(p, s.size_(x), (u32)WGA_OP_M, (u32)WGA_OP_M);

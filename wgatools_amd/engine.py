@@ -25,6 +25,10 @@ PAF_LINE_DTYPE = np.dtype([("num", np.uint64, 9), ("qname_off", np.uint64), ("tn
                            ("cg_beg", np.uint64), ("cg_end", np.uint64), ("qname_len", np.uint32),
                            ("tname_len", np.uint32), ("n_fields", np.uint32), ("strand_neg", np.uint8),
                            ("status", np.uint8), ("pad", np.uint8, 2)])
+CHAIN_HEAD_DTYPE = np.dtype([("num", np.uint64, 8), ("tname_off", np.uint64), ("qname_off", np.uint64),
+                             ("tname_len", np.uint32), ("qname_len", np.uint32), ("tstrand_neg", np.uint8),
+                             ("qstrand_neg", np.uint8), ("pad", np.uint8, 6)])
+CHAIN_OK, CHAIN_FALLBACK = 0, 1
 
 OP_CODES = {"M": 0, "I": 1, "D": 2, "N": 3, "S": 4, "H": 5, "P": 6, "=": 7, "X": 8}
 OP_I_CONT, OP_D_CONT, OP_OTHER = 9, 10, 11
@@ -393,6 +397,23 @@ class Engine:
         cap = 0 if lines is None else (lines.numel() if hasattr(lines, "numel") else lines.size)
         self._check(self.lib.wga_maf_split(self.ctx, _p(text), int(n_bytes), C.byref(nl), _p(lines), int(cap)))
         return int(nl.value)
+
+    def chain_split(self, text, n_bytes, heads=None, lines=None, line_off=None):
+        """K23: (n_chains, n_data_lines, status, first bad line or None); the count call when the three arrays are None,
+        else they are filled (heads: CHAIN_HEAD_DTYPE, lines: n x 3 u64, line_off: n_chains + 1 u64)"""
+        nc, nd, st, bad = C.c_uint64(0), C.c_uint64(0), C.c_uint32(0), C.c_uint64(0)
+
+        def cap(a, per):
+            return 0 if a is None else (a.numel() if hasattr(a, "numel") else a.size) // per
+        self._check(self.lib.wga_chain_split(self.ctx, _p(text), int(n_bytes), C.byref(nc), C.byref(nd), C.byref(st),
+                                             C.byref(bad), _p(heads), cap(heads, 1), _p(lines), cap(lines, 3), _p(line_off)))
+        return int(nc.value), int(nd.value), int(st.value), None if bad.value == int(NONE) else int(bad.value)
+
+    def chain_line_off_rebase(self, n, line_off, out=None):
+        """K23's offsets of a run of n chains (line_off: its first entry, a device pointer) as a batch of its own: out[i] = line_off[i] - line_off[0]"""
+        out = out if out is not None else self.empty(n + 1, np.uint64)
+        self._check(self.lib.wga_chain_line_off_rebase(self.ctx, int(n), _p(line_off), _p(out)))
+        return out
 
     def cigar_tokenise_spans(self, n, text, beg, end, op_cnt=None, err=None, ops=None, op_off=None):
         """device tokeniser on spans text[beg[i], end[i]) (e.g. the cg:Z: texts inside a PAF file)"""

@@ -157,26 +157,123 @@ int cmd_paf2chain(const std::string* input, Output& out) {
   return leave(0);
 }
 
-/* ---- the chain readers' device batch: data lines -> packed ops (wga_chain_lines_ops) ----------------- */
+/* ---- a chain input: the records (chain.rs:49-55,76-91) and where their data lines are ---------------------------
+ * A plain file is split on the device (K23, wga_chain_split): the heads come back, the data lines stay in HBM as the n x 3 array
+ * the converters' kernels take, with each chain's first line in d_line_off (the host keeps a copy of those n + 1 offsets: its
+ * batches are cut by them).  A file the splitter does not take (CR, non-ASCII bytes, comments, another float syntax for the
+ * score, ... : include/wga_hip.h), one of 0xFFFFFFF0 bytes or more, or any file under WGA_CHAIN_READER=host goes through
+ * parse_chain: the same records, or the records in front of the reference's error and its text. */
+struct ChainInput {
+  std::vector<ChainRecord> recs; /* without their `lines`: those are in `lines` or on the device */
+  std::string error;             /* the host reader's, "" when the whole file was read */
+  bool on_device = false;
+  uint64_t* d_lines = nullptr;    /* on_device: 3 u64 per data line, all chains back to back (+ one line of slack), device 0 */
+  uint64_t* d_line_off = nullptr; /* on_device: n + 1 */
+  std::vector<uint64_t> line_off; /* n + 1 */
+  std::vector<uint64_t> lines;    /* host reader, or fetch_lines(): the same array on the host (+ one line of slack) */
+  bool have_lines = false;
+  uint64_t n_lines(size_t i) const { return line_off[i + 1] - line_off[i]; }
+  /* the device's data lines on the host as well, in one download: for filter's text and for the other devices of --gpus N */
+  void fetch_lines(Dev& d) {
+    if (have_lines) return;
+    lines.assign((size_t)(line_off.back() + 1) * 3, 0);
+    if (line_off.back()) d.download(lines.data(), d_lines, (size_t)line_off.back() * 3);
+    have_lines = true;
+  }
+};
+ChainInput load_chain(Dev& d, const std::string* input) {
+  ChainInput in;
+  std::string text = read_all(input);
+  const char* force = getenv("WGA_CHAIN_READER"); /* "host": always the nom-semantics reader (measurements) */
+  if (!text.empty() && text.size() < 0xFFFFFFF0ull && !(force && strcmp(force, "host") == 0)) {
+    g_timer.mark("file read");
+    d.init();
+    const size_t n_bytes = text.size();
+    text.append(16, '\0'); /* slack behind the text for whole-vector loads */
+    uint8_t* d_text = d.upload((const uint8_t*)text.data(), text.size());
+    text.resize(n_bytes);
+    g_timer.mark("upload");
+    uint64_t nc = 0, nd = 0, bad = 0;
+    uint32_t status = WGA_CHAIN_FALLBACK;
+    d.check(wga_chain_split(d.ctx, d_text, n_bytes, &nc, &nd, &status, &bad, nullptr, 0, nullptr, 0, nullptr));
+    if (status == WGA_CHAIN_OK) {
+      auto* d_heads = (wga_chain_head*)d.alloc((size_t)(nc + 1) * sizeof(wga_chain_head));
+      in.d_lines = (uint64_t*)d.alloc((size_t)(nd + 1) * 3 * sizeof(uint64_t));
+      in.d_line_off = (uint64_t*)d.alloc((size_t)(nc + 1) * sizeof(uint64_t));
+      d.check(wga_chain_split(d.ctx, d_text, n_bytes, &nc, &nd, &status, &bad, d_heads, nc, in.d_lines, nd, in.d_line_off));
+      std::vector<wga_chain_head> heads((size_t)nc);
+      in.line_off.resize((size_t)nc + 1);
+      if (nc) d.download(heads.data(), d_heads, (size_t)nc);
+      d.download(in.line_off.data(), in.d_line_off, (size_t)nc + 1);
+      d.release(d_heads);
+      d.release(d_text);
+      in.recs.reserve((size_t)nc);
+      for (const wga_chain_head& h : heads) {
+        ChainRecord r;
+        r.score = (double)h.num[0]; /* at most 15 digits: exact */
+        r.target_name.assign(text, (size_t)h.tname_off, h.tname_len);
+        r.target_size = h.num[1];
+        r.target_start = h.num[2];
+        r.target_end = h.num[3];
+        r.query_name.assign(text, (size_t)h.qname_off, h.qname_len);
+        r.query_size = h.num[4];
+        r.query_start = h.num[5];
+        r.query_end = h.num[6];
+        r.chain_id = h.num[7];
+        r.target_neg = h.tstrand_neg != 0;
+        r.query_neg = h.qstrand_neg != 0;
+        in.recs.push_back(std::move(r));
+      }
+      in.on_device = true;
+      g_timer.mark("device split + host records");
+      return in;
+    }
+    d.release(d_text);
+  }
+  in.recs = parse_chain(text, &in.error);
+  in.line_off.assign(1, 0);
+  size_t total = 0;
+  for (const ChainRecord& r : in.recs) total += r.lines.size();
+  in.lines.reserve(total + 3);
+  for (ChainRecord& r : in.recs) {
+    in.lines.insert(in.lines.end(), r.lines.begin(), r.lines.end());
+    in.line_off.push_back(in.lines.size() / 3);
+    std::vector<uint64_t>().swap(r.lines);
+  }
+  in.lines.resize(in.lines.size() + 3);
+  in.have_lines = true;
+  return in;
+}
+
+/* ---- the chain readers' device batch: data lines -> packed ops (wga_chain_lines_ops) -----------------
+ * chains [first, first + n) of the input on device d.  in_place: d is the device the splitter ran on, the lines are used where
+ * they are (a batch that does not start at chain 0 gets its offsets rebased on the device); otherwise the range's lines are
+ * uploaded from the host's array. */
 struct ChainBatch {
   wga_cigar_batch cb;
   uint64_t* d_lines = nullptr;
   uint64_t* d_line_off = nullptr;
   uint64_t n_lines = 0;
 };
-ChainBatch chain_device_batch(Dev& d, const ChainRecord* recs, uint32_t n) {
+ChainBatch chain_device_batch(Dev& d, const ChainInput& in, size_t first, uint32_t n, bool in_place) {
   ChainBatch b;
-  std::vector<uint64_t> lines, line_off{0};
-  std::vector<uint8_t> strand;
-  for (uint32_t k = 0; k < n; k++) {
-    lines.insert(lines.end(), recs[k].lines.begin(), recs[k].lines.end());
-    line_off.push_back(lines.size() / 3);
-    strand.push_back(recs[k].query_neg ? 1 : 0);
+  const uint64_t l0 = in.line_off[first];
+  b.n_lines = in.line_off[first + n] - l0;
+  std::vector<uint8_t> strand(n);
+  for (uint32_t k = 0; k < n; k++) strand[k] = in.recs[first + k].query_neg ? 1 : 0;
+  if (in_place && in.on_device) {
+    b.d_lines = in.d_lines + 3 * l0;
+    b.d_line_off = in.d_line_off;
+    if (first) {
+      b.d_line_off = (uint64_t*)d.alloc(((size_t)n + 1) * 8);
+      d.check(wga_chain_line_off_rebase(d.ctx, n, in.d_line_off + first, b.d_line_off));
+    }
+  } else {
+    std::vector<uint64_t> line_off((size_t)n + 1);
+    for (uint32_t k = 0; k <= n; k++) line_off[k] = in.line_off[first + k] - l0;
+    b.d_lines = d.upload(in.lines.data() + 3 * l0, (size_t)(b.n_lines + 1) * 3); /* what follows the range is its slack */
+    b.d_line_off = d.upload(line_off);
   }
-  b.n_lines = lines.size() / 3;
-  lines.resize(lines.size() + 3);
-  b.d_lines = d.upload(lines);
-  b.d_line_off = d.upload(line_off);
   auto* d_cnt = (uint64_t*)d.alloc((size_t)n * 8);
   d.check(wga_chain_lines_ops(d.ctx, n, b.n_lines, b.d_lines, b.d_line_off, d_cnt, nullptr, nullptr));
   auto* d_ooff = (uint64_t*)d.alloc(((size_t)n + 1) * 8);
@@ -199,8 +296,9 @@ ChainBatch chain_device_batch(Dev& d, const ChainRecord* recs, uint32_t n) {
 /* the converter's record loop over chains [lo, hi), in resident batches: slices fetched (:309-316: target first, then query, both on
  * the forward strand), data lines -> ops, rows expanded, text handed to the sink (record k of the run is record k of the file).
  * Returns the index of the first failing record, or hi; `err` = the reference's message for it. */
-static size_t c2m_run(Dev& d, DevFasta& tf, DevFasta& qf, const std::vector<ChainRecord>& recs, size_t lo, size_t hi, BatchSink sink,
+static size_t c2m_run(Dev& d, DevFasta& tf, DevFasta& qf, const ChainInput& in, bool in_place, size_t lo, size_t hi, BatchSink sink,
                       std::string& err) {
+  const std::vector<ChainRecord>& recs = in.recs;
   const uint64_t kMaxBytes = 6ull << 30, kMaxLines = 32ull << 20;
   const size_t keep = d.owned.size(); /* the pools stay */
   size_t i0 = lo;
@@ -224,11 +322,11 @@ static size_t c2m_run(Dev& d, DevFasta& tf, DevFasta& qf, const std::vector<Chai
               r.target_size, r.query_name, r.query_neg ? r.query_size - r.query_end : r.query_start, /* :299-302 */
               r.query_end - r.query_start, r.query_neg, r.query_size);
       est += tl + ql + (tl + ql) / 4;
-      est_lines += r.lines.size() / 3;
+      est_lines += in.n_lines(i);
     }
     const uint32_t n = (uint32_t)(i - i0);
     if (n) {
-      ChainBatch b = chain_device_batch(d, &recs[i0], n);
+      ChainBatch b = chain_device_batch(d, in, i0, n, in_place);
       wga_rec_diag g;
       sink.which = nullptr;
       sink.first = i0;
@@ -258,10 +356,16 @@ static size_t c2m_run(Dev& d, DevFasta& tf, DevFasta& qf, const std::vector<Chai
 /* `wgatools --gpus N chain2maf`: the chains in N contiguous ranges, both pools on every device; sizes first (K1 + layout), a
  * prefix gives every record its file offset, rows second, every device pwrite()s its records; the file ends in front of the
  * first failing record. */
-static int cmd_chain2maf_multi(std::vector<ChainRecord>& recs, std::string pending_error, const std::string& t_fa,
-                               const std::string& q_fa, Output& out, int ngpu) {
+static int cmd_chain2maf_multi(Dev& d, ChainInput& in, const std::string& t_fa, const std::string& q_fa, Output& out, int ngpu) {
+  const std::vector<ChainRecord>& recs = in.recs;
+  std::string pending_error = in.error;
   std::vector<std::unique_ptr<Dev>> devs;
   for (int g = 0; g < ngpu; g++) devs.emplace_back(new Dev(g));
+  if (in.on_device) { /* device 0 split the file: its worker borrows the reader's context, the others get their ranges' lines */
+    devs[0]->ctx = d.ctx;
+    devs[0]->own_ctx = false;
+    in.fetch_lines(d);
+  }
   std::vector<DevFasta> tf(ngpu), qf(ngpu);
   on_devices(ngpu, [&](int g) {
     devs[g]->init();
@@ -286,7 +390,7 @@ static int cmd_chain2maf_multi(std::vector<ChainRecord>& recs, std::string pendi
       sink.offsets = &offsets;
       sink.fd = fd;
       std::string err;
-      const size_t k = c2m_run(*devs[g], tf[g], qf[g], recs, lo, hi, sink, err);
+      const size_t k = c2m_run(*devs[g], tf[g], qf[g], in, g == 0, lo, hi, sink, err);
       if (k < hi && k < bad_at[g]) {
         bad_at[g] = k;
         bad_msg[g] = err;
@@ -311,15 +415,15 @@ static int cmd_chain2maf_multi(std::vector<ChainRecord>& recs, std::string pendi
 }
 
 int cmd_chain2maf(const std::string* input, const std::string& t_fa, const std::string& q_fa, Output& out) {
-  std::string pending_error;
-  std::vector<ChainRecord> recs = parse_chain(read_all(input), &pending_error);
+  Dev d;
+  ChainInput in = load_chain(d, input);
+  const std::vector<ChainRecord>& recs = in.recs;
+  std::string pending_error = in.error;
   {
     uint64_t pos = 0;
-    if (g_gpus > 1 && recs.size() > 1 && out.plain_fd(&pos) >= 0)
-      return cmd_chain2maf_multi(recs, pending_error, t_fa, q_fa, out, g_gpus);
+    if (g_gpus > 1 && recs.size() > 1 && out.plain_fd(&pos) >= 0) return cmd_chain2maf_multi(d, in, t_fa, q_fa, out, g_gpus);
   }
   DevFasta tf, qf;
-  Dev d;
   d.init();
   tf.load(d, t_fa);
   qf.load(d, q_fa);
@@ -327,7 +431,7 @@ int cmd_chain2maf(const std::string* input, const std::string& t_fa, const std::
   BatchSink sink;
   sink.out = &out;
   std::string err;
-  if (c2m_run(d, tf, qf, recs, 0, recs.size(), sink, err) < recs.size()) pending_error = err;
+  if (c2m_run(d, tf, qf, in, true, 0, recs.size(), sink, err) < recs.size()) pending_error = err;
   out.close();
   if (!pending_error.empty()) fail(pending_error);
   return leave(0);
@@ -336,23 +440,25 @@ int cmd_chain2maf(const std::string* input, const std::string& t_fa, const std::
 /* ---- chain2paf (converter.rs:391-416, chain.rs:430-452) ------------------------------------------------
  * GPU: data lines -> ops -> K1 (matches, block length) and the CIGAR text (wga_chain_lines_cigar_text).
  * All records are converted before the first is written (:402-410): an error leaves the output empty. */
-/* the PAF rows of chains recs[0 .. n_recs) on device d, in resident batches; a batch's text goes to `sink` while it is on the device */
-static void chain2paf_range(Dev& d, const ChainRecord* recs, size_t n_recs,
+/* the PAF rows of chains [lo, hi) of the input on device d, in resident batches; a batch's text goes to `sink` while it is on the device */
+static void chain2paf_range(Dev& d, const ChainInput& in, bool in_place, size_t lo, size_t hi,
                             const std::function<void(Dev&, const uint8_t*, size_t)>& sink) {
+  const std::vector<ChainRecord>& recs = in.recs;
   d.init();
   const size_t keep = d.owned.size();
-  const uint64_t kMaxLines = 32ull << 20;
-  size_t i0 = 0;
-  while (i0 < n_recs) {
+  uint64_t kMaxLines = 32ull << 20;
+  if (const char* e = getenv("WGA_CHAIN_BATCH_LINES")) kMaxLines = strtoull(e, nullptr, 10); /* the tests reach several batches with small files */
+  size_t i0 = lo;
+  while (i0 < hi) {
     size_t i = i0;
     uint64_t est = 0;
-    for (; i < n_recs; i++) {
+    for (; i < hi; i++) {
       if (i > i0 && est > kMaxLines) break;
-      est += recs[i].lines.size() / 3;
+      est += in.n_lines(i);
     }
     d.init();
     const uint32_t n = (uint32_t)(i - i0);
-    ChainBatch b = chain_device_batch(d, &recs[i0], n);
+    ChainBatch b = chain_device_batch(d, in, i0, n, in_place);
     auto* d_counts = (wga_cigar_counts*)d.alloc((size_t)n * sizeof(wga_cigar_counts));
     auto* d_diag = (wga_rec_diag*)d.alloc((size_t)n * sizeof(wga_rec_diag));
     d.check(wga_cigar_stat(d.ctx, &b.cb, d_counts, d_diag, nullptr));
@@ -408,27 +514,32 @@ static void chain2paf_range(Dev& d, const ChainRecord* recs, size_t n_recs,
 }
 
 int cmd_chain2paf(const std::string* input, Output& out) {
-  std::string perr;
-  std::vector<ChainRecord> recs = parse_chain(read_all(input), &perr);
-  if (!perr.empty()) {
-    out.close();
-    fail(perr);
-  }
   Dev d;
+  ChainInput in = load_chain(d, input);
+  const std::vector<ChainRecord>& recs = in.recs;
+  if (!in.error.empty()) {
+    out.close();
+    fail(in.error);
+  }
   if (g_gpus == 1 || recs.size() < 2) {
     if (!recs.empty())
-      chain2paf_range(d, recs.data(), recs.size(),
+      chain2paf_range(d, in, true, 0, recs.size(),
                       [&](Dev& dg, const uint8_t* d_out, size_t bytes) { stream_out(dg, out, d_out, bytes); });
   } else { /* --gpus N: the chains in contiguous ranges over the devices, the rows meet in input order */
     const int ng = g_gpus;
     const size_t n = recs.size();
     std::vector<std::unique_ptr<Dev>> devs;
     for (int g = 0; g < ng; g++) devs.emplace_back(new Dev(g));
+    if (in.on_device) { /* device 0 split the file: its worker borrows the reader's context, the others get their ranges' lines */
+      devs[0]->ctx = d.ctx;
+      devs[0]->own_ctx = false;
+      in.fetch_lines(d);
+    }
     std::vector<std::string> part(ng);
     on_devices(ng, [&](int g) {
       const size_t lo = n * (size_t)g / ng, hi = n * (size_t)(g + 1) / ng;
       if (lo == hi) return;
-      chain2paf_range(*devs[g], recs.data() + lo, hi - lo, [&](Dev& dd, const uint8_t* d_out, size_t bytes) {
+      chain2paf_range(*devs[g], in, g == 0, lo, hi, [&](Dev& dd, const uint8_t* d_out, size_t bytes) {
         const size_t at = part[g].size();
         part[g].resize(at + bytes);
         if (bytes) dd.download((uint8_t*)&part[g][at], d_out, bytes);

@@ -103,8 +103,9 @@ static int rewrite_maf(const std::string* input, const std::string& header, MafR
 }
 
 /* ---- filter (tools/filter.rs, utils.rs:540-576) --------------------------------------------------------------------------------
- * MAF: K22 with the thresholds (`-a` is ignored, as in the reference).  PAF and chain are host paths: the records are
- * re-serialised field by field (csv writer / the chain Display impls), which no kernel of this engine does. */
+ * MAF: K22 with the thresholds (`-a` is ignored, as in the reference).  PAF and chain are written on the host: the records are
+ * re-serialised field by field (csv writer / the chain Display impls), which no kernel of this engine does; a plain chain file
+ * is read on the device (ChainInput) and its data lines come back in one copy. */
 static const char* kFilterNoQuery = "panic: a block with a single s-line has no query row (maf.rs:430 index out of bounds)";
 
 int cmd_filter_maf(const std::string* input, uint64_t min_block, uint64_t min_query, Output& out) {
@@ -180,9 +181,13 @@ int cmd_filter_paf(const std::string* input, uint64_t min_block, uint64_t min_qu
 }
 
 int cmd_filter_chain(const std::string* input, uint64_t min_block, uint64_t min_query, Output& out) {
-  std::string err, text;
-  const std::vector<ChainRecord> recs = parse_chain(read_all(input), &err);
-  for (const ChainRecord& r : recs) {
+  std::string text;
+  Dev d;
+  ChainInput in = load_chain(d, input);
+  if (in.on_device) in.fetch_lines(d); /* the text is formatted here: the data lines come back once */
+  const std::string& err = in.error;
+  for (size_t i = 0; i < in.recs.size(); i++) {
+    const ChainRecord& r = in.recs[i];
     if (r.target_end - r.target_start < min_block || r.query_size < min_query) continue;
     text += "chain\t" + format_chain_score(r.score) + "\t" + r.target_name + "\t";
     append_u64(text, r.target_size);
@@ -198,13 +203,13 @@ int cmd_filter_chain(const std::string* input, uint64_t min_block, uint64_t min_
     append_u64(text, r.query_end);
     text.push_back('\t');
     append_u64(text, r.chain_id);
-    for (size_t k = 0; k + 2 < r.lines.size(); k += 3) { /* chain.rs:92-100 */
+    for (size_t k = 3 * (size_t)in.line_off[i]; k < 3 * (size_t)in.line_off[i + 1]; k += 3) { /* chain.rs:92-100 */
       text.push_back('\n');
-      append_u64(text, r.lines[k]);
+      append_u64(text, in.lines[k]);
       text.push_back('\t');
-      append_u64(text, r.lines[k + 1]);
+      append_u64(text, in.lines[k + 1]);
       text.push_back('\t');
-      append_u64(text, r.lines[k + 2]);
+      append_u64(text, in.lines[k + 2]);
     }
     text += "\n\n";
   }

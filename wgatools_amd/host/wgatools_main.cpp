@@ -1379,6 +1379,26 @@ static int run_command(int argc, char** argv) {
       printf("%zu records %zu lines %s\n", recs.size(), nl, e.c_str());
       return 0;
     }
+    if (cmd == "__chain_reader") { /* which reader takes this file, and the chains it yields */
+      Dev d;
+      ChainInput in = load_chain(d, rest.empty() ? nullptr : &rest[0]);
+      const bool dev = in.on_device;
+      if (dev) in.fetch_lines(d);
+      printf("%s\n", dev ? "device" : "host");
+      for (size_t k = 0; k < in.recs.size(); k++) {
+        const ChainRecord& r = in.recs[k];
+        uint64_t sum = 0; /* wraps */
+        for (size_t x = 3 * (size_t)in.line_off[k]; x < 3 * (size_t)in.line_off[k + 1]; x++) sum += in.lines[x];
+        printf("%s|%s|%llu|%c|%llu|%llu|%s|%llu|%c|%llu|%llu|%llu|%llu|%llu\n", format_chain_score(r.score).c_str(),
+               r.target_name.c_str(), (unsigned long long)r.target_size, r.target_neg ? '-' : '+',
+               (unsigned long long)r.target_start, (unsigned long long)r.target_end, r.query_name.c_str(),
+               (unsigned long long)r.query_size, r.query_neg ? '-' : '+', (unsigned long long)r.query_start,
+               (unsigned long long)r.query_end, (unsigned long long)r.chain_id, (unsigned long long)in.n_lines(k),
+               (unsigned long long)sum);
+      }
+      if (!in.error.empty()) fail(in.error);
+      return 0;
+    }
     if (cmd == "__paf_reader") { /* which reader takes this file, and the fixed fields it yields */
       Dev d;
       PafInput pin = load_paf(d, rest.empty() ? nullptr : &rest[0], false);
