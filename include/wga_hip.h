@@ -289,10 +289,15 @@ int wga_paf_call_events(wga_ctx*, const wga_cigar_batch*, uint64_t svlen, int sn
  * d_ev / d_ev_off: the events of wga_paf_call_events on the same batch (with the same svlen).  d_recs: per record its
  * names (offsets into d_names), PAF coordinates and the place of its fetched target / query sequence inside the pools
  * (paf.rs:221-237: [start, end] inclusive, clipped at the contig end).  Two calls: d_out == NULL -> d_nbytes[n] and
- * d_err[n]; then d_out_off = exclusive scan of d_nbytes and the call again with d_out.  d_err[i].item == ~0: clean;
- * otherwise the record's first failing item (0 = the <INV> row, 1 + e = event e) with kind 1 = a REF / ALT slice outside
- * the fetched sequence (the reference's slice panic, caller.rs:695-696,753-754,800-801) or kind 2 = a base outside
- * ACGTN in any case (noodles-vcf's parse error; ch = the byte); the record's text ends in front of that item. */
+ * d_err[n]; then d_out_off = exclusive scan of d_nbytes and the call again with d_out.  d_err[i].item == ~0: clean
+ * (kind and ch are 0); otherwise the record's first failing item (0 = the <INV> row, 1 + e = event e) with kind 1 = a
+ * REF / ALT slice outside the fetched sequence (the reference's slice panic, caller.rs:695-696,753-754,800-801) or
+ * kind 2 = a base outside ACGTN in any case (noodles-vcf's parse error; ch = the byte); the record's text ends in front
+ * of that item.  A '-' record whose fetched target is empty (t_len == 0) reports kind 1 at item 0 (the <INV> row quotes
+ * the first fetched base, :642) and has no text: the kernel reads no byte of a sequence whose length is 0, and t_off /
+ * q_off only have to lie inside the pools.  An indel event in front of which neither sequence has advanced (a
+ * zero-length M-like op: `0=5I`) is kind 1 as well (the reference's slice start underflows, :733-737,786-790).  The fill
+ * pass writes record i's d_nbytes[i] bytes into [d_out_off[i], d_out_off[i + 1]) and touches no other byte of d_out. */
 typedef struct {
   uint64_t t_name_off, q_name_off;
   uint32_t t_name_len, q_name_len;

@@ -729,6 +729,8 @@ int orc_call_within_var(const char* chro, const char* q_chro, const char* t, con
             after_m = 0;
             continue;
           }
+          /* after_m: an '=' / X run lies in front, and a run of columns is never empty, so both offsets have moved and
+           * `- 1` cannot underflow here or in the D branch (the PAF twin below can: a CIGAR op may have length 0) */
           uint64_t ts = target_current_offset - t_start - 1;
           uint64_t qs = query_current_offset - q_start - 1;
           if (ts + 1 > t_ref_n || qs + len + 1 > q_ref_n) {
@@ -875,6 +877,12 @@ int orc_call_within_var_paf(const char* chro, const char* q_chro, const char* cg
           after_m = 0;
           continue;
         }
+        /* a zero-length M-like op in front (`0=5I`): the slice start `pos - start - 1` underflows and the slice panics
+         * (:733-737,750-751) */
+        if (t_pos == t_start || q_pos == q_start) {
+          rc = ORC_PANIC;
+          goto done;
+        }
         uint64_t ts = t_pos - t_start - 1, qs = q_pos - q_start - 1;
         if (ts + 1 > t_n || qs + len + 1 > q_n) {
           rc = ORC_PANIC;
@@ -894,6 +902,10 @@ int orc_call_within_var_paf(const char* chro, const char* q_chro, const char* cg
           t_pos += len;
           after_m = 0;
           continue;
+        }
+        if (t_pos == t_start || q_pos == q_start) { /* as for I (:786-790,800-801) */
+          rc = ORC_PANIC;
+          goto done;
         }
         uint64_t ts = t_pos - t_start - 1, qs = q_pos - q_start - 1;
         if (ts + len + 1 > t_n || qs + 1 > q_n) {

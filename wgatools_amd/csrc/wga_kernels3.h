@@ -118,6 +118,10 @@ template <class S>
 __device__ __forceinline__ void vcf_item(S& s, const VcfRecCtx& r, u64 item, u32* kind, u32* ch) {
   if (item == 0) { /* caller.rs:640-658 */
     if (!r.neg) return;
+    if (r.tn == 0) { /* the row quotes the first fetched target base: an empty fetch is the reference's slice panic (:642) */
+      *kind = 1u;
+      return;
+    }
     vcf_row_open(s, r, r.t_start + 1u);
     s.bases(r.ts, 1, kind, ch);
     vcf_lit(s, "\t<INV>\t.\t.\tSVTYPE=INV;END=");
@@ -195,6 +199,7 @@ __global__ __launch_bounds__(256) void k_paf_call_vcf(u32 n, const u32* __restri
   r.neg = strand_neg[k] != 0;
   const u64 n_items = 1u + (ev_off[k + 1] - ev_off[k]);
   u64 run = 0; /* bytes of the steps in front */
+  bool clean = true;
   for (u64 base = 0; base < n_items; base += 64u) {
     const u64 item = base + lane;
     VcfCount cs;
@@ -228,10 +233,18 @@ __global__ __launch_bounds__(256) void k_paf_call_vcf(u32 n, const u32* __restri
         e2.item = item, e2.kind = kind, e2.ch = ch;
         err[k] = e2;
       }
+      clean = false;
       break;
     }
   }
-  if (!FILL && lane == 0) nbytes[k] = run;
+  if (!FILL && lane == 0) {
+    nbytes[k] = run;
+    if (clean) {
+      wga_vcf_err_dev e2;
+      e2.item = WGA_NONE, e2.kind = 0u, e2.ch = 0u;
+      err[k] = e2;
+    }
+  }
 }
 
 /* ============================================================================================ */

@@ -126,6 +126,9 @@ MAF_REWRITE_BLOCK_DTYPE = np.dtype([("row0", "<u8"), ("n_rows", "<u4"), ("pad", 
 MAF_REWRITE_PARAMS_DTYPE = np.dtype([("min_block_size", "<u8"), ("min_query_size", "<u8"), ("filter", "<u4"), ("n_prefix", "<u4"),
                                      ("d_prefix_text", "<u8"), ("d_prefix_off", "<u8")])
 VCF_ERR_DTYPE = np.dtype([("item", "<u8"), ("kind", "<u4"), ("ch", "<u4")])
+VCF_REC_DTYPE = np.dtype([("t_name_off", "<u8"), ("q_name_off", "<u8"), ("t_name_len", "<u4"), ("q_name_len", "<u4"),
+                          ("t_start", "<u8"), ("t_end", "<u8"), ("q_start", "<u8"), ("q_end", "<u8"),
+                          ("t_off", "<u8"), ("t_len", "<u8"), ("q_off", "<u8"), ("q_len", "<u8")])
 MAF_VCF_REC_DTYPE = np.dtype([("t_name_off", "<u8"), ("q_name_off", "<u8"), ("t_name_len", "<u4"), ("q_name_len", "<u4"),
                               ("t_start", "<u8"), ("q_start", "<u8"), ("q_size", "<u8"), ("q_neg", "<u4"), ("pad", "<u4")])
 
@@ -444,6 +447,18 @@ class Engine:
         self._check(self.lib.wga_paf_call_events(self.ctx, C.byref(batch.c), int(svlen), int(bool(snp)),
                                                  _p(ev_cnt), _p(ev), _p(ev_off)))
         return ev_cnt
+
+    def paf_call_vcf(self, batch, svlen, ev, ev_off, recs, names, t_pool, q_pool, nbytes=None, err=None, out=None,
+                     out_off=None):
+        """the VCF rows of `call` on PAF (wga_paf_call_vcf, K16) on K7's event list: count pass when out is None (returns
+        nbytes, err), fill pass otherwise.  recs: n x VCF_REC_DTYPE"""
+        if out is None:
+            nbytes = nbytes if nbytes is not None else self.empty(batch.n, np.uint64)
+            err = err if err is not None else self.empty(batch.n, VCF_ERR_DTYPE)
+        self._check(self.lib.wga_paf_call_vcf(self.ctx, C.byref(batch.c), int(svlen), _p(ev), _p(ev_off), _p(recs), _p(names),
+                                              _p(t_pool), _p(q_pool), _p(nbytes) if out is None else None,
+                                              _p(err) if out is None else None, _p(out), _p(out_off)))
+        return nbytes, err
 
     def pafcov_accumulate(self, batch, target_id, t_start, cov_off, cov_len, cov, total_cov):
         self._check(self.lib.wga_pafcov_accumulate(self.ctx, C.byref(batch.c), _p(target_id),
