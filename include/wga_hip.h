@@ -730,6 +730,59 @@ int wga_maf_rewrite(wga_ctx*, const uint8_t* d_text, const wga_maf_slice_row* d_
                     const wga_maf_rewrite_block* d_blocks, uint64_t n_lines, const wga_maf_rewrite_params* params, void* d_work,
                     uint64_t* text_bytes, uint32_t* n_kept, uint32_t* first_bad_block, uint8_t* d_out);
 
+/* ---- K24: `filter -f paf` — a line filter and the pair sums of `-a` (tools/filter.rs:88-160 with the csv writer of
+ *      paf.rs:50-65) ----------------------------------------------------------------------------------------------------------
+ * For a plain line (WGA_PAF_OK) the reference's writer reproduces the line's bytes whenever its nine numbers are in canonical
+ * decimal: names and tags pass through as they are, only the numbers are printed anew.  Both entries work on d_text, n_bytes
+ * and d_lines[n_lines] — the arguments and the result of wga_paf_split on the same text, with its limits: n_bytes < 0xFFFFFFF0,
+ * 16 bytes of slack behind the text, n_lines < 2^32.  Both are called twice with the same arguments; the calls share d_work
+ * (wga_paf_*_work_bytes(n_lines) bytes of device memory) and keep nothing else between them.  n_lines == 0: zero counts and
+ * success.
+ *
+ * wga_paf_pairs looks only at WGA_PAF_OK lines; every other line gets d_pair_of_line[i] = 0xFFFFFFFF.  Two records are the same
+ * PAIR exactly when their query-name bytes are equal and their target-name bytes are equal ("ab","c" and "a","bc" are two
+ * pairs): a hash places a pair in the call's table, the names' bytes decide.  Pairs are numbered by ascending first_line, so
+ * the numbering is the same for every call on the same lines.  A pair's sum is that of (num[5] - num[4]) over its records, the
+ * difference and the sum wrapping mod 2^64 (filter.rs:118-127 in a release build).
+ *   d_pairs == NULL and d_pair_of_line == NULL: the grouping; *n_pairs (host value; synchronises).
+ *   otherwise: d_pair_of_line[n_lines] and d_pairs[*n_pairs] are written; cap_pairs >= *n_pairs (WGA_E_TOO_SMALL otherwise).
+ * Context parameter "paf_pair_hash_bits" (1 .. 64, default 64): the hash is cut to that many low bits before it picks a place,
+ * so that a test can make every pair collide.
+ *
+ * wga_paf_filter writes the text of the lines that are kept, in input order:
+ *   selection  a WGA_PAF_SKIP line is never written.  A WGA_PAF_OK line is kept in threshold mode (d_pair_keep == NULL) unless
+ *              (num[5] - num[4]) (wrapping) < min_block_size or num[0] < min_query_size (filter.rs:96-101: both compare with
+ *              `<`), in pair mode when d_pair_keep[d_pair_of_line[i]] != 0 (filter.rs:143-152 with the caller's flags).
+ *   text       a kept line's bytes from its first byte up to (not including) its `\n`, or up to n_bytes for an unterminated
+ *              last line, and a `\n`.  *text_bytes = the sum of (length + 1) over the kept lines, *n_kept = their count.
+ *   exactness  a line is INEXACT when it is WGA_PAF_FALLBACK, holds a byte >= 0x80, or is WGA_PAF_OK and one of its nine
+ *              numbers (columns 2, 3, 4, 7 .. 12) starts with `+` or with `0` and another digit: the reference would write
+ *              other bytes than the line's, or none.  Every line is checked, kept or not.  *first_inexact_line = the lowest
+ *              such line, WGA_NONE when there is none.  If there is one, *text_bytes = 0, the second call writes nothing and
+ *              the caller takes its csv-semantics path for this text.
+ *   d_out == NULL: selection, line extents, places and the exactness check; the three host values (synchronises).
+ *   otherwise     : the text at d_out[0 .. text_bytes); d_out is 16-byte aligned, no byte outside that extent is written;
+ *                   *text_bytes and *n_kept are read as the first call left them. */
+typedef struct {
+  uint64_t first_line;           /* lowest line index of the pair */
+  uint64_t sum;                  /* sum of (num[5] - num[4]) over the pair's records, both wrapping mod 2^64 */
+  uint64_t qname_off, tname_off; /* the spans of first_line's names in d_text */
+  uint32_t qname_len, tname_len;
+} wga_paf_pair; /* 40 bytes */
+uint64_t wga_paf_pairs_work_bytes(uint64_t n_lines);
+int wga_paf_pairs(wga_ctx*, const uint8_t* d_text, uint64_t n_bytes, const wga_paf_line* d_lines, uint64_t n_lines, void* d_work,
+                  uint64_t* n_pairs, uint32_t* d_pair_of_line, wga_paf_pair* d_pairs, uint64_t cap_pairs);
+typedef struct {
+  uint64_t min_block_size, min_query_size; /* used when d_pair_keep == NULL */
+  const uint32_t* d_pair_of_line;          /* wga_paf_pairs' array for the same lines */
+  const uint8_t* d_pair_keep;              /* one byte per pair; NULL: threshold mode */
+} wga_paf_filter_params;
+#define WGA_PAF_FILTER_TILE_BYTES 8192 /* the text leaves in tiles of this many bytes, one per block (tests place line ends by it) */
+uint64_t wga_paf_filter_work_bytes(uint64_t n_lines);
+int wga_paf_filter(wga_ctx*, const uint8_t* d_text, uint64_t n_bytes, const wga_paf_line* d_lines, uint64_t n_lines,
+                   const wga_paf_filter_params*, void* d_work, uint64_t* text_bytes, uint64_t* n_kept,
+                   uint64_t* first_inexact_line, uint8_t* d_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -96,6 +96,11 @@ PROTOTYPES = {
     "wga_maf_rewrite_work_bytes": (C.c_uint64, [C.c_uint32, C.c_uint64]),
     "wga_maf_rewrite": (C.c_int, [vp, vp, vp, C.c_uint32, vp, C.c_uint64, vp, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
                                   C.POINTER(C.c_uint32), vp]),
+    "wga_paf_pairs_work_bytes": (C.c_uint64, [C.c_uint64]),
+    "wga_paf_pairs": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.POINTER(C.c_uint64), vp, vp, C.c_uint64]),
+    "wga_paf_filter_work_bytes": (C.c_uint64, [C.c_uint64]),
+    "wga_paf_filter": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                 C.POINTER(C.c_uint64), vp]),
     "wga_pafcov_finalize": (C.c_int, [vp, C.c_uint32, vp, vp, vp]),
     "wga_pafpseudo_fill": (C.c_int, [vp, C.POINTER(CigarBatch), C.c_int, vp, C.c_uint64, vp, vp,
                                      vp, vp, vp, vp]),

@@ -1,4 +1,5 @@
-/* capi_text.inc — K8 / K9 / K13 / K14 / K15 / K17 / K18 / K23: text in, text out (tokenisers, line splitters, FASTA pool, BGZF, BED lines).
+/* capi_text.inc — K8 / K9 / K13 / K14 / K15 / K17 / K18 / K23 / K24: text in, text out (tokenisers, line splitters, FASTA pool, BGZF, BED
+ * lines, the PAF line filter and its pair sums).
  * A part of wga_capi.cpp (included there: one translation unit). */
 /* K13 / K14 / K23: the two delimiter lists of a text (count, scan, fill over 4 KB blocks) in the context scratch, with `tail`
  * bytes of the caller's own behind them (tail_per_256_lines for every 256 lines or part of them, plus tail_fixed).
@@ -118,6 +119,155 @@ int wga_maf_split(wga_ctx* c, const uint8_t* d_text, uint64_t n_bytes, uint64_t*
                   uint64_t cap_lines) {
   static_assert(sizeof(wga_maf_line) == sizeof(wga_maf_line_dev), "wga_maf_line layout");
   return split_lines<1>(c, d_text, n_bytes, n_lines, (void*)d_lines, cap_lines);
+}
+
+/* d_work of K24's filter in u64 words: header [2] | the scan of (bytes | kept << 32) [n + 1] | the kept lines' places [n + 1] |
+ * their sources [n] (the scan's input before that) | the newlines' positions, u32 [n] */
+uint64_t wga_paf_filter_work_bytes(uint64_t n_lines) { return 8ull * (3ull * n_lines + 4ull + (n_lines + 1ull) / 2ull); }
+
+int wga_paf_filter(wga_ctx* c, const uint8_t* d_text, uint64_t n_bytes, const wga_paf_line* d_lines, uint64_t n_lines,
+                   const wga_paf_filter_params* params, void* d_work, uint64_t* text_bytes, uint64_t* n_kept,
+                   uint64_t* first_inexact_line, uint8_t* d_out) {
+  int rc = ctx_bind(c);
+  if (rc) return rc;
+  static_assert(sizeof(wga_paf_filter_params) == 32 && sizeof(wga_paf_filter_params) == sizeof(wga_paf_filter_params_dev),
+                "K24 params layout");
+  if (!params || !text_bytes || !n_kept || !first_inexact_line) return fail(WGA_E_INVALID_ARG, "null argument", nullptr);
+  if (n_lines >= 0xFFFFFFFFull || n_bytes >= 0xFFFFFFF0ull) return fail(WGA_E_INVALID_ARG, "a text within wga_paf_split's limits", nullptr);
+  if (n_lines && (!d_text || !d_lines || !d_work || n_bytes == 0)) return fail(WGA_E_INVALID_ARG, "null array", nullptr);
+  if (params->d_pair_keep && !params->d_pair_of_line) return fail(WGA_E_INVALID_ARG, "d_pair_keep without d_pair_of_line", nullptr);
+  const u32 n = (u32)n_lines;
+  K24Hdr* hdr = (K24Hdr*)d_work;
+  u64* P = (u64*)d_work + 2;
+  u64* koff = P + n + 1u;
+  u64* ksrc = koff + n + 1u;
+  u32* nl_pos = (u32*)(ksrc + n);
+  if (!d_out) {
+    *text_bytes = 0;
+    *n_kept = 0;
+    *first_inexact_line = WGA_NONE;
+    if (n == 0) return WGA_OK;
+    /* scratch: the text blocks' newline counts, scanned in place (+ total) | that scan's partials | the line scan's partials */
+    const u32 nb = (u32)((n_bytes + 4095u) / 4096u);
+    void* ws = nullptr;
+    if ((rc = ctx_scratch(c, ((size_t)nb + 1 + (size_t)nb / 1024 + 4 + (size_t)n / 1024 + 4) * sizeof(u64), &ws))) return rc;
+    u64* blk = (u64*)ws;
+    u64* partial = blk + nb + 1;
+    u64* lpartial = partial + (size_t)nb / 1024 + 4;
+    RT_CHECK(rt_memset(hdr, 0xFF, sizeof(K24Hdr), c->stream));
+    WGA_LAUNCH(k_paf_newlines<false>, nb, WGA_BLOCK, c->stream, d_text, (u64)n_bytes, blk, (const u64*)nullptr, (u32*)nullptr,
+               (u64)0, (K24Hdr*)nullptr);
+    LAUNCH_CHECK();
+    ScanPlain f;
+    f.in = blk;
+    if ((rc = run_scan_ws(c, f, nb, blk, partial))) return rc;
+    u64 n_nl = 0;
+    u8 last = 0;
+    RT_CHECK(rt_d2h(&n_nl, blk + nb, sizeof n_nl, c->stream));
+    RT_CHECK(rt_d2h(&last, d_text + n_bytes - 1, 1, c->stream));
+    if (n_nl + (last != (u8)0x0A ? 1u : 0u) != n_lines) return fail(WGA_E_INVALID_ARG, "n_lines is not this text's", nullptr);
+    WGA_LAUNCH(k_paf_newlines<true>, nb, WGA_BLOCK, c->stream, d_text, (u64)n_bytes, (u64*)nullptr, (const u64*)blk, nl_pos,
+               (u64)n, hdr);
+    LAUNCH_CHECK();
+    wga_paf_filter_params_dev Pd;
+    Pd.min_block_size = params->min_block_size;
+    Pd.min_query_size = params->min_query_size;
+    Pd.pair_of_line = params->d_pair_of_line;
+    Pd.pair_keep = params->d_pair_keep;
+    WGA_LAUNCH(k_paf_filter_lines, (n + 255u) / 256u, WGA_BLOCK, c->stream, d_text, (u64)n_bytes, (u64)n, (const u64*)(blk + nb),
+               (const u32*)nl_pos, (const wga_paf_line_dev*)d_lines, Pd, ksrc, hdr);
+    LAUNCH_CHECK();
+    f.in = ksrc;
+    if ((rc = run_scan_ws(c, f, n, P, lpartial))) return rc;
+    WGA_LAUNCH(k_paf_filter_compact, (n + 255u) / 256u, WGA_BLOCK, c->stream, (u64)n, (const u32*)nl_pos, (const u64*)P, koff, ksrc);
+    LAUNCH_CHECK();
+    u64 tot = 0;
+    K24Hdr h;
+    RT_CHECK(rt_d2h(&tot, P + n, sizeof tot, c->stream));
+    RT_CHECK(rt_d2h(&h, hdr, sizeof h, c->stream));
+    *n_kept = tot >> 32;
+    *first_inexact_line = h.first_inexact;
+    *text_bytes = h.first_inexact == WGA_NONE ? tot & 0xFFFFFFFFull : 0u;
+    return WGA_OK;
+  }
+  if (n == 0 || *text_bytes == 0) return WGA_OK;
+  if (*n_kept == 0 || *n_kept > n_lines || *text_bytes > n_bytes + 1u) return fail(WGA_E_INVALID_ARG, "the counts are not the first call's", nullptr);
+  if (((uintptr_t)d_out & 15u) != 0) return fail(WGA_E_INVALID_ARG, "d_out must be 16-byte aligned", nullptr);
+  const u64 tiles = (*text_bytes + WGA_PAF_FILTER_TILE - 1u) / WGA_PAF_FILTER_TILE;
+  WGA_LAUNCH(k_paf_filter_fill, (u32)tiles, WGA_BLOCK, c->stream, d_text, (const u64*)koff, (const u64*)ksrc, (u32)*n_kept,
+             (u64)*text_bytes, d_out);
+  LAUNCH_CHECK();
+  return WGA_OK;
+}
+
+/* d_work of K24's pairs in u64 words: header [2] | the table [M] | sums [n] | the scan of "is a representative" [n + 1] | then u32:
+ * representatives [n] | start slots [n] | the two lists of lines without a pair [n] each */
+static uint64_t paf_pair_slots(uint64_t n_lines) {
+  uint64_t m = 16;
+  while (m < 2 * n_lines && m < (1ull << 32)) m <<= 1;
+  return m;
+}
+uint64_t wga_paf_pairs_work_bytes(uint64_t n_lines) {
+  return 8ull * (2ull + paf_pair_slots(n_lines) + 2ull * n_lines + 1ull) + 16ull * n_lines;
+}
+
+int wga_paf_pairs(wga_ctx* c, const uint8_t* d_text, uint64_t n_bytes, const wga_paf_line* d_lines, uint64_t n_lines, void* d_work,
+                  uint64_t* n_pairs, uint32_t* d_pair_of_line, wga_paf_pair* d_pairs, uint64_t cap_pairs) {
+  int rc = ctx_bind(c);
+  if (rc) return rc;
+  static_assert(sizeof(wga_paf_pair) == 40 && sizeof(wga_paf_pair) == sizeof(wga_paf_pair_dev), "wga_paf_pair layout");
+  if (!n_pairs) return fail(WGA_E_INVALID_ARG, "n_pairs null", nullptr);
+  if (n_lines >= 0xFFFFFFFFull || n_bytes >= 0xFFFFFFF0ull) return fail(WGA_E_INVALID_ARG, "a text within wga_paf_split's limits", nullptr);
+  if (n_lines && (!d_text || !d_lines || !d_work)) return fail(WGA_E_INVALID_ARG, "null array", nullptr);
+  const u32 n = (u32)n_lines;
+  const u64 M = paf_pair_slots(n_lines);
+  const u32 slot_mask = (u32)(M - 1u);
+  K24PairHdr* hdr = (K24PairHdr*)d_work;
+  u64* slots = (u64*)d_work + 2;
+  u64* sum = slots + M;
+  u64* pidx = sum + n;
+  u32* rep = (u32*)(pidx + n + 1u);
+  u32* start = rep + n;
+  u32* list[2] = {start + n, start + 2u * (size_t)n};
+  const bool fill = d_pair_of_line != nullptr || d_pairs != nullptr;
+  if (!fill) {
+    *n_pairs = 0;
+    if (n == 0) return WGA_OK;
+    const unsigned bits = c->paf_pair_hash_bits;
+    const u64 hash_mask = bits >= 64u ? ~0ull : (1ull << bits) - 1ull;
+    RT_CHECK(rt_memset(hdr, 0, sizeof(K24PairHdr), c->stream));
+    RT_CHECK(rt_memset(slots, 0xFF, (size_t)M * sizeof(u64), c->stream));
+    const wga_paf_line_dev* lines = (const wga_paf_line_dev*)d_lines;
+    WGA_LAUNCH(k_paf_pairs_init, (n + 255u) / 256u, WGA_BLOCK, c->stream, d_text, lines, (u64)n, hash_mask, slot_mask, start, rep,
+               sum, list[0], hdr);
+    LAUNCH_CHECK();
+    u64 m = 0;
+    RT_CHECK(rt_d2h(&m, &hdr->cnt[0], sizeof m, c->stream));
+    for (u64 r = 0; m; r++) { /* every round gives the lowest line of each start slot's class a pair, or steps over a taken slot */
+      if (m > n || r > 2u * M + 64u) return fail(WGA_E_HIP, "the pair table did not settle", nullptr);
+      const u32 g = (u32)((m + 255u) / 256u);
+      WGA_LAUNCH(k_paf_pairs_claim, g, WGA_BLOCK, c->stream, (const u32*)list[r & 1u], m, r, slot_mask, (const u32*)start, slots, hdr);
+      LAUNCH_CHECK();
+      WGA_LAUNCH(k_paf_pairs_settle, g, WGA_BLOCK, c->stream, d_text, lines, (const u32*)list[r & 1u], m, r, slot_mask,
+                 (const u32*)start, (const u64*)slots, rep, sum, list[(r + 1u) & 1u], hdr);
+      LAUNCH_CHECK();
+      RT_CHECK(rt_d2h(&m, &hdr->cnt[(r + 1u) & 1u], sizeof m, c->stream));
+    }
+    ScanPairRep f;
+    f.rep = rep;
+    if ((rc = run_scan(c, f, n, pidx))) return rc;
+    u64 np = 0;
+    RT_CHECK(rt_d2h(&np, pidx + n, sizeof np, c->stream));
+    *n_pairs = np;
+    return WGA_OK;
+  }
+  if (n == 0) return WGA_OK;
+  if (!d_pair_of_line || (*n_pairs && !d_pairs)) return fail(WGA_E_INVALID_ARG, "null array", nullptr);
+  if (cap_pairs < *n_pairs) return fail(WGA_E_TOO_SMALL, "d_pairs too small", nullptr);
+  WGA_LAUNCH(k_paf_pairs_emit, (n + 255u) / 256u, WGA_BLOCK, c->stream, (const wga_paf_line_dev*)d_lines, (u64)n, (const u32*)rep,
+             (const u64*)sum, (const u64*)pidx, (u32*)d_pair_of_line, (wga_paf_pair_dev*)d_pairs);
+  LAUNCH_CHECK();
+  return WGA_OK;
 }
 
 int wga_chain_split(wga_ctx* c, const uint8_t* d_text, uint64_t n_bytes, uint64_t* n_chains, uint64_t* n_data_lines,

@@ -38,6 +38,7 @@
 #include "wga_k21_maf_slice.h" /* K21: maf-ext's slices */
 #include "wga_k22_maf_rewrite.h" /* K22: filter and rename on MAF */
 #include "wga_k23_chain_split.h" /* K23: the chain line splitter */
+#include "wga_k24_paf_filter.h" /* K24: filter on PAF, the pair sums of `-a` */
 
 /* A grow-only device buffer of a context.  reserve() leaves it with room for `need` bytes: one that is too small is freed
  * behind the work of the context's stream and allocated anew with `grow` (>= need) bytes — every site has its own growth rule —,
@@ -101,6 +102,7 @@ struct wga_ctx {
   uint64_t op_piece_ops = 8192;  /* ... are walked in pieces of this many (a multiple of 256), one wave each (test knobs: "op_long_ops", "op_piece_ops") */
   uint64_t maf_long_cols = 32768;  /* MAF blocks beyond this many columns are walked piece by piece ... */
   uint64_t maf_piece_cols = 16384; /* ... of this many columns, one wave each (test knobs: "maf_long_cols", "maf_piece_cols") */
+  unsigned paf_pair_hash_bits = 64; /* K24: the low bits of the pair hash that pick a slot (test knob "paf_pair_hash_bits": few bits make the pairs collide) */
   unsigned maf_group = 0;          /* blocks per wave of the MAF stream kernels, 1 .. 8 ("maf_group"; 0 = by the number of blocks) */
   DevBuf maf_tab;                  /* K3 / K4: the table of a call's long blocks (header, list, pieces) */
   bool maf_hdr_clean = false;      /* the header's append counters are zero (the plan kernel leaves them so) */
@@ -361,6 +363,11 @@ int wga_ctx_set_param(wga_ctx* c, const char* name, int64_t value) {
     c->maf_group = (unsigned)value;
     return WGA_OK;
   }
+  if (strcmp(name, "paf_pair_hash_bits") == 0) { /* wga_paf_pairs: the hash is cut to this many low bits before it picks a place */
+    if (value < 1 || value > 64) return fail(WGA_E_INVALID_ARG, "paf_pair_hash_bits: 1 .. 64", nullptr);
+    c->paf_pair_hash_bits = (unsigned)value;
+    return WGA_OK;
+  }
   if (strcmp(name, "expand_variant") == 0) {
     if (value != -1 && value != 0 && value != 3) return fail(WGA_E_INVALID_ARG, "expand_variant: -1 (the library's choice), 0, 3", nullptr);
     c->expand_variant = (int)value;
@@ -496,6 +503,10 @@ int wga_ctx_get_param(wga_ctx* c, const char* name, int64_t* value) {
       RT_CHECK(rt_d2h(h, c->stream_counts, sizeof(h), c->stream));
       *value = (int64_t)h[0] + (int64_t)h[1];
     }
+    return WGA_OK;
+  }
+  if (strcmp(name, "paf_pair_hash_bits") == 0) {
+    *value = (int64_t)c->paf_pair_hash_bits;
     return WGA_OK;
   }
   if (strcmp(name, "expand_job_tiles") == 0) {

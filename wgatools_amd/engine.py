@@ -29,6 +29,13 @@ CHAIN_HEAD_DTYPE = np.dtype([("num", np.uint64, 8), ("tname_off", np.uint64), ("
                              ("tname_len", np.uint32), ("qname_len", np.uint32), ("tstrand_neg", np.uint8),
                              ("qstrand_neg", np.uint8), ("pad", np.uint8, 6)])
 CHAIN_OK, CHAIN_FALLBACK = 0, 1
+# K24 (include/wga_hip.h wga_paf_pair / wga_paf_filter_params; WGA_PAF_FILTER_TILE_BYTES)
+PAF_PAIR_DTYPE = np.dtype([("first_line", "<u8"), ("sum", "<u8"), ("qname_off", "<u8"), ("tname_off", "<u8"),
+                           ("qname_len", "<u4"), ("tname_len", "<u4")])
+PAF_FILTER_PARAMS_DTYPE = np.dtype([("min_block_size", "<u8"), ("min_query_size", "<u8"), ("d_pair_of_line", "<u8"),
+                                    ("d_pair_keep", "<u8")])
+PAF_OK, PAF_SKIP, PAF_FALLBACK = 0, 1, 2
+PAF_FILTER_TILE = 8192
 
 OP_CODES = {"M": 0, "I": 1, "D": 2, "N": 3, "S": 4, "H": 5, "P": 6, "=": 7, "X": 8}
 OP_I_CONT, OP_D_CONT, OP_OTHER = 9, 10, 11
@@ -393,6 +400,53 @@ class Engine:
         cap = 0 if lines is None else (lines.numel() if hasattr(lines, "numel") else lines.size)
         self._check(self.lib.wga_paf_split(self.ctx, _p(text), int(n_bytes), C.byref(nl), _p(lines), int(cap)))
         return int(nl.value)
+
+    def paf_pairs(self, text, n_bytes, lines, n_lines):
+        """K24 (filter.rs:108-160): the (query name, target name) pairs of the OK lines of wga_paf_split's table, both calls
+        of wga_paf_pairs.  Returns (pairs as numpy PAF_PAIR_DTYPE in first-line order, pair_of_line as a device array of u32:
+        0xFFFFFFFF for a line that is not OK).  Bytes behind either array are checked to be left alone."""
+        n_lines = int(n_lines)
+        work = self.empty(max(int(self.lib.wga_paf_pairs_work_bytes(n_lines)), 16), np.uint8)
+        np_ = C.c_uint64(0)
+        args = (self.ctx, _p(text), int(n_bytes), _p(lines), n_lines, _p(work), C.byref(np_))
+        self._check(self.lib.wga_paf_pairs(*args, None, None, 0))
+        n_pairs = int(np_.value)
+        pol = self.empty(n_lines + 4, np.uint32).fill(0xA5)
+        pairs = self.empty(n_pairs + 1, PAF_PAIR_DTYPE).fill(0xA5)
+        self._check(self.lib.wga_paf_pairs(*args, _p(pol), _p(pairs), n_pairs))
+        self.sync()
+        if int(np_.value) != n_pairs:
+            raise _lib.WgaError("wga_paf_pairs changed *n_pairs in its second call")
+        if not ((pol.numpy()[n_lines:] == 0xA5A5A5A5).all() and pairs.numpy()[n_pairs:].tobytes() == b"\xa5" * 40):
+            raise _lib.WgaError("wga_paf_pairs wrote behind its arrays")
+        pol.shape = (n_lines,)
+        return pairs.numpy()[:n_pairs], pol
+
+    def paf_filter(self, text, n_bytes, lines, n_lines, min_block_size=0, min_query_size=0, pair_of_line=None, pair_keep=None):
+        """K24 (filter.rs:88-160): the text of the kept lines of wga_paf_split's table, both calls of wga_paf_filter.  Threshold
+        mode, or pair mode when pair_keep (a device array of one byte per pair) and pair_of_line (wga_paf_pairs') are given.
+        Returns (text, n_kept, first inexact line or None); the 64 bytes in front of and behind the text are checked."""
+        n_lines = int(n_lines)
+        par = np.zeros(1, dtype=PAF_FILTER_PARAMS_DTYPE)
+        par["min_block_size"], par["min_query_size"] = int(min_block_size), int(min_query_size)
+        if pair_keep is not None:
+            par["d_pair_of_line"], par["d_pair_keep"] = _p(pair_of_line), _p(pair_keep)
+        work = self.empty(max(int(self.lib.wga_paf_filter_work_bytes(n_lines)), 16), np.uint8)
+        total, kept, bad = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        args = (self.ctx, _p(text), int(n_bytes), _p(lines), n_lines, par.ctypes.data, _p(work), C.byref(total), C.byref(kept),
+                C.byref(bad))
+        self._check(self.lib.wga_paf_filter(*args, None))
+        first = (int(total.value), int(kept.value), int(bad.value))
+        guard = 64  # bytes around the text that the fill call must leave alone
+        out = self.upload(np.full(first[0] + 2 * guard, 0xA5, dtype=np.uint8))
+        self._check(self.lib.wga_paf_filter(*args, out.ptr + guard))
+        self.sync()
+        if (int(total.value), int(kept.value), int(bad.value)) != first:
+            raise _lib.WgaError("wga_paf_filter changed its counts in the second call")
+        got = out.numpy()
+        if not ((got[:guard] == 0xA5).all() and (got[guard + first[0]:] == 0xA5).all()):
+            raise _lib.WgaError("wga_paf_filter wrote outside d_out[0 .. text_bytes)")
+        return got[guard:guard + first[0]].tobytes(), first[1], (None if first[2] == int(NONE) else first[2])
 
     def maf_split(self, text, n_bytes, lines=None):
         """K14: number of text lines (lines is None), or the wga_maf_line of every line"""

@@ -103,9 +103,10 @@ static int rewrite_maf(const std::string* input, const std::string& header, MafR
 }
 
 /* ---- filter (tools/filter.rs, utils.rs:540-576) --------------------------------------------------------------------------------
- * MAF: K22 with the thresholds (`-a` is ignored, as in the reference).  PAF and chain are written on the host: the records are
- * re-serialised field by field (csv writer / the chain Display impls), which no kernel of this engine does; a plain chain file
- * is read on the device (ChainInput) and its data lines come back in one copy. */
+ * MAF: K22 with the thresholds (`-a` is ignored, as in the reference).  PAF: K24 selects and copies the lines of every piece whose
+ * bytes the csv writer would reproduce, and groups the name pairs of `-a`; the other pieces are re-serialised field by field on
+ * the host (csv writer).  Chain is written on the host (the chain Display impls re-format scores and white space, which no
+ * kernel of this engine does); a plain chain file is read on the device (ChainInput) and its data lines come back in one copy. */
 static const char* kFilterNoQuery = "panic: a block with a single s-line has no query row (maf.rs:430 index out of bounds)";
 
 int cmd_filter_maf(const std::string* input, uint64_t min_block, uint64_t min_query, Output& out) {
@@ -139,43 +140,204 @@ static void filter_paf_row(std::string& rows, const PafRecord& r) { /* csv write
   rows.push_back('\n');
 }
 
-int cmd_filter_paf(const std::string* input, uint64_t min_block, uint64_t min_query, const uint64_t* min_align, Output& out) {
-  Dev d; /* never started: with tags wanted every piece goes through the host reader */
+/* ---- filter -f paf on the device (K24) -----------------------------------------------------------------------------------------
+ * For a plain line whose nine numbers are in canonical decimal the csv writer reproduces the line's bytes, so a piece whose lines
+ * are all of that kind (wga_paf_filter's exactness check: no fallback line of the splitter, no byte >= 0x80, no `+5` / `007`) is
+ * filtered where it was uploaded: the line table stays on the device, no record is built, and the kept lines leave through the
+ * pinned-buffer sink of the MAF window commands.  Any other piece goes through parse_paf + filter_paf_row with the same record,
+ * line and byte counters, so device and host pieces may alternate within one file and the reader's error text is what it was.
+ * WGA_PAF_READER=host sends every piece to the host path.  The PAF filter runs on device 0 whatever --gpus says. */
+struct PafOnDev {
+  size_t owned0 = 0; /* the Dev's buffers in front of this piece's */
+  uint8_t* d_text = nullptr;
+  wga_paf_line* d_lines = nullptr;
+  void* d_work = nullptr;
+  uint64_t n_bytes = 0, n_lines = 0, n_ok = 0; /* n_ok: the piece's records */
+  uint64_t bytes = 0, kept = 0;                /* of the last count call */
+};
+static bool paf_filter_host_forced() {
+  const char* force = getenv("WGA_PAF_READER");
+  return force && strcmp(force, "host") == 0;
+}
+/* the piece on the device, split, and through the count call at thresholds 0 (every record kept: n_ok).  False, with nothing left
+ * on the device: the piece is the host path's. */
+static bool paf_filter_upload(Dev& d, std::string& text, PafOnDev& p) {
+  if (paf_filter_host_forced() || text.empty() || text.size() >= 0xFFFFFFF0ull) return false;
+  d.init();
+  p = PafOnDev();
+  p.owned0 = d.owned.size();
+  p.n_bytes = text.size();
+  text.append(16, '\0'); /* slack behind the text for whole-vector loads */
+  p.d_text = d.upload((const uint8_t*)text.data(), text.size());
+  text.resize(text.size() - 16);
+  g_timer.mark("upload");
+  d.check(wga_paf_split(d.ctx, p.d_text, p.n_bytes, &p.n_lines, nullptr, 0));
+  p.d_lines = (wga_paf_line*)d.alloc((size_t)(p.n_lines + 1) * sizeof(wga_paf_line));
+  d.check(wga_paf_split(d.ctx, p.d_text, p.n_bytes, &p.n_lines, p.d_lines, p.n_lines));
+  p.d_work = d.alloc((size_t)wga_paf_filter_work_bytes(p.n_lines));
+  const wga_paf_filter_params all = {0, 0, nullptr, nullptr};
+  uint64_t inexact = WGA_NONE;
+  d.check(wga_paf_filter(d.ctx, p.d_text, p.n_bytes, p.d_lines, p.n_lines, &all, p.d_work, &p.bytes, &p.kept, &inexact, nullptr));
+  p.n_ok = p.kept;
+  g_timer.mark("device split + exactness");
+  if (inexact == WGA_NONE) return true;
+  d.release_to(p.owned0);
+  return false;
+}
+/* the text of the piece's kept lines: the count call (unless `counted`: the one at thresholds 0 is the caller's), the fill, out */
+static void paf_filter_write(Dev& d, PafOnDev& p, const wga_paf_filter_params& par, bool counted, Output& out) {
+  uint64_t inexact = WGA_NONE;
+  if (!counted)
+    d.check(wga_paf_filter(d.ctx, p.d_text, p.n_bytes, p.d_lines, p.n_lines, &par, p.d_work, &p.bytes, &p.kept, &inexact, nullptr));
+  if (p.bytes == 0) return;
+  auto* d_out = (uint8_t*)d.alloc((size_t)p.bytes + 16);
+  d.check(wga_paf_filter(d.ctx, p.d_text, p.n_bytes, p.d_lines, p.n_lines, &par, p.d_work, &p.bytes, &p.kept, &inexact, d_out));
+  stream_out(d, out, d_out, (size_t)p.bytes);
+}
+
+int paf_filter_paths(const std::string* input) { /* `__paf_filter_path`: one line per piece */
+  Dev d;
   PafChunks chunks(input, true);
-  PafInput pin;
-  std::string pending_error;
+  std::string piece;
+  uint64_t line0 = 0, byte0 = 0;
+  while (chunks.next_text(piece, line0, byte0)) {
+    PafOnDev p;
+    const bool dev = paf_filter_upload(d, piece, p);
+    if (dev) d.release_to(p.owned0);
+    printf("%s\n", dev ? "device" : "host");
+  }
+  return 0;
+}
+
+int cmd_filter_paf(const std::string* input, uint64_t min_block, uint64_t min_query, const uint64_t* min_align, Output& out) {
+  Dev d; /* started by the first piece that takes the device path */
+  PafChunks chunks(input, true);
+  std::string pending_error, text;
+  uint64_t recs_before = 0, line0 = 0, byte0 = 0;
   auto next = [&]() {
     try {
-      return chunks.next(d, pin);
+      return chunks.next_text(text, line0, byte0);
     } catch (Error& e) { /* the records in front of a reader error are written first */
       pending_error = e.msg;
       return false;
     }
   };
+  auto host_records = [&](const std::string& piece, uint64_t l0, uint64_t b0, std::vector<PafRecord>& recs) {
+    try {
+      recs = parse_paf(piece, recs_before, l0, b0);
+      return true;
+    } catch (Error& e) {
+      pending_error = e.msg;
+      return false;
+    }
+  };
+  g_timer.mark("host");
   if (min_align) { /* filter.rs:108-160: the whole input, the pairs' sums, then the records in input order */
     log_warn("`min_align_size` is set, will not filter paf `min_block_size` and `min_query_size`");
-    std::vector<PafRecord> all;
-    std::map<std::pair<std::string, std::string>, uint64_t> sum;
-    while (next())
-      for (PafRecord& r : pin.recs) {
-        sum[{r.query_name, r.target_name}] += r.target_end - r.target_start; /* wraps, as the release build does */
-        all.push_back(std::move(r));
+    typedef std::map<std::pair<std::string, std::string>, uint64_t> Sums;
+    Sums sum;
+    struct Piece {
+      std::string text;
+      bool on_dev = false;
+      std::vector<uint64_t*> pair_sum; /* device piece: the global sum of every pair of the piece, in the device's numbering */
+      std::vector<PafRecord> recs;     /* host piece */
+    };
+    std::vector<Piece> pieces;
+    PafOnDev resident; /* the latest device piece stays where it is: with one piece in all, the second pass needs no upload */
+    uint32_t* d_resident_pol = nullptr;
+    bool have_resident = false;
+    /* wga_paf_pairs on a piece that is on the device: d_pol, and the piece's pairs if asked for */
+    auto device_pairs = [&](PafOnDev& p, uint32_t** d_pol, std::vector<wga_paf_pair>* pairs) {
+      void* d_work = d.alloc((size_t)wga_paf_pairs_work_bytes(p.n_lines));
+      uint64_t np = 0;
+      d.check(wga_paf_pairs(d.ctx, p.d_text, p.n_bytes, p.d_lines, p.n_lines, d_work, &np, nullptr, nullptr, 0));
+      *d_pol = (uint32_t*)d.alloc((size_t)(p.n_lines + 1) * sizeof(uint32_t));
+      auto* d_pairs = (wga_paf_pair*)d.alloc((size_t)(np + 1) * sizeof(wga_paf_pair));
+      d.check(wga_paf_pairs(d.ctx, p.d_text, p.n_bytes, p.d_lines, p.n_lines, d_work, &np, *d_pol, d_pairs, np));
+      if (pairs) {
+        pairs->resize((size_t)np);
+        if (np) d.download(pairs->data(), d_pairs, (size_t)np);
       }
+      d.release(d_pairs);
+      d.release(d_work);
+      return np;
+    };
+    while (next()) {
+      if (have_resident) d.release_to(resident.owned0);
+      have_resident = false;
+      Piece pc;
+      PafOnDev p;
+      if (paf_filter_upload(d, text, p)) {
+        pc.on_dev = true;
+        std::vector<wga_paf_pair> pairs;
+        device_pairs(p, &d_resident_pol, &pairs);
+        for (const wga_paf_pair& q : pairs) { /* the names come from the host copy of the text */
+          uint64_t& g = sum[{std::string(text, (size_t)q.qname_off, q.qname_len), std::string(text, (size_t)q.tname_off, q.tname_len)}];
+          g += q.sum; /* wraps, as the release build does */
+          pc.pair_sum.push_back(&g);
+        }
+        recs_before += p.n_ok;
+        resident = p;
+        have_resident = true;
+        g_timer.mark("device pairs + host merge");
+      } else {
+        if (!host_records(text, line0, byte0, pc.recs)) break;
+        for (const PafRecord& r : pc.recs) sum[{r.query_name, r.target_name}] += r.target_end - r.target_start;
+        recs_before += pc.recs.size();
+      }
+      if (pc.on_dev) { /* a device piece is uploaded again for the second pass; a host piece has its records */
+        pc.text = std::move(text);
+        text = std::string();
+      }
+      pieces.push_back(std::move(pc));
+    }
     if (pending_error.empty()) { /* the reference collects before it writes: an error leaves no record */
-      std::string rows;
-      for (const PafRecord& r : all)
-        if (sum[{r.query_name, r.target_name}] >= *min_align) filter_paf_row(rows, r);
-      out.write(rows);
+      for (size_t k = 0; k < pieces.size(); k++) {
+        Piece& pc = pieces[k];
+        if (!pc.on_dev) {
+          std::string rows;
+          for (const PafRecord& r : pc.recs)
+            if (sum[{r.query_name, r.target_name}] >= *min_align) filter_paf_row(rows, r);
+          out.write(rows);
+          continue;
+        }
+        PafOnDev p = resident;
+        uint32_t* d_pol = d_resident_pol;
+        if (!(have_resident && pieces.size() == 1)) {
+          if (have_resident) d.release_to(resident.owned0);
+          have_resident = false;
+          if (!paf_filter_upload(d, pc.text, p)) fail("internal error: a PAF piece changed between the passes");
+          if (device_pairs(p, &d_pol, nullptr) != pc.pair_sum.size()) fail("internal error: a PAF piece's pairs changed between the passes");
+        }
+        std::vector<uint8_t> keep(pc.pair_sum.size() + 16, 0);
+        for (size_t j = 0; j < pc.pair_sum.size(); j++) keep[j] = *pc.pair_sum[j] >= *min_align ? 1 : 0;
+        const wga_paf_filter_params par = {0, 0, d_pol, d.upload(keep)};
+        paf_filter_write(d, p, par, false, out);
+        d.release_to(p.owned0);
+        have_resident = false;
+      }
     }
   } else {
+    const wga_paf_filter_params par = {min_block, min_query, nullptr, nullptr};
     while (next()) {
+      PafOnDev p;
+      if (paf_filter_upload(d, text, p)) {
+        paf_filter_write(d, p, par, min_block == 0 && min_query == 0, out);
+        d.release_to(p.owned0);
+        recs_before += p.n_ok;
+        continue;
+      }
+      std::vector<PafRecord> recs;
+      if (!host_records(text, line0, byte0, recs)) break;
       std::string rows;
-      for (const PafRecord& r : pin.recs)
+      for (const PafRecord& r : recs)
         if (!(r.target_end - r.target_start < min_block || r.query_length < min_query)) filter_paf_row(rows, r);
       out.write(rows);
+      recs_before += recs.size();
     }
   }
   out.close();
+  g_timer.mark("write");
   if (!pending_error.empty()) fail(pending_error);
   return leave(0);
 }

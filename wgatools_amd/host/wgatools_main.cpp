@@ -789,22 +789,34 @@ struct PafChunks {
       ahead = std::move(a);
     });
   }
+  /* the next piece as it was read, with the reader's counters in front of it, or false at the end of the input (`piece` is then
+   * left alone).  `piece` comes in as the text the caller has finished with: its buffer takes a later piece */
+  bool next_text(std::string& piece, uint64_t& lines_before, uint64_t& bytes_before) {
+    if (!started) {
+      started = true;
+      read_ahead();
+    }
+    if (!reader.joinable()) return false; /* the end was seen */
+    reader.join();
+    Ahead a = std::move(ahead);
+    if (!a.err.empty()) fail(a.err);
+    if (!a.ok) return false;
+    rd.recycle(std::move(piece));
+    piece = std::string();
+    read_ahead();
+    piece = std::move(a.piece);
+    lines_before = a.lines_before;
+    bytes_before = a.bytes_before;
+    return true;
+  }
   /* the next piece with at least one record, or false at the end of the input */
   bool next(Dev& d, PafInput& in) {
     for (;;) {
-      if (!started) {
-        started = true;
-        read_ahead();
-      }
-      if (!reader.joinable()) return false; /* the end was seen */
-      reader.join();
-      Ahead a = std::move(ahead);
-      if (!a.err.empty()) fail(a.err);
-      if (!a.ok) return false;
-      rd.recycle(std::move(in.text)); /* the piece the caller has finished with: its buffer takes a later piece */
+      uint64_t lines_before = 0, bytes_before = 0;
+      if (!next_text(in.text, lines_before, bytes_before)) return false;
+      std::string piece = std::move(in.text);
       in.text = std::string();
-      read_ahead();
-      in = paf_from_text(d, std::move(a.piece), want_tags, recs_before, a.lines_before, a.bytes_before);
+      in = paf_from_text(d, std::move(piece), want_tags, recs_before, lines_before, bytes_before);
       recs_before += in.recs.size();
       if (!in.recs.empty()) return true;
       if (in.d_text) d.release(in.d_text);
@@ -1421,6 +1433,9 @@ static int run_command(int argc, char** argv) {
         printf("\n");
       }
       return 0;
+    }
+    if (cmd == "__paf_filter_path") { /* which path `filter -f paf` takes for every piece of this file */
+      return paf_filter_paths(rest.empty() ? nullptr : &rest[0]);
     }
     if (cmd == "__parse_paf" || cmd == "__parse_maf") { /* echo the parsed records */
       std::string text = read_all(rest.empty() ? nullptr : &rest[0]);
