@@ -783,6 +783,38 @@ int wga_paf_filter(wga_ctx*, const uint8_t* d_text, uint64_t n_bytes, const wga_
                    const wga_paf_filter_params*, void* d_work, uint64_t* text_bytes, uint64_t* n_kept,
                    uint64_t* first_inexact_line, uint8_t* d_out);
 
+/* ---- K25: `filter -f chain` — the chain record writer (replaces the formatting loop of the host's cmd_filter_chain,
+ *      wgatools_amd/host/cmd_filter.inc:345-382 of the commit before it: every data line downloaded as 24 bytes and printed by
+ *      one CPU thread; in the reference chain.rs:92-100,185-204 behind the selection of tools/filter.rs:17-39,91-105) ---------
+ * d_text, d_heads[n_chains], d_lines and d_line_off[n_chains + 1] are wga_chain_split's arguments and results for a file it
+ * took (WGA_CHAIN_OK), or arrays of the same meaning: d_line_off[0] = 0, d_line_off ascending, d_line_off[n_chains] = the
+ * number of data lines (the call reads it from there), the names' spans inside d_text.  For every KEPT chain r, in input order:
+ *   chain\t<score>\t<tname>\t<tsize>\t<+|->\t<tstart>\t<tend>\t<qname>\t<qsize>\t<+|->\t<qstart>\t<qend>\t<id>
+ *   then per data line   \n<size>\t<col2>\t<col3>
+ *   then                 \n\n
+ * All numbers in canonical decimal (the score is num[0]: 1 to 15 digits for a file the splitter takes, whose f64 Display is that
+ * decimal), the names copied from d_text.  Chain r is DROPPED when (num[3] - num[2]) (wrapping) < min_block_size or num[4] <
+ * min_query_size (filter.rs:96-101: both compare with `<`).  A chain with d_line_off[r] == d_line_off[r + 1] is legal here: its
+ * text is the header and "\n\n".
+ *   d_out == NULL: the selection, the byte count of every header and data line and their places; *total_bytes and *n_kept
+ *                  (host values: the call reads d_line_off[n_chains], then both totals in one copy).
+ *   otherwise    : the text at d_out[0 .. *total_bytes); d_out may have any alignment, the caller leaves 16 bytes of slack
+ *                  behind it; no byte in front of d_out and none from d_out + *total_bytes + 16 on is touched (this
+ *                  implementation writes none outside the text).  *total_bytes and *n_kept are read as the first call left
+ *                  them; the selection and the places are the first call's (d_work), so the two calls take the same arguments.
+ * n_chains == 0: zero counts, nothing written.  WGA_E_INVALID_ARG: n_chains + data lines > 0xFFFFFFF0, a null array with
+ * n_chains > 0, a null d_work.
+ * d_work: wga_chain_filter_work_bytes(n_chains, n_data_lines) bytes of device memory, 8-byte aligned, shared by the two calls
+ * = 8 * (n_chains + N + 2 + N / 1024 + 4) with N = n_chains + n_data_lines: 8 bytes per chain (the plan) and 8 per chain and
+ * data line (the scan of the item sizes), plus the scan's partial sums. */
+typedef struct {
+  uint64_t min_block_size, min_query_size;
+} wga_chain_filter_params; /* 16 bytes */
+uint64_t wga_chain_filter_work_bytes(uint64_t n_chains, uint64_t n_data_lines);
+int wga_chain_filter(wga_ctx*, const uint8_t* d_text, uint64_t n_bytes, const wga_chain_head* d_heads, uint64_t n_chains,
+                     const uint64_t* d_lines, const uint64_t* d_line_off, const wga_chain_filter_params*, void* d_work,
+                     uint64_t* total_bytes, uint64_t* n_kept, uint8_t* d_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,81 @@
+"""`filter -f chain` on the CPU: the C-ABI entry on the emulator build of K25, and the `wgatools` host code linked against it
+(tests/emu/wgatools_emu).  Same cases as test_gpu_chain_filter.py, plus `--gpus 2` over two emulated
+devices."""
+import pytest
+
+from wgatools_amd import build
+import chain_filter_cases as cf
+
+
+@pytest.fixture(scope="module")
+def cli():
+    return build.build_cli_emu()
+
+
+@pytest.fixture(scope="module")
+def eng(emu):
+    return emu
+
+
+def test_chain_filter_abi_fill_block_edges(eng):
+    cf.check_abi_fill_block_edges(eng)
+
+
+def test_chain_filter_abi_stage_limit(eng):
+    cf.check_abi_stage_limit(eng)
+
+
+def test_chain_filter_abi_over_the_stage(eng):
+    cf.check_abi_over_the_stage(eng)
+
+
+def test_chain_filter_abi_plan_edges(eng):
+    cf.check_abi_plan_edges(eng)
+
+
+def test_chain_filter_abi_alignment(eng):
+    cf.check_abi_alignment(eng)
+
+
+def test_chain_filter_abi_thresholds(eng):
+    cf.check_abi_thresholds(eng)
+
+
+def test_chain_filter_abi_values(eng):
+    cf.check_abi_values(eng)
+
+
+def test_chain_filter_abi_hand_built_arrays(eng):
+    cf.check_abi_hand_built(eng)
+
+
+def test_chain_filter_abi_arguments(eng):
+    cf.check_abi_arguments(eng)
+
+
+def test_chain_filter_abi_count_fill_consistency(eng):
+    cf.check_abi_count_fill(eng)
+
+
+@pytest.mark.parametrize("lo", range(0, 12, 3))
+def test_chain_filter_abi_random_files(eng, lo):
+    cf.check_abi_random_files(eng, range(lo, lo + 3))
+
+
+@pytest.mark.parametrize("part", range(cf.PATH_PARTS))
+def test_chain_filter_path_selection(cli, tmp_path, part):
+    cf.check_path_selection(cli, tmp_path, part)
+
+
+@pytest.mark.parametrize("name", cf.BYTE_FILES)
+def test_chain_filter_bytes(cli, tmp_path, name):
+    cf.check_bytes(cli, tmp_path, name)
+
+
+def test_chain_filter_error_order(cli, tmp_path):
+    cf.check_error_order(cli, tmp_path)
+
+
+def test_chain_filter_over_two_devices(cli, tmp_path, monkeypatch):
+    monkeypatch.setenv("WGA_EMU_DEVICES", "2")
+    cf.check_gpus(cli, tmp_path, 2)

@@ -101,6 +101,9 @@ PROTOTYPES = {
     "wga_paf_filter_work_bytes": (C.c_uint64, [C.c_uint64]),
     "wga_paf_filter": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                  C.POINTER(C.c_uint64), vp]),
+    "wga_chain_filter_work_bytes": (C.c_uint64, [C.c_uint64, C.c_uint64]),
+    "wga_chain_filter": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp, vp, C.POINTER(C.c_uint64),
+                                   C.POINTER(C.c_uint64), vp]),
     "wga_pafcov_finalize": (C.c_int, [vp, C.c_uint32, vp, vp, vp]),
     "wga_pafpseudo_fill": (C.c_int, [vp, C.POINTER(CigarBatch), C.c_int, vp, C.c_uint64, vp, vp,
                                      vp, vp, vp, vp]),

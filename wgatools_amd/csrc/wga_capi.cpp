@@ -39,6 +39,7 @@
 #include "wga_k22_maf_rewrite.h" /* K22: filter and rename on MAF */
 #include "wga_k23_chain_split.h" /* K23: the chain line splitter */
 #include "wga_k24_paf_filter.h" /* K24: filter on PAF, the pair sums of `-a` */
+#include "wga_k25_chain_write.h" /* K25: the chain record writer of filter on chain */
 
 /* A grow-only device buffer of a context.  reserve() leaves it with room for `need` bytes: one that is too small is freed
  * behind the work of the context's stream and allocated anew with `grow` (>= need) bytes — every site has its own growth rule —,
@@ -215,7 +216,7 @@ static int ctx_scratch(wga_ctx* c, size_t bytes, void** out) {
 /* the exclusive scan of f(0 .. n - 1) into d_out[0 .. n] (the total last): the one place that launches the scan kernels */
 template <typename F>
 static int run_scan_ws(wga_ctx* c, F f, u32 n, u64* d_out /* n+1 */, u64* partial /* n/1024 + 2 */) {
-  u32 nb = (n + 1023u) / 1024u;
+  u32 nb = (u32)(((u64)n + 1023u) / 1024u); /* n may lie within 1023 of 2^32 */
   if (nb) {
     WGA_LAUNCH(k_scan_partials<F>, nb, WGA_BLOCK, c->stream, f, n, partial);
     LAUNCH_CHECK();
@@ -542,6 +543,7 @@ int wga_ctx_get_param(wga_ctx* c, const char* name, int64_t* value) {
 #include "capi_maf.inc"
 #include "capi_opwalk.inc"
 #include "capi_text.inc"
+#include "capi_chain_write.inc"
 #include "capi_pafcov.inc"
 #include "capi_pafpseudo.inc"
 #include "capi_multigpu.inc"

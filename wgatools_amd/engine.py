@@ -36,6 +36,8 @@ PAF_FILTER_PARAMS_DTYPE = np.dtype([("min_block_size", "<u8"), ("min_query_size"
                                     ("d_pair_keep", "<u8")])
 PAF_OK, PAF_SKIP, PAF_FALLBACK = 0, 1, 2
 PAF_FILTER_TILE = 8192
+# K25 (include/wga_hip.h wga_chain_filter_params)
+CHAIN_FILTER_PARAMS_DTYPE = np.dtype([("min_block_size", "<u8"), ("min_query_size", "<u8")])
 
 OP_CODES = {"M": 0, "I": 1, "D": 2, "N": 3, "S": 4, "H": 5, "P": 6, "=": 7, "X": 8}
 OP_I_CONT, OP_D_CONT, OP_OTHER = 9, 10, 11
@@ -471,6 +473,45 @@ class Engine:
         out = out if out is not None else self.empty(n + 1, np.uint64)
         self._check(self.lib.wga_chain_line_off_rebase(self.ctx, int(n), _p(line_off), _p(out)))
         return out
+
+    def chain_filter_count(self, text, n_bytes, heads, n_chains, lines, line_off, work, min_block_size=0, min_query_size=0):
+        """K25: the count call of wga_chain_filter alone, (total_bytes, n_kept); it leaves its plan and item scan in `work`"""
+        par = np.zeros(1, dtype=CHAIN_FILTER_PARAMS_DTYPE)
+        par["min_block_size"], par["min_query_size"] = int(min_block_size), int(min_query_size)
+        total, kept = C.c_uint64(0), C.c_uint64(0)
+        self._check(self.lib.wga_chain_filter(self.ctx, _p(text), int(n_bytes), _p(heads), int(n_chains), _p(lines), _p(line_off),
+                                              par.ctypes.data, _p(work), C.byref(total), C.byref(kept), None))
+        return int(total.value), int(kept.value)
+
+    def chain_filter(self, text, n_bytes, heads, n_chains, lines, line_off, min_block_size=0, min_query_size=0, work=None,
+                     n_data_lines=None, out_shift=0):
+        """K25 (chain.rs:92-100,185-204 behind filter.rs:91-105): the text of the kept chains of wga_chain_split's arrays, both
+        calls of wga_chain_filter.  Returns (text, n_kept); the 64 bytes in front of and behind the text are checked.
+        work: a device buffer to use (else one of wga_chain_filter_work_bytes, for which n_data_lines is read from line_off when
+        it is not given); out_shift: d_out starts that many bytes behind a 64-byte aligned address"""
+        n_chains = int(n_chains)
+        if work is None:
+            if n_data_lines is None:
+                n_data_lines = int(line_off.numpy()[n_chains]) if n_chains else 0
+            work = self.empty(max(int(self.lib.wga_chain_filter_work_bytes(n_chains, int(n_data_lines))), 16), np.uint8)
+        par = np.zeros(1, dtype=CHAIN_FILTER_PARAMS_DTYPE)
+        par["min_block_size"], par["min_query_size"] = int(min_block_size), int(min_query_size)
+        total, kept = C.c_uint64(0), C.c_uint64(0)
+        args = (self.ctx, _p(text), int(n_bytes), _p(heads), n_chains, _p(lines), _p(line_off), par.ctypes.data, _p(work),
+                C.byref(total), C.byref(kept))
+        self._check(self.lib.wga_chain_filter(*args, None))
+        first = (int(total.value), int(kept.value))
+        guard = 64  # bytes around the text that the fill call must leave alone
+        out = self.upload(np.full(first[0] + 2 * guard + 96, 0xA5, dtype=np.uint8))
+        lead = guard + (-out.ptr) % 64 + int(out_shift)
+        self._check(self.lib.wga_chain_filter(*args, out.ptr + lead))
+        self.sync()
+        if (int(total.value), int(kept.value)) != first:
+            raise _lib.WgaError("wga_chain_filter changed its counts in the second call")
+        got = out.numpy()
+        if not ((got[:lead] == 0xA5).all() and (got[lead + first[0]:] == 0xA5).all()):
+            raise _lib.WgaError("wga_chain_filter wrote outside d_out[0 .. total_bytes)")
+        return got[lead:lead + first[0]].tobytes(), first[1]
 
     def cigar_tokenise_spans(self, n, text, beg, end, op_cnt=None, err=None, ops=None, op_off=None):
         """device tokeniser on spans text[beg[i], end[i]) (e.g. the cg:Z: texts inside a PAF file)"""

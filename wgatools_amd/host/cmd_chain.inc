@@ -172,8 +172,13 @@ struct ChainInput {
   std::vector<uint64_t> line_off; /* n + 1 */
   std::vector<uint64_t> lines;    /* host reader, or fetch_lines(): the same array on the host (+ one line of slack) */
   bool have_lines = false;
+  /* load_chain(.., keep_on_device = true) with on_device: the text and the heads stay in HBM too (the chain writer, K25, takes
+   * them there) and no record is built on the host: recs is empty, the counts are here */
+  uint8_t* d_text = nullptr;
+  wga_chain_head* d_heads = nullptr;
+  uint64_t n_bytes = 0, n_chains = 0, n_data_lines = 0;
   uint64_t n_lines(size_t i) const { return line_off[i + 1] - line_off[i]; }
-  /* the device's data lines on the host as well, in one download: for filter's text and for the other devices of --gpus N */
+  /* the device's data lines on the host as well, in one download: for the other devices of --gpus N */
   void fetch_lines(Dev& d) {
     if (have_lines) return;
     lines.assign((size_t)(line_off.back() + 1) * 3, 0);
@@ -181,7 +186,7 @@ struct ChainInput {
     have_lines = true;
   }
 };
-ChainInput load_chain(Dev& d, const std::string* input) {
+ChainInput load_chain(Dev& d, const std::string* input, bool keep_on_device = false) {
   ChainInput in;
   std::string text = read_all(input);
   const char* force = getenv("WGA_CHAIN_READER"); /* "host": always the nom-semantics reader (measurements) */
@@ -201,6 +206,16 @@ ChainInput load_chain(Dev& d, const std::string* input) {
       in.d_lines = (uint64_t*)d.alloc((size_t)(nd + 1) * 3 * sizeof(uint64_t));
       in.d_line_off = (uint64_t*)d.alloc((size_t)(nc + 1) * sizeof(uint64_t));
       d.check(wga_chain_split(d.ctx, d_text, n_bytes, &nc, &nd, &status, &bad, d_heads, nc, in.d_lines, nd, in.d_line_off));
+      if (keep_on_device) {
+        in.d_text = d_text;
+        in.d_heads = d_heads;
+        in.n_bytes = n_bytes;
+        in.n_chains = nc;
+        in.n_data_lines = nd;
+        in.on_device = true;
+        g_timer.mark("device split");
+        return in;
+      }
       std::vector<wga_chain_head> heads((size_t)nc);
       in.line_off.resize((size_t)nc + 1);
       if (nc) d.download(heads.data(), d_heads, (size_t)nc);

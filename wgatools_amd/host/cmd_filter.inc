@@ -105,8 +105,9 @@ static int rewrite_maf(const std::string* input, const std::string& header, MafR
 /* ---- filter (tools/filter.rs, utils.rs:540-576) --------------------------------------------------------------------------------
  * MAF: K22 with the thresholds (`-a` is ignored, as in the reference).  PAF: K24 selects and copies the lines of every piece whose
  * bytes the csv writer would reproduce, and groups the name pairs of `-a`; the other pieces are re-serialised field by field on
- * the host (csv writer).  Chain is written on the host (the chain Display impls re-format scores and white space, which no
- * kernel of this engine does); a plain chain file is read on the device (ChainInput) and its data lines come back in one copy. */
+ * the host (csv writer).  Chain: a plain file is read on the device (ChainInput, K23) and written there (K25, wga_chain_filter:
+ * for a file the splitter takes the score's f64 Display is its plain decimal, the names are spans of the text, everything else
+ * is a u64); the kept text comes back once.  A file the splitter leaves to the host reader is formatted on the host as before. */
 static const char* kFilterNoQuery = "panic: a block with a single s-line has no query row (maf.rs:430 index out of bounds)";
 
 int cmd_filter_maf(const std::string* input, uint64_t min_block, uint64_t min_query, Output& out) {
@@ -342,11 +343,42 @@ int cmd_filter_paf(const std::string* input, uint64_t min_block, uint64_t min_qu
   return leave(0);
 }
 
+/* ---- filter -f chain on the device (K25) ---------------------------------------------------------------------------------------
+ * A file the chain splitter takes stays in HBM whole (text, heads, data lines, offsets); wga_chain_filter selects the chains and
+ * writes their text there, and the kept bytes leave through the pinned-buffer sink (`.gz`: deflated on the device first).  Any
+ * other input (WGA_CHAIN_READER=host, a fallback file, an empty file, 4 GiB or more) is formatted on the host from the host
+ * reader's records, the chains in front of a reader error first.  Runs on device 0 whatever --gpus says. */
+int chain_filter_path(const std::string* input) { /* `__chain_filter_path` */
+  Dev d;
+  ChainInput in = load_chain(d, input, true);
+  printf("%s\n", in.on_device ? "device" : "host");
+  return 0;
+}
+
+static int filter_chain_device(Dev& d, const ChainInput& in, uint64_t min_block, uint64_t min_query, Output& out) {
+  const wga_chain_filter_params par = {min_block, min_query};
+  void* d_work = d.alloc((size_t)wga_chain_filter_work_bytes(in.n_chains, in.n_data_lines) + 16);
+  uint64_t bytes = 0, kept = 0;
+  d.check(wga_chain_filter(d.ctx, in.d_text, in.n_bytes, in.d_heads, in.n_chains, in.d_lines, in.d_line_off, &par, d_work, &bytes,
+                           &kept, nullptr));
+  if (bytes) {
+    auto* d_out = (uint8_t*)d.alloc((size_t)bytes + 16);
+    d.check(wga_chain_filter(d.ctx, in.d_text, in.n_bytes, in.d_heads, in.n_chains, in.d_lines, in.d_line_off, &par, d_work, &bytes,
+                             &kept, d_out));
+    d.check(wga_sync(d.ctx));
+    g_timer.mark("device text");
+    stream_out(d, out, d_out, (size_t)bytes, false);
+    g_timer.mark("copy out + write");
+  }
+  out.close();
+  return leave(0);
+}
+
 int cmd_filter_chain(const std::string* input, uint64_t min_block, uint64_t min_query, Output& out) {
   std::string text;
   Dev d;
-  ChainInput in = load_chain(d, input);
-  if (in.on_device) in.fetch_lines(d); /* the text is formatted here: the data lines come back once */
+  ChainInput in = load_chain(d, input, true);
+  if (in.on_device) return filter_chain_device(d, in, min_block, min_query, out);
   const std::string& err = in.error;
   for (size_t i = 0; i < in.recs.size(); i++) {
     const ChainRecord& r = in.recs[i];
