@@ -815,6 +815,30 @@ int wga_chain_filter(wga_ctx*, const uint8_t* d_text, uint64_t n_bytes, const wg
                      const uint64_t* d_lines, const uint64_t* d_line_off, const wga_chain_filter_params*, void* d_work,
                      uint64_t* total_bytes, uint64_t* n_kept, uint8_t* d_out);
 
+/* ---- K26: `dotplot --out-format csv`, base-level — the csv row writer (replaces the row loop of the host's dotplot_rows,
+ *      wgatools_amd/host/cmd_dotplot.inc:41-58 of the commit before it: every segment downloaded as 40 bytes and printed by one
+ *      CPU thread; in the reference the csv writer of tools/dotplot.rs:208-262 over emit_baseplotdatas, cigar.rs:815-914) -----
+ * d_segs (5 u64 per segment: four numbers and the kind 0 M / 1 I / 2 D) and d_seg_off[n + 1] are wga_cigar_dotplot's result and
+ * the scan of its counts, or arrays of the same meaning: d_seg_off[0] = 0, d_seg_off ascending, equal neighbours = a record
+ * without segments, d_seg_off[n] = the number of rows N (the call reads it from there).  d_tails[d_tail_off[i] ..
+ * d_tail_off[i + 1]) is record i's TAIL, the bytes `,<ref_chro>,<query_chro>\n` as the caller's csv quoting made them: opaque
+ * bytes of any length >= 1, copied as they are.  For every segment, in order:
+ *   <s0>,<s1>,<s2>,<s3>,<M|I|D>   then its record's tail
+ * The numbers in canonical decimal.  A kind above 2 is the caller's error: its letter is `?`, nothing is indexed by it.
+ *   d_out == NULL: the byte count of every row and the rows' places (d_work); *total_bytes (a host value: the call reads
+ *                  d_seg_off[n], then the total).
+ *   otherwise    : the text at d_out[0 .. *total_bytes) with the places of the first call; d_out may have any alignment, the
+ *                  caller leaves 16 bytes of slack behind it; no byte in front of d_out and none from d_out + *total_bytes + 16
+ *                  on is touched (this implementation writes none outside the text).  *total_bytes is read as the first call
+ *                  left it, so the two calls take the same arguments.
+ * n == 0 or N == 0: total 0, nothing written.  WGA_E_INVALID_ARG: N > 0xFFFFFFF0 (refused before a segment is read), a null
+ * array with n > 0, a null d_work with N > 0.
+ * d_work: wga_dotplot_csv_work_bytes(N) bytes of device memory, 8-byte aligned, shared by the two calls
+ * = 8 * (N + 1 + N / 1024 + 4): 8 bytes per row (its size, then its place) plus the scan's partial sums. */
+uint64_t wga_dotplot_csv_work_bytes(uint64_t n_rows);
+int wga_dotplot_csv(wga_ctx*, uint32_t n, const uint64_t* d_segs, const uint64_t* d_seg_off, const uint8_t* d_tails,
+                    const uint64_t* d_tail_off, void* d_work, uint64_t* total_bytes, uint8_t* d_out);
+
 #ifdef __cplusplus
 }
 #endif

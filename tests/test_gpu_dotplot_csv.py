@@ -1,0 +1,84 @@
+"""The base-level csv rows of `dotplot` on a real GPU: the C-ABI entry (K26) and the `wgatools` binary over libwgahip.so, the
+cases of test_emu_dotplot_csv.py."""
+import os
+import pytest
+
+from wgatools_amd import build
+import dotplot_csv_cases as dc
+
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def cli():
+    if not os.path.exists(build.CLI_BIN):
+        build.build_cli()
+    return build.CLI_BIN
+
+
+@pytest.fixture(scope="module")
+def eng(gpu):
+    return gpu
+
+
+def test_dotplot_csv_abi_block_edges(eng):
+    dc.check_abi_block_edges(eng)
+
+
+def test_dotplot_csv_abi_empty_records(eng):
+    dc.check_abi_empty_records(eng)
+
+
+def test_dotplot_csv_abi_stage_limit(eng):
+    dc.check_abi_stage_limit(eng)
+
+
+def test_dotplot_csv_abi_over_the_stage(eng):
+    dc.check_abi_over_the_stage(eng)
+
+
+def test_dotplot_csv_abi_alignment(eng):
+    dc.check_abi_alignment(eng)
+
+
+def test_dotplot_csv_abi_values(eng):
+    dc.check_abi_values(eng)
+
+
+def test_dotplot_csv_abi_opaque_tails(eng):
+    dc.check_abi_opaque_tails(eng)
+
+
+def test_dotplot_csv_abi_arguments(eng):
+    dc.check_abi_arguments(eng)
+
+
+def test_dotplot_csv_abi_count_fill_consistency(eng):
+    dc.check_abi_count_fill(eng)
+
+
+@pytest.mark.parametrize("lo", range(0, 12, 3))
+def test_dotplot_csv_abi_random(eng, lo):
+    dc.check_abi_random(eng, range(lo, lo + 3))
+
+
+def test_dotplot_csv_pipeline_from_k12(eng):
+    dc.check_pipeline(eng)
+
+
+@pytest.mark.parametrize("name", [n for n, _ in dc.GOLDEN_RUNS])
+def test_dotplot_csv_cli_golden_both_writers(cli, name):
+    dc.check_golden(cli, name)
+
+
+def test_dotplot_csv_cli_quoted_names(cli, tmp_path):
+    dc.check_quoted_names(cli, tmp_path)
+
+
+def test_dotplot_csv_cli_no_segment(cli, tmp_path):
+    dc.check_no_segment(cli, tmp_path)
+
+
+def test_dotplot_csv_cli_error_leaves_nothing(cli, tmp_path):
+    dc.check_error_leaves_nothing(cli, tmp_path)

@@ -513,6 +513,40 @@ class Engine:
             raise _lib.WgaError("wga_chain_filter wrote outside d_out[0 .. total_bytes)")
         return got[lead:lead + first[0]].tobytes(), first[1]
 
+    def dotplot_csv_count(self, n, segs, seg_off, tails, tail_off, work):
+        """K26: the count call of wga_dotplot_csv alone, total_bytes; it leaves the scan of the row sizes in `work`"""
+        total = C.c_uint64(0)
+        self._check(self.lib.wga_dotplot_csv(self.ctx, int(n), _p(segs), _p(seg_off), _p(tails), _p(tail_off), _p(work),
+                                             C.byref(total), None))
+        return int(total.value)
+
+    def dotplot_csv(self, n, segs, seg_off, tails, tail_off, work=None, n_rows=None, out_shift=0):
+        """K26 (the csv rows of dotplot.rs:208-262, base-level): `<s0>,<s1>,<s2>,<s3>,<M|I|D>` and the record's tail for every
+        segment of wga_cigar_dotplot's arrays, both calls of wga_dotplot_csv.  Returns the text; the 64 bytes in front of and
+        behind it are checked.
+        work: a device buffer to use (else one of wga_dotplot_csv_work_bytes, for which n_rows is read from seg_off when it is not
+        given); out_shift: d_out starts that many bytes behind a 64-byte aligned address"""
+        n = int(n)
+        if work is None:
+            if n_rows is None:
+                n_rows = int(seg_off.numpy()[n]) if n else 0
+            work = self.empty(max(int(self.lib.wga_dotplot_csv_work_bytes(int(n_rows))), 16), np.uint8)
+        total = C.c_uint64(0)
+        args = (self.ctx, n, _p(segs), _p(seg_off), _p(tails), _p(tail_off), _p(work), C.byref(total))
+        self._check(self.lib.wga_dotplot_csv(*args, None))
+        first = int(total.value)
+        guard = 64  # bytes around the text that the fill call must leave alone
+        out = self.upload(np.full(first + 2 * guard + 96, 0xA5, dtype=np.uint8))
+        lead = guard + (-out.ptr) % 64 + int(out_shift)
+        self._check(self.lib.wga_dotplot_csv(*args, out.ptr + lead))
+        self.sync()
+        if int(total.value) != first:
+            raise _lib.WgaError("wga_dotplot_csv changed its total in the second call")
+        got = out.numpy()
+        if not ((got[:lead] == 0xA5).all() and (got[lead + first:] == 0xA5).all()):
+            raise _lib.WgaError("wga_dotplot_csv wrote outside d_out[0 .. total_bytes)")
+        return got[lead:lead + first].tobytes()
+
     def cigar_tokenise_spans(self, n, text, beg, end, op_cnt=None, err=None, ops=None, op_off=None):
         """device tokeniser on spans text[beg[i], end[i]) (e.g. the cg:Z: texts inside a PAF file)"""
         op_cnt = op_cnt if op_cnt is not None else self.empty(n, np.uint64)

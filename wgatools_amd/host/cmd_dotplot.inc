@@ -1,7 +1,8 @@
 /* cmd_dotplot.inc — part of wgatools_main.cpp (included there, inside its namespace: the commands share the device helpers, readers and
  * writers defined in front of the include). */
 /* ---- dotplot --out-format csv (tools/dotplot.rs; SURVEY.md 8f rank 4) -----------------------------------
- * base-level: segments from wga_cigar_dotplot (PAF: device tokeniser; MAF: K3 runs -> wga_maf_runs_ops);
+ * base-level: segments from wga_cigar_dotplot (PAF: device tokeniser; MAF: K3 runs -> wga_maf_runs_ops), their rows
+ * written on the device (K26) unless WGA_DOTPLOT_WRITER=host;
  * overview: one row per record, identity = matched / target_align_size from K1 / K3.  All data is generated
  * before anything is written (:208-262), so an error leaves the output empty.  The html / json outputs embed
  * the reference's Vega-Lite document and are not provided. */
@@ -21,8 +22,13 @@ struct DotRecs {
     ali.push_back(a);
   }
 };
-/* csv rows (no header line) of the records R: base-level segments from wga_cigar_dotplot over the device batch cb, or one
- * overview row per record from the counts */
+/* WGA_DOTPLOT_WRITER=host: the base-level rows are printed on the host from the downloaded segments (measurements) */
+static bool dotplot_host_writer() {
+  const char* e = getenv("WGA_DOTPLOT_WRITER");
+  return e && std::string(e) == "host";
+}
+/* csv rows (no header line) of the records R: base-level segments from wga_cigar_dotplot over the device batch cb, written as
+ * text on the device (K26, wga_dotplot_csv), or one overview row per record from the counts */
 static std::string dotplot_rows(Dev& d, bool base, bool no_identity, uint64_t cutoff, const DotRecs& R, const wga_cigar_batch& cb,
                                 const std::vector<wga_cigar_counts>& counts) {
   std::string text;
@@ -34,27 +40,50 @@ static std::string dotplot_rows(Dev& d, bool base, bool no_identity, uint64_t cu
       d.check(wga_cigar_dotplot(d.ctx, &cb, cutoff, d_ts, d_qs, d_cnt, nullptr, nullptr));
       auto* d_off = (uint64_t*)d.alloc(((size_t)n + 1) * 8);
       d.check(wga_exclusive_scan_u64(d.ctx, n, d_cnt, d_off));
-      std::vector<uint64_t> off(n + 1);
-      d.download(off.data(), d_off, n + 1);
-      auto* d_segs = (uint64_t*)d.alloc((off[n] + 1) * 5 * 8);
+      uint64_t n_rows = 0;
+      d.download(&n_rows, d_off + n, 1);
+      auto* d_segs = (uint64_t*)d.alloc((n_rows + 1) * 5 * 8);
       d.check(wga_cigar_dotplot(d.ctx, &cb, cutoff, d_ts, d_qs, nullptr, d_segs, d_off));
-      std::vector<uint64_t> segs(off[n] * 5);
-      if (off[n]) d.download(segs.data(), d_segs, off[n] * 5);
+      /* every row ends in its record's tail: the names quoted once per record, the newline */
+      std::string tails;
+      std::vector<uint64_t> tail_off(n + 1);
       for (uint32_t k = 0; k < n; k++) {
-        std::string names;
-        names.push_back(',');
-        append_csv_field(names, R.t_names[k], ',');
-        names.push_back(',');
-        append_csv_field(names, R.q_names[k], ',');
-        names.push_back('\n');
-        for (uint64_t x = off[k]; x < off[k + 1]; x++) {
-          const uint64_t* sg = &segs[5 * x];
-          for (int f = 0; f < 4; f++) {
-            append_u64(text, sg[f]);
-            text.push_back(',');
+        tail_off[k] = tails.size();
+        tails.push_back(',');
+        append_csv_field(tails, R.t_names[k], ',');
+        tails.push_back(',');
+        append_csv_field(tails, R.q_names[k], ',');
+        tails.push_back('\n');
+      }
+      tail_off[n] = tails.size();
+      if (!dotplot_host_writer() && n_rows <= 0xFFFFFFF0ull) {
+        /* K26: the rows are written where the segments are and come back as text */
+        auto* d_tails = d.upload((const uint8_t*)tails.data(), tails.size());
+        auto* d_tail_off = d.upload(tail_off);
+        void* d_work = d.alloc((size_t)wga_dotplot_csv_work_bytes(n_rows) + 16);
+        uint64_t bytes = 0;
+        d.check(wga_dotplot_csv(d.ctx, n, d_segs, d_off, d_tails, d_tail_off, d_work, &bytes, nullptr));
+        if (bytes) {
+          auto* d_out = (uint8_t*)d.alloc((size_t)bytes + 16);
+          d.check(wga_dotplot_csv(d.ctx, n, d_segs, d_off, d_tails, d_tail_off, d_work, &bytes, d_out));
+          text.resize((size_t)bytes);
+          d.download((uint8_t*)&text[0], d_out, (size_t)bytes);
+        }
+      } else {
+        std::vector<uint64_t> off(n + 1);
+        d.download(off.data(), d_off, n + 1);
+        std::vector<uint64_t> segs(n_rows * 5);
+        if (n_rows) d.download(segs.data(), d_segs, n_rows * 5);
+        for (uint32_t k = 0; k < n; k++) {
+          for (uint64_t x = off[k]; x < off[k + 1]; x++) {
+            const uint64_t* sg = &segs[5 * x];
+            for (int f = 0; f < 4; f++) {
+              append_u64(text, sg[f]);
+              text.push_back(',');
+            }
+            text.push_back("MID"[sg[4]]);
+            text.append(tails, tail_off[k], tail_off[k + 1] - tail_off[k]);
           }
-          text.push_back("MID"[sg[4]]);
-          text += names;
         }
       }
     }
@@ -166,6 +195,8 @@ int cmd_dotplot(const std::string* input, const std::string& format, const std::
   }
   if (format != "maf" && format != "paf") fail("Only support MAF and PAF format");
   const bool base = mode == "base-level";
+  /* WGA_TIMING=1 names the writer of the rows; the overview rows are always the host's */
+  const char* const rows_phase = base && !dotplot_host_writer() ? "dotplot rows (device)" : "dotplot rows (host)";
   std::string text; /* all data is generated before anything is written (dotplot.rs:208-262) */
   uint64_t n_records = 0;
   Dev d;
@@ -210,6 +241,7 @@ int cmd_dotplot(const std::string* input, const std::string& format, const std::
         }
         text += part[g];
       }
+      g_timer.mark(rows_phase);
       d.release_all();
     }
   } else {
@@ -232,9 +264,11 @@ int cmd_dotplot(const std::string* input, const std::string& format, const std::
         }
         for (const std::string& t : part) text += t;
       }
+      g_timer.mark(rows_phase);
       md.release_all();
     }
   }
+  g_timer.mark(rows_phase);
   /* the header line: base-level once a segment exists, overview once a record does */
   if (base ? !text.empty() : n_records != 0)
     text = std::string(base ? "ref_start,ref_end,query_start,query_end,cigar,ref_chro,query_chro\n"
