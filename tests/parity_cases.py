@@ -1404,8 +1404,9 @@ def check_tokeniser(eng, texts):
 # ------------------------------------------------------------------------------------------------
 # K9 pafcov BED text
 # ------------------------------------------------------------------------------------------------
-def check_pafcov_format(eng, name, cov, p0):
-    """lines "<name>\\t<pos>\\t<pos+1>\\t<count>\\n" exactly as pafcov.rs:56-60 prints them"""
+def check_pafcov_format(eng, name, cov, p0, shift=None):
+    """lines "<name>\\t<pos>\\t<pos+1>\\t<count>\\n" exactly as pafcov.rs:56-60 prints them.  With `shift` the text starts `shift`
+    bytes behind a 16-byte border of the buffer; the bytes in front of it and behind it stay as they were"""
     cov = np.asarray(cov, dtype=np.int32)
     n = len(cov)
     d_name = eng.upload(np.frombuffer(name or b"\0", dtype=np.uint8)[: max(1, len(name))])
@@ -1415,12 +1416,21 @@ def check_pafcov_format(eng, name, cov, p0):
     o = off.numpy()
     want = b"".join(b"%s\t%d\t%d\t%d\n" % (name, p0 + i, p0 + i + 1, int(np.uint32(cov[i]))) for i in range(n))
     assert int(o[n]) - int(o[0]) == len(want), (int(o[n]), len(want))
-    out = eng.empty(len(want) + 8, np.uint8).fill(0x23)
-    eng.pafcov_format(d_name, d_cov, p0, n, line_off=off, out=out)
+    lead = 0 if shift is None else 16 + shift
+    out = eng.empty(lead + len(want) + 8, np.uint8).fill(0x23)
+    assert out.ptr % 16 == 0
+    eng.pafcov_format(d_name, d_cov, p0, n, line_off=off, out=out.ptr + lead)
     got = out.numpy()
-    assert got[: len(want)].tobytes() == want
-    assert (got[len(want):] == 0x23).all()
+    assert got[lead: lead + len(want)].tobytes() == want
+    assert (got[:lead] == 0x23).all() and (got[lead + len(want):] == 0x23).all()
 
+
+def check_pafcov_format_alignment(eng):
+    """K9's stretch at every place inside a 16-byte group: 600 lines (one full block of 512 and one partial), a digit roll-over
+    of the position inside; the byte in front of the text and the one behind it are canaries"""
+    cov = np.random.default_rng(9).integers(0, 300, 600)
+    for shift in range(16):
+        check_pafcov_format(eng, b"c", cov, 999_999_700, shift=shift)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -486,6 +486,11 @@ def test_pafcov_format(emu):
     pc.check_pafcov_format(emu, b"c", rng.integers(0, 9, 512 * 3), 999_999_000)   # exactly three blocks, a digit roll-over inside
 
 
+def test_pafcov_format_alignment(emu):
+    """K9's text at all 16 alignments of the output, canaries around it (tests/parity_cases.py)"""
+    pc.check_pafcov_format_alignment(emu)
+
+
 def test_device_tokeniser_random_bytes(emu):
     """adversarial texts: digits, op letters and stray bytes in any order — the device tokeniser must agree
     with the host packer on ops, error code and error token for every one of them"""

@@ -419,6 +419,11 @@ def test_pafcov_format(gpu):
     pc.check_pafcov_format(gpu, b"none", [], 0)
 
 
+def test_pafcov_format_alignment(gpu):
+    """K9's text at all 16 alignments of the output, canaries around it (tests/parity_cases.py)"""
+    pc.check_pafcov_format_alignment(gpu)
+
+
 def test_cigar_chain(gpu):
     b = synth.make_paf_batch(57, 300, 3000, 400000)
     pc.check_cigar_chain(gpu, b["ops"], b["op_off"])

@@ -25,6 +25,7 @@
 #include "wga_k3_maf.h"        /* K3 / K4: the MAF walks */
 #include "wga_k7_paf_call.h"
 #include "wga_k8_tokenise.h"
+#include "wga_text_out.h"      /* what the text writers share: decimals, sinks, the staged stretch */
 #include "wga_k9_bed.h"
 #include "wga_k10_chain.h"
 #include "wga_k11_bridges.h"

@@ -5,7 +5,7 @@
 #ifndef WGA_K11_BRIDGES_H
 #define WGA_K11_BRIDGES_H
 
-#include "wga_k9_bed.h" /* dec_digits, dec_write, lds_text_flush */
+#include "wga_text_out.h" /* dec_digits, dec_write, lds_text_flush, csr_find_in */
 
 /* ============================================================================================ */
 /* K11: bridges between the run / data-line lists and the packed-op and CIGAR-text forms        */
@@ -15,14 +15,8 @@
  * src.size(x, r) output units (packed ops or text bytes); an exclusive scan over the elements
  * gives every element its place inside its record's output, which starts at out_off[r].  One
  * thread per element; its record is found by bisection in the CSR offsets. */
-__device__ __forceinline__ u32 csr_find_rec(const u64* __restrict__ off, u32 n, u64 x) {
-  u32 lo = 0, hi = n; /* largest r < n with off[r] <= x (records without elements are skipped) */
-  while (hi - lo > 1u) {
-    const u32 mid = lo + ((hi - lo) >> 1);
-    if (off[mid] <= x) lo = mid; else hi = mid;
-  }
-  return lo;
-}
+/* largest r < n with off[r] <= x (records without elements are skipped) */
+__device__ __forceinline__ u32 csr_find_rec(const u64* __restrict__ off, u32 n, u64 x) { return csr_find_in(off, 0u, n, x); }
 
 /* pieces of at most WGA_OP_MAX_LEN, none for 0: exactly as many as put_split writes, for every u64 (a chain data line may hold
  * 2^64 - 1: rounding up by adding first would wrap, and 2^36 pieces do not fit 32 bits) */
@@ -181,12 +175,8 @@ __global__ __launch_bounds__(256) void k_elem_fill(F f, u32 n, u32 ne, const u64
     return;
   }
   if (x >= x1) return;
-  u32 lo = r_lo, hi = r_hi + 1u; /* largest r in [r_lo, r_hi] with elem_off[r] <= x */
-  while (hi - lo > 1u) {
-    const u32 mid = lo + ((hi - lo) >> 1);
-    if (elem_off[mid] <= (u64)x) lo = mid; else hi = mid;
-  }
-  f.write((u64)x, lo, out + out_off[lo] + (esc[x] - esc[elem_off[lo]]));
+  const u32 r = csr_find_in(elem_off, r_lo, r_hi + 1u, (u64)x);
+  f.write((u64)x, r, out + out_off[r] + (esc[x] - esc[elem_off[r]]));
 }
 
 #endif /* WGA_K11_BRIDGES_H */

@@ -18,12 +18,11 @@
  *   * rows: one per column of an X run with `-s` (:570-603), one per I / D run longer than `svlen` behind an '=' / X run
  *     (:464-569), one <INV> row in front of a '-' block's chunk with `inv` (:423-440).
  * One wave per block; a chunk is three passes over its runs, 64 runs a step (boundary; the run the chunk ends in; the rows).
- * Text as K16 writes it (wga_kernels3.h): a step counts its rows' bytes, a wave scan places them, the fill pass assembles the
- * step in LDS and stores it in 16-byte groups.  Two-call protocol: bytes per block and the first bad base (noodles-vcf's parse
- * error: a REF / ALT character outside ACGTN in either case), then the text.  A block's text ends in front of the CHUNK that
- * holds its first bad base: the reference collects a chunk's records before it writes any of them (:137-141).  The fill pass
- * writes block k's bytes into [out_off[k], out_off[k + 1]) and nothing else: it leaves the chunk loop when those bytes are out,
- * in front of the first bad chunk, whose clean steps belong to no reported byte.
+ * Text as K16 writes it (wga_kernels3.h: the sinks, the row frame, the step's staged stretch).  Two-call protocol: bytes per
+ * block and the first bad base (noodles-vcf's parse error: a REF / ALT character outside ACGTN in either case), then the text.
+ * A block's text ends in front of the CHUNK that holds its first bad base: the reference collects a chunk's records before it
+ * writes any of them (:137-141).  The fill pass writes block k's bytes into [out_off[k], out_off[k + 1]) and nothing else: it
+ * leaves the chunk loop when those bytes are out, in front of the first bad chunk, whose clean steps belong to no reported byte.
  */
 #ifndef WGA_K19_MAF_CALL_H
 #define WGA_K19_MAF_CALL_H
@@ -49,32 +48,9 @@ __device__ __forceinline__ bool maf_cls_gap(u32 c) { return c == 1u || c == 2u |
 __device__ __forceinline__ bool maf_cls_adv_t(u32 c) { return c == 0u || c == 3u || c == 2u; }
 __device__ __forceinline__ bool maf_cls_adv_q(u32 c) { return c == 0u || c == 3u || c == 1u; }
 
-struct MafVcfCtx {
-  const u8 *t_name, *q_name, *trow, *qrow;
-  u32 t_name_len, q_name_len;
-  bool neg;
+struct MafVcfCtx : VcfNames {
+  const u8 *trow, *qrow;
 };
-template <class S>
-__device__ __forceinline__ void mvcf_open(S& s, const MafVcfCtx& r, u64 pos) { /* "<chro>\t<pos>\t.\t" */
-  s.str(r.t_name, r.t_name_len);
-  s.c((u8)'\t');
-  s.dec(pos);
-  vcf_lit(s, "\t.\t");
-}
-template <class S>
-__device__ __forceinline__ void mvcf_close(S& s, const MafVcfCtx& r, u64 a, u64 b, bool three) { /* "\tGT:QI\t1|1:<query>@<a>[@<b>]@<P|N>\n" */
-  vcf_lit(s, "\tGT:QI\t1|1:");
-  s.str(r.q_name, r.q_name_len);
-  s.c((u8)'@');
-  s.dec(a);
-  if (!three) {
-    s.c((u8)'@');
-    s.dec(b);
-  }
-  s.c((u8)'@');
-  s.c(r.neg ? (u8)'N' : (u8)'P');
-  s.c((u8)'\n');
-}
 /* what a lane's run asks for: kind 0 nothing, 1 the <INV> row (lane 0's extra item), 2 SNP rows, 3 INS, 4 DEL */
 struct MafVcfItem {
   u32 kind;
@@ -84,24 +60,24 @@ struct MafVcfItem {
 template <class S>
 __device__ __forceinline__ void mvcf_item(S& s, const MafVcfCtx& r, const MafVcfItem& it, u32* kind, u32* ch) {
   if (it.kind == 1u) { /* caller.rs:423-440 */
-    mvcf_open(s, r, it.t_pos + 1u);
+    vcf_row_open(s, r, it.t_pos + 1u);
     s.bases(r.trow + it.pc, 1, kind, ch);
     vcf_lit(s, "\t<INV>\t.\t.\tSVTYPE=INV;END=");
     s.dec(it.t_end);
-    mvcf_close(s, r, it.q_pos, it.q_end, false);
+    vcf_row_close(s, r, it.q_pos, it.q_end, false);
   } else if (it.kind == 2u) { /* :570-603, one row per column */
     for (u64 x = 0; x < it.len; x++) {
-      mvcf_open(s, r, it.t_pos + x + 1u);
+      vcf_row_open(s, r, it.t_pos + x + 1u);
       s.bases(r.trow + it.s0 + x, 1, kind, ch);
       s.c((u8)'\t');
       s.bases(r.qrow + it.s0 + x, 1, kind, ch);
       vcf_lit(s, "\t.\t.\t.");
-      mvcf_close(s, r, it.q_pos + x, 0, true);
+      vcf_row_close(s, r, it.q_pos + x, 0, true);
       if (*kind) return;
     }
   } else if (it.kind == 3u || it.kind == 4u) { /* :464-569 */
     const bool ins = it.kind == 3u;
-    mvcf_open(s, r, it.t_pos);
+    vcf_row_open(s, r, it.t_pos);
     s.bases(r.trow + it.pc, 1, kind, ch);
     if (!ins) s.bases(r.trow + it.s0, it.len, kind, ch);
     s.c((u8)'\t');
@@ -116,7 +92,7 @@ __device__ __forceinline__ void mvcf_item(S& s, const MafVcfCtx& r, const MafVcf
     s.dec(it.len);
     vcf_lit(s, ";END=");
     s.dec(ins ? it.t_pos : it.t_pos + it.len);
-    mvcf_close(s, r, it.q_pos, ins ? it.q_pos + it.len : it.q_pos, false);
+    vcf_row_close(s, r, it.q_pos, ins ? it.q_pos + it.len : it.q_pos, false);
   }
 }
 
@@ -285,20 +261,14 @@ __global__ __launch_bounds__(256) void k_maf_call_vcf(u32 n, const u8* __restric
         break;
       }
       if (FILL && step_bytes) { /* wave-uniform */
-        u8* const g0 = out + out_off[k] + written + chunk_bytes;
-        const u32 a = (u32)((uintptr_t)g0 & 15u);
-        const bool staged = step_bytes <= (u64)WGA_VCF_TB;
+        const TextStretch st(tbuf, WGA_VCF_TB, out + out_off[k] + written + chunk_bytes, step_bytes);
         if (cnt.n) {
           VcfEmit es;
-          es.p = (staged ? tbuf + a : g0) + (inc - cnt.n);
+          es.p = st.at(inc - cnt.n);
           if (iv.kind) mvcf_item(es, r, iv, &kind, &ch);
           if (it.kind) mvcf_item(es, r, it, &kind, &ch);
         }
-        if (staged) {
-          WGA_WAVE_SYNC();
-          lds_text_flush(tbuf, a, (u32)step_bytes, g0 - a, lane, 64u);
-          WGA_WAVE_SYNC();
-        }
+        st.flush_wave(lane);
       }
       chunk_bytes += step_bytes;
       items_before += 64u;

@@ -6,7 +6,7 @@
 #ifndef WGA_K25_CHAIN_WRITE_H
 #define WGA_K25_CHAIN_WRITE_H
 
-#include "wga_k9_bed.h"          /* dec_digits, dec_write, lds_text_flush */
+#include "wga_text_out.h"        /* the sinks, TextStretch, csr_find_in */
 #include "wga_k23_chain_split.h" /* wga_chain_head_dev */
 
 /* ============================================================================================ */
@@ -20,10 +20,11 @@
  *   plan   one thread per chain: the keep flag (filter.rs:96-101, both compare with `<`, the span wraps) and the head's byte
  *          count (0 = dropped; a kept head has at least 30 bytes), the kept chains counted by one atomicAdd per block.
  *   scan   the exclusive scan of the item sizes (ScanChainItem: an item's chain by bisection in line_off[r] + r).
- *   fill   256 consecutive items per block = one contiguous stretch of the text, whatever record borders lie inside it.  The
- *          block's threads write their items into an LDS image that mirrors the stretch's place inside its 16-byte group, and
- *          the stretch leaves in 16-byte stores (lds_text_flush).  256 line items are at most 256 x 65 bytes: that is the
- *          stage.  A block whose stretch is longer (a head with names of kilobytes) writes its items directly. */
+ *   fill   256 consecutive items per block = one contiguous stretch of the text, whatever record borders lie inside it, staged
+ *          and flushed as wga_text_out.h describes.  256 line items are at most 256 x 65 bytes: that is the stage.  A block whose
+ *          stretch is longer (a head with names of kilobytes) writes its items directly.
+ * The chain of item x is csr_find_in(line_off, lo, hi, x, true): the largest r with line_off[r] + r <= x.  The emitters run into a
+ * TextCount for the plan and the scan, into a TextPut for the fill. */
 #define WGA_CHAIN_WRITE_ITEMS 256u
 #define WGA_CHAIN_WRITE_STAGE (WGA_CHAIN_WRITE_ITEMS * 65u)
 
@@ -31,78 +32,49 @@ struct wga_chain_filter_params_dev {
   u64 min_block_size, min_query_size;
 };
 
-/* the largest r in [lo, hi) with line_off[r] + r <= x (line_off[lo] + lo <= x): the chain of item x */
-__device__ __forceinline__ u32 chain_item_rec(const u64* __restrict__ line_off, u32 lo, u32 hi, u64 x) {
-  while (hi - lo > 1u) {
-    const u32 mid = lo + ((hi - lo) >> 1);
-    if (line_off[mid] + (u64)mid <= x) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
-/* one emitter, two sinks: what ChainItemCount adds up is what ChainItemPut writes */
-struct ChainItemCount {
-  u64 n;
-  __device__ __forceinline__ void put(u8) { n++; }
-  __device__ __forceinline__ void num(u64 v) { n += dec_digits(v); }
-  __device__ __forceinline__ void span(const u8*, u32 len) { n += len; }
-};
-struct ChainItemPut {
-  u8* p; /* LDS or memory */
-  __device__ __forceinline__ void put(u8 ch) { *p++ = ch; }
-  __device__ __forceinline__ void num(u64 v) {
-    const u32 nd = dec_digits(v);
-    dec_write(p, v, nd);
-    p += nd;
-  }
-  __device__ __forceinline__ void span(const u8* src, u32 len) {
-    for (u32 k = 0; k < len; k++) p[k] = src[k];
-    p += len;
-  }
-};
 /* chain.rs:185-204: the score (1 to 15 digits for a file K23 takes: its f64 Display is the plain decimal), names as they are */
 template <typename S>
 __device__ __forceinline__ void chain_head_emit(S& s, const wga_chain_head_dev& H, const u8* __restrict__ text) {
   const char* c = "chain\t";
-  for (u32 k = 0; k < 6u; k++) s.put((u8)c[k]);
-  s.num(H.num[0]);
-  s.put((u8)'\t');
-  s.span(text + H.tname_off, H.tname_len);
-  s.put((u8)'\t');
-  s.num(H.num[1]);
-  s.put((u8)'\t');
-  s.put(H.tstrand_neg ? (u8)'-' : (u8)'+');
-  s.put((u8)'\t');
-  s.num(H.num[2]);
-  s.put((u8)'\t');
-  s.num(H.num[3]);
-  s.put((u8)'\t');
-  s.span(text + H.qname_off, H.qname_len);
-  s.put((u8)'\t');
-  s.num(H.num[4]);
-  s.put((u8)'\t');
-  s.put(H.qstrand_neg ? (u8)'-' : (u8)'+');
-  s.put((u8)'\t');
-  s.num(H.num[5]);
-  s.put((u8)'\t');
-  s.num(H.num[6]);
-  s.put((u8)'\t');
-  s.num(H.num[7]);
+  for (u32 k = 0; k < 6u; k++) s.c((u8)c[k]);
+  s.dec(H.num[0]);
+  s.c((u8)'\t');
+  s.str(text + H.tname_off, H.tname_len);
+  s.c((u8)'\t');
+  s.dec(H.num[1]);
+  s.c((u8)'\t');
+  s.c(H.tstrand_neg ? (u8)'-' : (u8)'+');
+  s.c((u8)'\t');
+  s.dec(H.num[2]);
+  s.c((u8)'\t');
+  s.dec(H.num[3]);
+  s.c((u8)'\t');
+  s.str(text + H.qname_off, H.qname_len);
+  s.c((u8)'\t');
+  s.dec(H.num[4]);
+  s.c((u8)'\t');
+  s.c(H.qstrand_neg ? (u8)'-' : (u8)'+');
+  s.c((u8)'\t');
+  s.dec(H.num[5]);
+  s.c((u8)'\t');
+  s.dec(H.num[6]);
+  s.c((u8)'\t');
+  s.dec(H.num[7]);
 }
 /* chain.rs:92-100: always three columns */
 template <typename S>
 __device__ __forceinline__ void chain_line_emit(S& s, const u64* __restrict__ v) {
-  s.put((u8)'\n');
-  s.num(v[0]);
-  s.put((u8)'\t');
-  s.num(v[1]);
-  s.put((u8)'\t');
-  s.num(v[2]);
+  s.c((u8)'\n');
+  s.dec(v[0]);
+  s.c((u8)'\t');
+  s.dec(v[1]);
+  s.c((u8)'\t');
+  s.dec(v[2]);
 }
 template <typename S>
 __device__ __forceinline__ void chain_end_emit(S& s) {
-  s.put((u8)'\n');
-  s.put((u8)'\n');
+  s.c((u8)'\n');
+  s.c((u8)'\n');
 }
 
 /* plan[r] = the bytes of chain r's head item without a chain end, 0 when the chain is dropped; *n_kept += the kept chains */
@@ -115,7 +87,7 @@ __global__ __launch_bounds__(256) void k_chain_write_plan(const u8* __restrict__
   if (r < (u64)n_chains) {
     const wga_chain_head_dev H = heads[r];
     const bool keep = !(H.num[3] - H.num[2] < P.min_block_size || H.num[4] < P.min_query_size);
-    ChainItemCount c;
+    TextCount c;
     c.n = 0;
     if (keep) chain_head_emit(c, H, text);
     plan[r] = c.n;
@@ -140,7 +112,7 @@ struct ChainItems {
     if (x == first + (u64)r) return head + (first == end ? 2u : 0u);
     const u64 l = x - (u64)r - 1u;
     if (l >= n_lines) return 0u;
-    ChainItemCount c;
+    TextCount c;
     c.n = 0;
     chain_line_emit(c, lines + 3u * l);
     return c.n + (l + 1u == end ? 2u : 0u);
@@ -148,7 +120,7 @@ struct ChainItems {
 };
 struct ScanChainItem { /* scan functor: the bytes of item x */
   ChainItems it;
-  __device__ u64 operator()(u32 x) const { return it.size((u64)x, chain_item_rec(it.line_off, 0u, it.n_chains, (u64)x)); }
+  __device__ u64 operator()(u32 x) const { return it.size((u64)x, csr_find_in(it.line_off, 0u, it.n_chains, (u64)x, true)); }
 };
 
 /* items [256 b, 256 b + 256) of n_items; isc = the exclusive scan of their sizes (isc[n_items] = the text's length).  Nothing is
@@ -163,19 +135,16 @@ __global__ __launch_bounds__(256) void k_chain_write_fill(ChainItems it, u64 n_i
   const u64 x1 = x0 + WGA_CHAIN_WRITE_ITEMS < n_items ? x0 + WGA_CHAIN_WRITE_ITEMS : n_items;
   const u64 e0 = isc[x0], e1 = isc[x1]; /* bytes in front of the block, and behind it */
   if (e1 <= e0 || e1 > total) return;   /* block-uniform: every chain of the block is dropped */
-  if (tid < 2u) s_r[tid] = chain_item_rec(it.line_off, 0u, it.n_chains, tid ? x1 - 1u : x0);
+  if (tid < 2u) s_r[tid] = csr_find_in(it.line_off, 0u, it.n_chains, tid ? x1 - 1u : x0, true);
   __syncthreads();
-  const bool staged = e1 - e0 <= (u64)WGA_CHAIN_WRITE_STAGE; /* block-uniform */
-  u8* const g0 = out + e0;
-  const u32 a = (u32)((uintptr_t)g0 & 15u);
-  u8* const tbuf = (u8*)s_buf;
+  const TextStretch st(s_buf, WGA_CHAIN_WRITE_STAGE, out + e0, e1 - e0); /* block-uniform */
   const u64 x = x0 + tid;
   if (x < x1) {
     const u64 at = isc[x], sz = isc[x + 1u] - at;
     if (sz) { /* a kept chain's item */
-      const u32 r = chain_item_rec(it.line_off, s_r[0], s_r[1] + 1u, x);
-      ChainItemPut w;
-      w.p = staged ? tbuf + a + (u32)(at - e0) : out + at;
+      const u32 r = csr_find_in(it.line_off, s_r[0], s_r[1] + 1u, x, true);
+      TextPut w;
+      w.p = st.at(at - e0);
       const u64 first = it.line_off[r], end = it.line_off[r + 1u];
       if (x == first + (u64)r) {
         chain_head_emit(w, heads[r], text);
@@ -187,9 +156,7 @@ __global__ __launch_bounds__(256) void k_chain_write_fill(ChainItems it, u64 n_i
       }
     }
   }
-  if (!staged) return;
-  __syncthreads();
-  lds_text_flush(tbuf, a, (u32)(e1 - e0), g0 - a, tid, 256u);
+  st.flush_block(tid);
 }
 
 #endif /* WGA_K25_CHAIN_WRITE_H */

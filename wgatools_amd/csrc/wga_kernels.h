@@ -20,7 +20,8 @@
  *                        '-' strand), "all dashes", or "touches a gap" (queued and assembled from
  *                        two windows under byte masks).  Raw buffer loads / stores with
  *                        out-of-range offsets as the lane predicate; no read-modify-write.
- *   (every later kernel family has a header of its own: wga_k3_maf.h ... wga_k20_maf_chunk.h.)
+ *   (every later kernel family has a header of its own: wga_k3_maf.h ... wga_k26_dotplot_csv.h; wga_text_out.h is what
+ *   the text writers among them share.)
  *
  * The same source also compiles under tests/emu/simt_emu.h for CPU-side logic tests: wga_intrin.h is the one place that
  * knows (it hands its names over to tests/emu/wga_intrin_emu.h there).

@@ -10,10 +10,9 @@
  * K7 (wga_paf_call_events) leaves the events; this kernel formats them where they lie.  One wave per record,
  * one item per lane and step: item 0 is the record's <INV> row (nothing for a '+' record), item 1 + e its event e.
  * A step counts its items' bytes (digit counts, name lengths; the REF / ALT bases are read and checked), scans
- * them over the wave and — in the fill pass — every lane writes its rows into the wave's LDS buffer at the
- * place the scan gives; the buffer mirrors the output's position inside its 16-byte group and goes out with
- * 16-byte stores (a ragged head and tail by bytes).  A step whose text does not fit the buffer (long INS / DEL
- * sequences) is written straight to the output.
+ * them over the wave and — in the fill pass — every lane writes its rows at the place the scan gives inside the
+ * step's stretch, staged in the wave's LDS buffer and flushed as wga_text_out.h describes.  A step whose text does
+ * not fit the buffer (long INS / DEL sequences) is written straight to the output.
  *
  * Errors are the reference's: a REF / ALT slice outside the fetched sequences is its slice panic
  * (caller.rs:695-696,753-754,800-801), a base outside ACGTN (any case) is noodles-vcf's parse error; the first
@@ -40,12 +39,9 @@ struct wga_vcf_err_dev { /* = wga_vcf_err */
 
 #define WGA_VCF_TB 8192u /* LDS text bytes per wave */
 
-struct VcfCount {
-  u64 n;
-  __device__ __forceinline__ void c(u8) { n++; }
-  __device__ __forceinline__ void dec(u64 v) { n += dec_digits(v); }
-  __device__ __forceinline__ void str(const u8*, u32 len) { n += len; }
-  /* bases are checked where they are counted; the first bad one is kept */
+/* the text sinks (wga_text_out.h) with REF / ALT bases: checked where they are counted (the first bad one is kept), upper-cased
+ * where they are written */
+struct VcfCount : TextCount {
   __device__ __forceinline__ void bases(const u8* p, u64 len, u32* kind, u32* ch) {
     for (u64 k = 0; k < len; k++) {
       const u8 b = p[k], u = (b >= 'a' && b <= 'z') ? (u8)(b - 32) : b;
@@ -54,18 +50,7 @@ struct VcfCount {
     n += len;
   }
 };
-struct VcfEmit {
-  u8* p;
-  __device__ __forceinline__ void c(u8 ch) { *p++ = ch; }
-  __device__ __forceinline__ void dec(u64 v) {
-    const u32 nd = dec_digits(v);
-    dec_write(p, v, nd);
-    p += nd;
-  }
-  __device__ __forceinline__ void str(const u8* s, u32 len) {
-    for (u32 k = 0; k < len; k++) p[k] = s[k];
-    p += len;
-  }
+struct VcfEmit : TextPut {
   __device__ __forceinline__ void bases(const u8* s, u64 len, u32*, u32*) {
     for (u64 k = 0; k < len; k++) {
       const u8 b = s[k];
@@ -80,18 +65,22 @@ __device__ __forceinline__ void vcf_lit(S& s, const char (&t)[N]) {
   for (u32 k = 0; k + 1u < N; k++) s.c((u8)t[k]);
 }
 
-struct VcfRecCtx {
-  const u8 *t_name, *q_name, *ts, *qs;
+/* what the frame of a row needs: K16's and K19's record contexts both start with it */
+struct VcfNames {
+  const u8 *t_name, *q_name;
   u32 t_name_len, q_name_len;
+  bool neg;
+};
+struct VcfRecCtx : VcfNames {
+  const u8 *ts, *qs;
   u64 t_start, t_end, q_start, q_end, tn, qn, svlen, nops;
   const u32* rops;
   const u64* ev; /* the record's events */
-  bool neg;
 };
 
 /* "<chro>\t<pos>\t.\t" */
 template <class S>
-__device__ __forceinline__ void vcf_row_open(S& s, const VcfRecCtx& r, u64 pos) {
+__device__ __forceinline__ void vcf_row_open(S& s, const VcfNames& r, u64 pos) {
   s.str(r.t_name, r.t_name_len);
   s.c((u8)'\t');
   s.dec(pos);
@@ -99,7 +88,7 @@ __device__ __forceinline__ void vcf_row_open(S& s, const VcfRecCtx& r, u64 pos) 
 }
 /* "\tGT:QI\t1|1:<query>@<a>[@<b>]@<P|N>\n" */
 template <class S>
-__device__ __forceinline__ void vcf_row_close(S& s, const VcfRecCtx& r, u64 a, u64 b, bool three) {
+__device__ __forceinline__ void vcf_row_close(S& s, const VcfNames& r, u64 a, u64 b, bool three) {
   vcf_lit(s, "\tGT:QI\t1|1:");
   s.str(r.q_name, r.q_name_len);
   s.c((u8)'@');
@@ -212,19 +201,13 @@ __global__ __launch_bounds__(256) void k_paf_call_vcf(u32 n, const u32* __restri
     const u64 inc = wave_incl_scan_u64(mine, lane);
     const u64 total = WGA_UNI64(__shfl((long long)inc, 63));
     if (FILL && total) { /* wave-uniform */
-      u8* const g0 = out + out_off[k] + run;
-      const u32 a = (u32)((uintptr_t)g0 & 15u);
-      const bool staged = total <= (u64)WGA_VCF_TB;
+      const TextStretch st(tbuf, WGA_VCF_TB, out + out_off[k] + run, total);
       if (mine) {
         VcfEmit es;
-        es.p = (staged ? tbuf + a : g0) + (inc - mine);
+        es.p = st.at(inc - mine);
         vcf_item(es, r, item, &kind, &ch);
       }
-      if (staged) {
-        WGA_WAVE_SYNC();
-        lds_text_flush(tbuf, a, (u32)total, g0 - a, lane, 64u);
-        WGA_WAVE_SYNC();
-      }
+      st.flush_wave(lane);
     }
     run += total;
     if (bad) {

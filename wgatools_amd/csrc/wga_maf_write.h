@@ -7,7 +7,7 @@
  *   fill    maf_fill_tile: the text in 8 KiB TILES, one per block.  Thread 0 finds the tile's lines [l0, l1] in line_off and
  *           has the command narrow the range of their OWNERS (blocks, hits: what a line is looked up in), so that the lines'
  *           own searches stay short.  The block's threads write the short fields of the tile's lines into an LDS image of the
- *           tile (MafClip drops what falls outside it; decimal fields by dec_digits / dec_write of K9; prefix and name are
+ *           tile (MafClip drops what falls outside it; decimal fields by dec_digits / dec_write; prefix and name are
  *           spans of other memory, either may straddle a tile edge), the slices are copied into the image in 16-byte groups
  *           (one unaligned 16-byte load + one aligned LDS store when a group lies inside one slice, bytes at slice ends), and
  *           the tile leaves in 16-byte stores (lds_text_flush).  A row of 10^8 columns is 12 000 tiles, spread over the grid
@@ -19,8 +19,7 @@
 #ifndef WGA_MAF_WRITE_H
 #define WGA_MAF_WRITE_H
 
-#include "wga_kernels.h"
-#include "wga_k9_bed.h" /* dec_digits, dec_write, lds_text_flush */
+#include "wga_text_out.h" /* dec_digits, dec_write, lds_text_flush */
 
 #define WGA_MAF_TILE 8192u /* bytes of text per fill block */
 /* lines one tile can meet: a line holds at least 11 bytes (the shortest, an empty name and slice and three one-digit numbers,
