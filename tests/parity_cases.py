@@ -613,6 +613,23 @@ def check_pafcov(eng, b, target_id, t_start, target_len, align=4, split=False, s
 # ------------------------------------------------------------------------------------------------
 # K6 pafpseudo
 # ------------------------------------------------------------------------------------------------
+CLASS_OF_CODE = np.array([0, 1, 2, 4, 3, 4, 4, 0, 0, 1, 2, 4, 4, 4, 4, 4])      # M I D N S H P = X, the rest of a split I / D
+CLASS_NAMES = ("mx", "i", "d", "s", "o")
+
+
+def expected_class_sums(ops, op_off):
+    """per record and class (M = X | I | D | S | everything else) the sum of the op lengths, in numpy u64"""
+    code = ops & 15
+    length = (ops >> 4).astype(np.uint64)
+    lo, hi = op_off[:-1].astype(np.int64), op_off[1:].astype(np.int64)
+    out = {}
+    for ci, name in enumerate(CLASS_NAMES):
+        v = np.where(CLASS_OF_CODE[code] == ci, length, 0).astype(np.uint64)
+        c = np.concatenate([np.zeros(1, np.uint64), np.cumsum(v, dtype=np.uint64)])
+        out[name] = c[hi] - c[lo]
+    return out
+
+
 def check_pafpseudo(eng, b, base_mode, skip=None, sums_call=True, variant=None):
     """sums_call=False: the fill without wga_cigar_class_sums in front (it then computes the tile and record sums itself
     instead of taking what the class-sums call left in the context); variant: "pseudo_variant" for this call (base mode:
@@ -628,13 +645,7 @@ def check_pafpseudo(eng, b, base_mode, skip=None, sums_call=True, variant=None):
     batch = eng.make_batch(b["ops"], b["op_off"], b["strand_neg"])
     sums = eng.cigar_class_sums(batch).numpy() if sums_call else {}
     # class sums against numpy
-    code = b["ops"] & 15
-    length = (b["ops"] >> 4).astype(np.uint64)
-    cls_of = np.array([0, 1, 2, 4, 3, 4, 4, 0, 0, 1, 2, 4, 4, 4, 4, 4])
-    for ci, name in enumerate(("mx", "i", "d", "s", "o")):
-        v = np.where(cls_of[code] == ci, length, 0).astype(np.uint64)
-        c = np.concatenate([[0], np.cumsum(v)]).astype(np.uint64)
-        exp = c[b["op_off"][1:].astype(np.int64)] - c[b["op_off"][:-1].astype(np.int64)]
+    for name, exp in expected_class_sums(b["ops"], b["op_off"]).items():
         if sums_call:
             assert (sums[name] == exp).all(), name
         else:
@@ -1238,7 +1249,8 @@ def expected_paf_call_events(ops, svlen, snp):
     return ev
 
 
-def check_paf_call_events(eng, ops, op_off, svlen, snp):
+def check_paf_call_events(eng, ops, op_off, svlen, snp, oracle=True):
+    """oracle=False: only the python restatement (records whose sequences would be as long as their ops say: gigabytes)"""
     n = len(op_off) - 1
     batch = eng.make_batch(ops, op_off, np.zeros(n, dtype=np.uint8))
     cnt = eng.paf_call_events(batch, svlen, snp)
@@ -1256,7 +1268,7 @@ def check_paf_call_events(eng, ops, op_off, svlen, snp):
         # ... and against the ORACLE (orc_call_within_var_paf, caller.rs:610-822): the event list implies exactly the
         # VCF rows it writes for the record — one SNP per base of an X op, one INS / DEL per event op, anchored at the
         # target base before it.  Records with split (>= 2^28) indels are left to the python restatement above.
-        if len(rops) and not ((rops & 15) >= 9).any() and len(rops) < 4000:
+        if oracle and len(rops) and not ((rops & 15) >= 9).any() and len(rops) < 4000:
             t_cons = int(sum(int(w) >> 4 for w in rops if (int(w) & 15) in (0, 2, 7, 8)))
             q_cons = int(sum(int(w) >> 4 for w in rops if (int(w) & 15) in (0, 1, 7, 8)))
             t_seq, q_seq = rand_seq(rng, t_cons + 1, b"ACGT"), rand_seq(rng, q_cons + 1, b"ACGT")
@@ -1672,6 +1684,7 @@ def check_dotplot(eng, ops, op_off, strands, cutoff, seed=3):
             else:
                 toks.append([ln, synth.OP_CHARS[c] if c < 9 else "B"])
         return "".join("%d%s" % (ln, ch) for ln, ch in toks)
+    top = 0
     for i in range(n):
         sl = ops[int(op_off[i]):int(op_off[i + 1])]
         if len(sl) == 0:
@@ -1681,7 +1694,10 @@ def check_dotplot(eng, ops, op_off, strands, cutoff, seed=3):
         got = sg[int(oo[i]):int(oo[i + 1])]
         assert int(cc[i]) == len(want), (i, int(cc[i]), len(want))
         assert (got == want).all(), (i, got[:4], want[:4])
+        if len(want):
+            top = max(top, int(want[:, :4].max()))
     assert (sg[int(oo[-1]):] == 0x2323232323232323).all()
+    return top       # the largest expected coordinate
 
 
 def check_dotplot_long_records(eng, mops=2):
@@ -2624,3 +2640,237 @@ def check_bgzf_deflate(eng, inflate_too=True):
     assert eng.lib.wga_bgzf_compress(eng.ctx, None, 0, None, 0, C.byref(exact), 0) == 0 and exact.value == 0
     assert rc != 0 and need.value == whole and (small.numpy() == 0x23).all()
     assert b"wga_bgzf_bound" in eng.lib.wga_last_error()
+
+
+# ------------------------------------------------------------------------------------------------
+# the op walks where sums, cutoffs and cuts leave 32 bits (K12, K7, K1, the class sums, K5)
+# ------------------------------------------------------------------------------------------------
+# An op of a packed CIGAR may be 2^28 - 1 long: 17 of them in one 256-op step (or one tile of 1 024 ops) pass 2^32.  The walks
+# add 64 lanes' lengths in 32-bit pieces — two 16-bit halves scanned on their own, or one 32-bit reduction while no lane reaches
+# 2^26 — and K7 / K12 compare a 28-bit length with a 64-bit cutoff.  Every case below asserts that its inputs really leave
+# 32 bits: an expected coordinate or sum above 2^32, a cutoff above 2^32, a continuation piece at op 256 or 512.
+WIDE_L = (1 << 28) - 1
+
+
+def _pack(p):
+    return np.array([(int(ln) << 4) | int(c) for c, ln in p], dtype=np.uint32)
+
+
+def _batch_of(recs, neg=None):
+    recs = [np.asarray(r, dtype=np.uint32) for r in recs]
+    ops = np.concatenate(recs).astype(np.uint32)
+    off = np.cumsum([0] + [len(r) for r in recs]).astype(np.uint64)
+    neg = np.zeros(len(recs), dtype=np.uint8) if neg is None else np.asarray(neg, dtype=np.uint8)
+    return dict(ops=ops, op_off=off, strand_neg=neg)
+
+
+class _small_pieces:
+    """records beyond 600 ops in pieces of 256 (the product: 16 384 / 8 192), as the neighbouring checks set them"""
+    def __init__(self, eng):
+        self.eng = eng
+
+    def __enter__(self):
+        self.eng.set_param("op_long_ops", 600)
+        self.eng.set_param("op_piece_ops", 256)
+
+    def __exit__(self, *exc):
+        self.eng.set_param("op_long_ops", 16384)
+        self.eng.set_param("op_piece_ops", 8192)
+        return False
+
+
+def check_dotplot_wide_steps(eng):
+    """K12: a step of 256 ops that advances more than 2^32 in both coordinates (the two 16-bit halves of the lane scans), as the
+    record's first step and as its second one behind an open M segment; cutoffs beyond 2^32, which a compare cut to 32 bits
+    reads as 5 and 70 — the (1, 70) ops then flip from small indels to breaks; the same with the wide step in the middle one
+    of three pieces walked by three waves (k_dotplot_pieces, k_dotplot_piece_scan)"""
+    L = WIDE_L
+    rec_a = [(7, 3)] + [(7, L), (2, L), (8, L), (1, L)] * 10 + [(7, 9), (2, 5), (7, 1)]
+    wide_b = [(7, L), (1, 70), (0, L), (2, L)] * 12
+    rec_b = [(7, 1), (1, 1)] * 150 + wide_b + [(7, 2)]
+    rec_b_long = [(7, 1), (1, 1)] * 200 + wide_b + [(7, 1), (1, 1)] * 130 + [(7, 2)]      # 709 ops: pieces of 256, the wide ops in 400 .. 447
+    cutoffs = (0, 50, 2 * L, (1 << 32) + 5, (1 << 32) + 70)
+    assert max(cutoffs) > 1 << 32 and ((1 << 32) + 5) & 0xFFFFFFFF < 70 <= ((1 << 32) + 70) & 0xFFFFFFFF
+    b = _batch_of([_pack(rec_a), _pack(rec_b)])
+    for cutoff in cutoffs:
+        top = check_dotplot(eng, b["ops"], b["op_off"], [0, 1], cutoff)
+        assert top > 1 << 32, top
+    b = _batch_of([_pack(rec_a), _pack(rec_b_long)])
+    assert len(rec_b_long) > 600 and rec_b_long[400:400 + len(wide_b)] == wide_b and 256 <= 400 and 400 + len(wide_b) <= 512
+    with _small_pieces(eng):
+        for cutoff in cutoffs:
+            top = check_dotplot(eng, b["ops"], b["op_off"], [0, 1], cutoff)
+            assert top > 1 << 32, top
+
+
+def _paf_call_border_record(at, head, follow, n_ops=700):
+    """`n_ops` ops with '=' 4 at op at - 2, `head` at op at - 1 (the last op of a 256-op step) and `follow` at op `at` (the
+    first op of the next step: lane 63 of the step in front looks at it); X and small indels around them"""
+    front = [(7, 2), (8, 1)] * ((at - 2) // 2)
+    rec = front + [(7, 4), head, follow]
+    k = 0
+    while len(rec) < n_ops:
+        rec.append(((7, 3), (2, 1), (8, 1), (1, 2))[k % 4])
+        k += 1
+    assert rec[at - 1] == head and rec[at] == follow and at % 256 == 0
+    return rec
+
+
+def check_paf_call_wide_steps(eng):
+    """K7: steps whose target and query advance pass 2^32 (the scans on 16-bit halves), cutoffs of 2^28 - 1 and 2^40 against
+    28-bit lengths, and the look across a step border: a split indel whose head is the last op of a 256-op step and whose
+    continuation piece opens the next one (a head of svlen or less is an event only because the piece follows), against the
+    same head followed by an '=' op.  Every record also runs in pieces of 256 ops, where the op behind the border belongs to
+    another wave's walk.  The records' sequences would be gigabytes: the python restatement is the reference, the oracle
+    takes copies of the border records whose split indels are short unsplit ones"""
+    L = WIDE_L
+    unit_a = [(7, L), (2, L), (1, L), (8, 2), (8, L), (1, L), (8, 1)]
+    rec_a = [(7, 3)] + unit_a * 10 + [(7, 9), (2, 5), (7, 1)]
+    wide_b = [(7, L), (1, 70), (0, L), (8, 1), (2, L)] * 12
+    rec_b = [(7, 1), (1, 1)] * 150 + wide_b + [(7, 2)]
+    rec_b_long = [(7, 1), (1, 1)] * 200 + wide_b + [(7, 1), (1, 1)] * 120 + [(7, 2)]     # 701 ops: three pieces, the wide ops in the middle one
+    assert len(rec_b_long) > 600 and rec_b_long[400:400 + len(wide_b)] == wide_b and 256 <= 400 and 400 + len(wide_b) <= 512
+    b = _batch_of([_pack(rec_a), _pack(rec_b), _pack(rec_b_long)])
+    ops, off = b["ops"], b["op_off"]
+    cases = ((0, True), (60, True), (L, False), (1 << 40, True))
+    for i in range(3):
+        want = expected_paf_call_events(ops[int(off[i]):int(off[i + 1])], 0, True)
+        assert max(t for _, t, _ in want) > 1 << 32 and max(q for _, _, q in want) > 1 << 32
+    for svlen, snp in cases:
+        check_paf_call_events(eng, ops, off, svlen, snp, oracle=False)
+    with _small_pieces(eng):
+        for svlen, snp in cases:
+            check_paf_call_events(eng, ops, off, svlen, snp, oracle=False)
+    # the step border
+    recs = [_paf_call_border_record(256, (1, L), (9, 5)),
+            _paf_call_border_record(256, (2, L), (10, 5)),
+            _paf_call_border_record(256, (1, L), (7, 1)),           # no continuation piece
+            _paf_call_border_record(512, (1, L), (9, 5)),
+            _paf_call_border_record(512, (2, L), (7, 1))]
+    b = _batch_of([_pack(r) for r in recs])
+    ops, off = b["ops"], b["op_off"]
+    for i, at in ((0, 256), (1, 256), (3, 512)):
+        assert int(ops[int(off[i]) + at]) & 15 in (9, 10) and int(ops[int(off[i]) + at - 1]) >> 4 == L
+    assert all(len(r) > 600 for r in recs)
+    for svlen in (L - 1, L, 1 << 40):
+        heads = [any(k == at - 1 for k, _, _ in expected_paf_call_events(ops[int(off[i]):int(off[i + 1])], svlen, False))
+                 for i, at in enumerate((256, 256, 256, 512, 512))]
+        # a head with a continuation piece is always an event; one without only when it is longer than svlen
+        assert heads == [True, True, svlen < L, True, svlen < L], (svlen, heads)
+        for snp in (False, True):
+            check_paf_call_events(eng, ops, off, svlen, snp, oracle=False)
+            with _small_pieces(eng):
+                check_paf_call_events(eng, ops, off, svlen, snp, oracle=False)
+    # ... and against the oracle: the same records with heads of 77 bases and an M op where the continuation piece was
+    short = [[(c, 77) if ln == L else (0, ln) if c in (9, 10) else (c, ln) for c, ln in r] for r in recs]
+    b = _batch_of([_pack(r) for r in short])
+    for svlen in (0, 76, 77):
+        check_paf_call_events(eng, b["ops"], b["op_off"], svlen, True)
+        with _small_pieces(eng):
+            check_paf_call_events(eng, b["ops"], b["op_off"], svlen, True)
+
+
+def _lane_ops(lane):
+    """the 16 ops of a 1 024-op tile that lane `lane` of K1 / the class sums holds: four consecutive ones in each quarter"""
+    return [j * 256 + 4 * lane + e for j in range(4) for e in range(4)]
+
+
+def _switch_tile(lanes, lane_sum, cut=None):
+    """1 024 ops (one record, or two cut at op `cut`) of length 1 in which the 16 ops of every lane in `lanes` add up to
+    `lane_sum`, over all of M = X I D"""
+    codes = (7, 8, 1, 2, 0, 7, 1, 2)
+    t = [(codes[k % 8], 1) for k in range(1024)]
+    for lane in lanes:
+        idx = _lane_ops(lane)
+        share = lane_sum // 16
+        for n, k in enumerate(idx):
+            t[k] = (codes[(k + lane) % 8], share + (lane_sum - 16 * share if n == 5 else 0))
+        assert sum(t[k][1] for k in idx) == lane_sum
+    return [t] if cut is None else [t[:cut], t[cut:]]
+
+
+def wide_tile_records(n_op=False, clips=False):
+    """K1 / class sums: tile 0 holds three records whose lengths pass 2^32 in every class (the third one goes on into tile 1,
+    where its wide part is the tile's first segment); tiles 2 .. 7 sit on the switch between one 32-bit reduction and two
+    16-bit halves (a lane's 16 ops reach 2^26): one lane at 2^26 - 1 and at 2^26, as one record and with the record cut
+    behind that lane's last op (the first segment takes the range-tested sums, the last what they leave of the tile's); every
+    lane at 2^26 - 1 (the wave sum 2^32 - 64, the most the 32-bit reduction can meet) and at 2^26 (2^32 exactly).
+    n_op: an N op in record 0 (stat: every segment of the tile is then measured on its own); clips: S, N and D ops of length L
+    in record 0, so that all five classes of the class sums pass 2^32 inside tile 0"""
+    L = WIDE_L
+    r0 = [(7, 3)] + [(7, L), (2, L), (8, L), (1, L), (0, L)] * 8
+    if n_op:
+        r0 += [(3, 7)]
+    if clips:
+        r0 += [(4, L)] * 17 + [(3, L)] * 17 + [(2, L)] * 10
+    r0 += [(7, 9)]
+    r1 = [(8, L)] * 20 + [(1, L)] * 20 + [(7, 5)]
+    r2 = [(7, 4), (1, 2)] * 600 + [(2, L)] * 40
+    recs, neg = [r0, r1, r2], [0, 1, 0]
+    used = sum(len(r) for r in recs)
+    assert len(r0) + len(r1) < 1024 < used - 40 and used < 2048     # r2's D ops open tile 1
+    recs.append([(7, 1), (8, 1), (1, 1)] * ((2048 - used) // 3) + [(7, 1)] * ((2048 - used) % 3))
+    neg.append(1)
+    for lanes, s, cut in (([37], (1 << 26) - 1, None), ([37], 1 << 26, None), ([37], (1 << 26) - 1, 920), ([37], 1 << 26, 920),
+                          (range(64), (1 << 26) - 1, None), (range(64), 1 << 26, None)):
+        for r in _switch_tile(lanes, s, cut):
+            neg.append(len(recs) & 1)
+            recs.append(r)
+    assert max(_lane_ops(37)) < 920
+    recs.append([(7, 30), (2, 1), (8, 2)] * 20)                      # a last, partial tile
+    neg.append(0)
+    b = _batch_of([_pack(r) for r in recs], neg)
+    assert int(b["op_off"][4]) == 2048 and (len(b["ops"]) - 60) % 1024 == 0
+    return b
+
+
+def check_stat_wide_tiles(eng):
+    """K1: tiles whose wave sums pass 2^32 in every counter, the switch to the sums on 16-bit halves at a lane sum of 2^26,
+    and the wide tile with an op outside M = X I D in it (see wide_tile_records)"""
+    b = wide_tile_records()
+    counts, _ = check_stat(eng, b)
+    c = counts.numpy().view(np.uint64).reshape(-1, 11)
+    # the M = X bases of record 0, the X and the I bases of record 1 ('-'), the D bases of record 2; the record whose 64 lanes
+    # hold 2^26 bases each
+    wide = [int(c[0][0]) + int(c[0][1]), int(c[1][1]), int(c[1][7]), int(c[2][5])]
+    assert min(wide) > 1 << 32, wide
+    assert sum(int(c[11][k]) for k in (0, 1, 3, 5, 7, 9)) == 1 << 32, c[11]
+    assert int(c.sum(axis=0, dtype=np.uint64).max()) > 1 << 33
+    bn = wide_tile_records(n_op=True)
+    _, diag = check_stat(eng, bn)
+    assert int(diag.numpy()["bad_op_idx"][0]) == 41 and int(bn["ops"][41]) == (7 << 4) | 3
+
+
+def check_class_sums_wide_tiles(eng):
+    """the class sums in front of K6 / K5 on wide_tile_records with S, N and further D ops of 2^28 - 1 in tile 0: all five
+    classes pass 2^32 inside one tile.  No fill call: the rows would be 2^32 bytes"""
+    b = wide_tile_records(clips=True)
+    batch = eng.make_batch(b["ops"], b["op_off"], b["strand_neg"])
+    sums = eng.cigar_class_sums(batch).numpy()
+    tile0 = expected_class_sums(b["ops"][:1024], np.array([0, 1024], dtype=np.uint64))
+    for name, exp in expected_class_sums(b["ops"], b["op_off"]).items():
+        assert int(tile0[name][0]) > 1 << 32, (name, tile0[name])
+        assert (sums[name] == exp).all(), (name, np.flatnonzero(sums[name] != exp)[:5])
+
+
+def check_pafcov_look_back_wide(eng):
+    """K5's look-back: a record whose first tile (1 024 ops) advances 2^32 + 1000 bases, a tile of zero-length ops, eighteen
+    tiles of I ops, and then — far outside the LDS hand-over inside a block of four tiles — the ops that count: their true
+    positions lie beyond the target, so nothing of them is marked; a look-back sum whose high word is lost marks counters from
+    about 1 020 on.  With cov_spin_limit 0 the look-back adds up the ops itself.  Which of the two ways a run with the
+    default limit took (the published tile sums, or the ops after too many polls) cannot be seen from outside"""
+    L = WIDE_L
+    first = [(7, 10)] + [(3, L)] * 16 + [(3, 16 + 1000 - 10)] + [(3, 0)] * (2048 - 18)
+    rec = first + [(1, 1)] * (2048 * 9 + 5) + [(7, 5), (8, 1), (2, 3)] * 300
+    assert len(first) == 2048 and sum(ln for c, ln in first[:1024]) == (1 << 32) + 1000
+    assert (len(rec) - 900) // 1024 >= 20                         # the counting ops: twenty tiles behind the wide one
+    b = _batch_of([_pack(rec), _pack([(7, 40), (8, 1)] * 30), _pack([(7, 30), (2, 2), (0, 7)] * 20)])
+    keep = eng.get_param("cov_spin_limit")
+    try:
+        for spin in (keep, 0):
+            eng.set_param("cov_spin_limit", spin)
+            for split in (False, True):
+                got = check_pafcov(eng, b, [0, 0, 0], [20, 300, 30000], [50000], split=split)
+                assert (got[:30] == [0] * 20 + [1] * 10).all() and not got[1600:30000].any()
+    finally:
+        eng.set_param("cov_spin_limit", keep)

@@ -452,6 +452,27 @@ def test_dotplot_long_records_in_pieces(emu):
     pc.check_dotplot_long_records(emu, mops=0)
 
 
+# sums, cutoffs and cuts that leave 32 bits (tests/parity_cases.py, the section of that name)
+def test_dotplot_wide_steps(emu):
+    pc.check_dotplot_wide_steps(emu)
+
+
+def test_paf_call_wide_steps(emu):
+    pc.check_paf_call_wide_steps(emu)
+
+
+def test_stat_wide_tiles(emu):
+    pc.check_stat_wide_tiles(emu)
+
+
+def test_class_sums_wide_tiles(emu):
+    pc.check_class_sums_wide_tiles(emu)
+
+
+def test_pafcov_look_back_wide(emu):
+    pc.check_pafcov_look_back_wide(emu)
+
+
 def test_piece_table_kept_or_rebuilt(emu):
     pc.check_piece_table_rebuild(emu)
 

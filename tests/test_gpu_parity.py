@@ -372,6 +372,27 @@ def test_dotplot_long_records_in_pieces(gpu):
     pc.check_dotplot_long_records(gpu, mops=2)
 
 
+# sums, cutoffs and cuts that leave 32 bits (tests/parity_cases.py, the section of that name)
+def test_dotplot_wide_steps(gpu):
+    pc.check_dotplot_wide_steps(gpu)
+
+
+def test_paf_call_wide_steps(gpu):
+    pc.check_paf_call_wide_steps(gpu)
+
+
+def test_stat_wide_tiles(gpu):
+    pc.check_stat_wide_tiles(gpu)
+
+
+def test_class_sums_wide_tiles(gpu):
+    pc.check_class_sums_wide_tiles(gpu)
+
+
+def test_pafcov_look_back_wide(gpu):
+    pc.check_pafcov_look_back_wide(gpu)
+
+
 def test_piece_table_kept_or_rebuilt(gpu):
     pc.check_piece_table_rebuild(gpu)
 
