@@ -839,6 +839,39 @@ uint64_t wga_dotplot_csv_work_bytes(uint64_t n_rows);
 int wga_dotplot_csv(wga_ctx*, uint32_t n, const uint64_t* d_segs, const uint64_t* d_seg_off, const uint8_t* d_tails,
                     const uint64_t* d_tail_off, void* d_work, uint64_t* total_bytes, uint8_t* d_out);
 
+/* ---- K27: `chain2paf` — the PAF record writer (replaces the record loop of the host's chain2paf_range,
+ *      wgatools_amd/host/cmd_chain.inc: every head downloaded, the lines turned into packed ops for K1's two sums, twelve columns
+ *      per record printed by one CPU thread and scattered around the CIGAR text; in the reference convert2paf chain.rs:430-452
+ *      over parse_chain_to_cigar cigar.rs:554-627, written by the csv writer of converter.rs:391-416) ----------------------------
+ * d_text, d_heads[n_chains], d_lines and d_line_off[n_chains + 1] are wga_chain_split's arguments and results for a file it
+ * took (WGA_CHAIN_OK), or arrays of the same meaning: d_line_off[0] = 0, d_line_off ascending, d_line_off[n_chains] = the
+ * number of data lines (the call reads it from there), the names' spans inside d_text[0 .. n_bytes).  For every chain r, in
+ * input order, one record:
+ *   <qname>\t<qsize>\t<qstart>\t<qend>\t<+|->\t<tname>\t<tsize>\t<tstart>\t<tend>\t<matches>\t<block_length>\t255\tcg:Z:
+ *   then per data line   <size>M   <col3>I when col3 != 0   <col2>D when col2 != 0      ("0M" for a size of 0)
+ *   then                 \n
+ * The numbers are num[4], num[5], num[6] and num[1], num[2], num[3] unchanged, in canonical decimal; the strand is the query's
+ * (the target's is not printed).  matches = the sum of the chain's sizes, block_length = matches + the sum of its 2nd columns,
+ * both mod 2^64 (mismatch is 0; a deletion counts once whichever strand books it).  A name is written as the csv writer with a
+ * tab delimiter and QuoteStyle::Necessary writes it: as it is, unless it holds a tab, a quote, CR or LF (a name the splitter
+ * takes can only hold the quote); then between quotes with every quote inside doubled.  A chain with d_line_off[r] ==
+ * d_line_off[r + 1] is legal here: its record ends in "cg:Z:\n".
+ *   d_out == NULL: the sums, the byte count of every head and data line and their places (d_work); *total_bytes (a host value:
+ *                  the call reads d_line_off[n_chains], then the total).
+ *   otherwise    : the text at d_out[0 .. *total_bytes) with the sums and places of the first call; d_out may have any
+ *                  alignment, the caller leaves 16 bytes of slack behind it; no byte in front of d_out and none from d_out +
+ *                  *total_bytes + 16 on is touched (this implementation writes none outside the text).  *total_bytes is read as
+ *                  the first call left it, so the two calls take the same arguments.
+ * n_chains == 0: total 0, nothing written.  WGA_E_INVALID_ARG: n_chains + data lines > 0xFFFFFFF0 (refused before anything is
+ * read beyond d_line_off[n_chains]), a null array with n_chains > 0, a null d_work.
+ * d_work: wga_chain2paf_work_bytes(n_chains, n_data_lines) bytes of device memory, 8-byte aligned, shared by the two calls
+ * = 8 * (3 C + N + 1 + 2 (L + 1) + N / 1024 + 4) with C = n_chains, L = n_data_lines, N = C + L: 24 bytes per chain (the head's
+ * byte count and the two sums), 8 per chain and data line (the scan of the item sizes), 16 per data line (the wrapping scans of
+ * the sizes and of the 2nd columns), plus the scans' partial sums. */
+uint64_t wga_chain2paf_work_bytes(uint64_t n_chains, uint64_t n_data_lines);
+int wga_chain2paf(wga_ctx*, const uint8_t* d_text, uint64_t n_bytes, const wga_chain_head* d_heads, uint64_t n_chains,
+                  const uint64_t* d_lines, const uint64_t* d_line_off, void* d_work, uint64_t* total_bytes, uint8_t* d_out);
+
 #ifdef __cplusplus
 }
 #endif

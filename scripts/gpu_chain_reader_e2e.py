@@ -1,6 +1,7 @@
 """The chain reader file to file: `wgatools chain2paf` on a synthetic chain file of N chains with a mean of 30 data lines (a few
-hundred MB at the default N), once with the default reader (K23, wga_chain_split) and once with WGA_CHAIN_READER=host (the
-nom-semantics host reader, unchanged), both under WGA_TIMING=1.  One process at a time, each under its own time limit; a step
+hundred MB at the default N), once with the default reader (K23, wga_chain_split; its arrays stay on the device, where K27 writes
+the records) and once with WGA_CHAIN_READER=host (the nom-semantics host reader and the host's records, unchanged), both under
+WGA_TIMING=1.  One process at a time, each under its own time limit; a step
 that fails ends the script.  The two outputs must be equal; both phase lines and wall times go to
 profiles/r07_chain_reader_e2e.txt.  Without a visible MI355X the file says so and holds no figure.
 Usage: python scripts/gpu_chain_reader_e2e.py [N_CHAINS] [WORKDIR]      (default 1 500 000 chains, a temporary directory)"""

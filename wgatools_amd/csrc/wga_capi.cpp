@@ -42,6 +42,7 @@
 #include "wga_k24_paf_filter.h" /* K24: filter on PAF, the pair sums of `-a` */
 #include "wga_k25_chain_write.h" /* K25: the chain record writer of filter on chain */
 #include "wga_k26_dotplot_csv.h" /* K26: the base-level csv rows of dotplot */
+#include "wga_k27_chain2paf.h" /* K27: the PAF record writer of chain2paf */
 
 /* A grow-only device buffer of a context.  reserve() leaves it with room for `need` bytes: one that is too small is freed
  * behind the work of the context's stream and allocated anew with `grow` (>= need) bytes — every site has its own growth rule —,
@@ -546,6 +547,7 @@ int wga_ctx_get_param(wga_ctx* c, const char* name, int64_t* value) {
 #include "capi_opwalk.inc"
 #include "capi_text.inc"
 #include "capi_chain_write.inc"
+#include "capi_chain2paf.inc"
 #include "capi_dotplot_csv.inc"
 #include "capi_pafcov.inc"
 #include "capi_pafpseudo.inc"

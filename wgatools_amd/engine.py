@@ -513,6 +513,39 @@ class Engine:
             raise _lib.WgaError("wga_chain_filter wrote outside d_out[0 .. total_bytes)")
         return got[lead:lead + first[0]].tobytes(), first[1]
 
+    def chain2paf_count(self, text, n_bytes, heads, n_chains, lines, line_off, work):
+        """K27: the count call of wga_chain2paf alone, total_bytes; it leaves its sums, plan and item scan in `work`"""
+        total = C.c_uint64(0)
+        self._check(self.lib.wga_chain2paf(self.ctx, _p(text), int(n_bytes), _p(heads), int(n_chains), _p(lines), _p(line_off),
+                                           _p(work), C.byref(total), None))
+        return int(total.value)
+
+    def chain2paf(self, text, n_bytes, heads, n_chains, lines, line_off, work=None, n_data_lines=None, out_shift=0):
+        """K27 (chain.rs:430-452 over cigar.rs:554-627): the PAF records of wga_chain_split's arrays, both calls of wga_chain2paf.
+        Returns the text; the 64 bytes in front of and behind it are checked.
+        work: a device buffer to use (else one of wga_chain2paf_work_bytes, for which n_data_lines is read from line_off when it is
+        not given); out_shift: d_out starts that many bytes behind a 64-byte aligned address"""
+        n_chains = int(n_chains)
+        if work is None:
+            if n_data_lines is None:
+                n_data_lines = int(line_off.numpy()[n_chains]) if n_chains else 0
+            work = self.empty(max(int(self.lib.wga_chain2paf_work_bytes(n_chains, int(n_data_lines))), 16), np.uint8)
+        total = C.c_uint64(0)
+        args = (self.ctx, _p(text), int(n_bytes), _p(heads), n_chains, _p(lines), _p(line_off), _p(work), C.byref(total))
+        self._check(self.lib.wga_chain2paf(*args, None))
+        first = int(total.value)
+        guard = 64  # bytes around the text that the fill call must leave alone
+        out = self.upload(np.full(first + 2 * guard + 96, 0xA5, dtype=np.uint8))
+        lead = guard + (-out.ptr) % 64 + int(out_shift)
+        self._check(self.lib.wga_chain2paf(*args, out.ptr + lead))
+        self.sync()
+        if int(total.value) != first:
+            raise _lib.WgaError("wga_chain2paf changed its total in the second call")
+        got = out.numpy()
+        if not ((got[:lead] == 0xA5).all() and (got[lead + first:] == 0xA5).all()):
+            raise _lib.WgaError("wga_chain2paf wrote outside d_out[0 .. total_bytes)")
+        return got[lead:lead + first].tobytes()
+
     def dotplot_csv_count(self, n, segs, seg_off, tails, tail_off, work):
         """K26: the count call of wga_dotplot_csv alone, total_bytes; it leaves the scan of the row sizes in `work`"""
         total = C.c_uint64(0)

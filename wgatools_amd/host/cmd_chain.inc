@@ -186,6 +186,26 @@ struct ChainInput {
     have_lines = true;
   }
 };
+/* the splitter's heads as the host's records (without their lines) */
+static void chain_records_of_heads(const std::vector<wga_chain_head>& heads, const std::string& text, std::vector<ChainRecord>& recs) {
+  recs.reserve(heads.size());
+  for (const wga_chain_head& h : heads) {
+    ChainRecord r;
+    r.score = (double)h.num[0]; /* at most 15 digits: exact */
+    r.target_name.assign(text, (size_t)h.tname_off, h.tname_len);
+    r.target_size = h.num[1];
+    r.target_start = h.num[2];
+    r.target_end = h.num[3];
+    r.query_name.assign(text, (size_t)h.qname_off, h.qname_len);
+    r.query_size = h.num[4];
+    r.query_start = h.num[5];
+    r.query_end = h.num[6];
+    r.chain_id = h.num[7];
+    r.target_neg = h.tstrand_neg != 0;
+    r.query_neg = h.qstrand_neg != 0;
+    recs.push_back(std::move(r));
+  }
+}
 ChainInput load_chain(Dev& d, const std::string* input, bool keep_on_device = false) {
   ChainInput in;
   std::string text = read_all(input);
@@ -222,23 +242,7 @@ ChainInput load_chain(Dev& d, const std::string* input, bool keep_on_device = fa
       d.download(in.line_off.data(), in.d_line_off, (size_t)nc + 1);
       d.release(d_heads);
       d.release(d_text);
-      in.recs.reserve((size_t)nc);
-      for (const wga_chain_head& h : heads) {
-        ChainRecord r;
-        r.score = (double)h.num[0]; /* at most 15 digits: exact */
-        r.target_name.assign(text, (size_t)h.tname_off, h.tname_len);
-        r.target_size = h.num[1];
-        r.target_start = h.num[2];
-        r.target_end = h.num[3];
-        r.query_name.assign(text, (size_t)h.qname_off, h.qname_len);
-        r.query_size = h.num[4];
-        r.query_start = h.num[5];
-        r.query_end = h.num[6];
-        r.chain_id = h.num[7];
-        r.target_neg = h.tstrand_neg != 0;
-        r.query_neg = h.qstrand_neg != 0;
-        in.recs.push_back(std::move(r));
-      }
+      chain_records_of_heads(heads, text, in.recs);
       in.on_device = true;
       g_timer.mark("device split + host records");
       return in;
@@ -528,9 +532,72 @@ static void chain2paf_range(Dev& d, const ChainInput& in, bool in_place, size_t 
   }
 }
 
+/* ---- chain2paf on the device (K27) ------------------------------------------------------------------------------------------
+ * A file the chain splitter takes stays in HBM whole (text, heads, data lines, offsets); wga_chain2paf sums, formats and places
+ * every record there, and the bytes leave through the pinned-buffer sink (`.gz`: deflated on the device first).  No record is
+ * built on the host.  Everything else goes through chain2paf_range: a file the host reader takes, WGA_CHAIN_READER=host,
+ * --gpus N > 1, more than 0xFFFFFFF0 chains and data lines, data lines of more than three packed ops each (below),
+ * WGA_CHAIN2PAF_WRITER=host (measurements). */
+static bool chain2paf_device_wanted() {
+  const char* w = getenv("WGA_CHAIN2PAF_WRITER");
+  return g_gpus == 1 && !(w && strcmp(w, "host") == 0);
+}
+/* ... and a file whose data lines need more packed ops than three per line (a value of 2^28 or more is walked in pieces, 2^64 - 1
+ * in 2^36 of them): chain2paf_range counts and allocates those ops, and the command keeps what that path does with such a file,
+ * the error of an allocation the device cannot make included.  The count is chain_device_batch's first step. */
+static bool chain2paf_device_takes(Dev& d, const ChainInput& in) {
+  if (!in.on_device || !in.d_text || in.n_chains + in.n_data_lines > 0xFFFFFFF0ull) return false;
+  if (in.n_chains == 0) return true;
+  const uint32_t n = (uint32_t)in.n_chains;
+  auto* d_cnt = (uint64_t*)d.alloc((size_t)n * 8);
+  auto* d_ooff = (uint64_t*)d.alloc(((size_t)n + 1) * 8);
+  d.check(wga_chain_lines_ops(d.ctx, n, in.n_data_lines, in.d_lines, in.d_line_off, d_cnt, nullptr, nullptr));
+  d.check(wga_exclusive_scan_u64(d.ctx, n, d_cnt, d_ooff));
+  uint64_t n_ops = 0;
+  d.download(&n_ops, d_ooff + n, 1);
+  d.release(d_ooff);
+  d.release(d_cnt);
+  return n_ops <= 3 * in.n_data_lines;
+}
+/* a file that was kept on the device for a writer that does not take it after all: the host's records and offsets, as
+ * load_chain(.., false) leaves them */
+static void chain_host_records(Dev& d, ChainInput& in) {
+  std::string text((size_t)in.n_bytes, '\0');
+  std::vector<wga_chain_head> heads((size_t)in.n_chains);
+  in.line_off.resize((size_t)in.n_chains + 1);
+  if (in.n_bytes) d.download((uint8_t*)&text[0], in.d_text, (size_t)in.n_bytes);
+  if (in.n_chains) d.download(heads.data(), in.d_heads, (size_t)in.n_chains);
+  d.download(in.line_off.data(), in.d_line_off, (size_t)in.n_chains + 1);
+  chain_records_of_heads(heads, text, in.recs);
+}
+int chain2paf_path(const std::string* input) { /* `__chain2paf_path` */
+  Dev d;
+  const bool want = chain2paf_device_wanted();
+  ChainInput in = load_chain(d, input, want);
+  printf("%s\n", want && chain2paf_device_takes(d, in) ? "device" : "host");
+  return 0;
+}
+
 int cmd_chain2paf(const std::string* input, Output& out) {
   Dev d;
-  ChainInput in = load_chain(d, input);
+  const bool want = chain2paf_device_wanted();
+  ChainInput in = load_chain(d, input, want);
+  if (want && chain2paf_device_takes(d, in)) { /* all records are made before the first byte is written, like the host path */
+    if (in.n_chains) {
+      void* d_work = d.alloc((size_t)wga_chain2paf_work_bytes(in.n_chains, in.n_data_lines) + 16);
+      uint64_t bytes = 0;
+      d.check(wga_chain2paf(d.ctx, in.d_text, in.n_bytes, in.d_heads, in.n_chains, in.d_lines, in.d_line_off, d_work, &bytes, nullptr));
+      auto* d_out = (uint8_t*)d.alloc((size_t)bytes + 16);
+      d.check(wga_chain2paf(d.ctx, in.d_text, in.n_bytes, in.d_heads, in.n_chains, in.d_lines, in.d_line_off, d_work, &bytes, d_out));
+      d.check(wga_sync(d.ctx));
+      g_timer.mark("chain2paf records (device)");
+      stream_out(d, out, d_out, (size_t)bytes, false);
+      g_timer.mark("copy out + write");
+    }
+    out.close();
+    return leave(0);
+  }
+  if (in.on_device && in.d_text) chain_host_records(d, in);
   const std::vector<ChainRecord>& recs = in.recs;
   if (!in.error.empty()) {
     out.close();
@@ -538,8 +605,12 @@ int cmd_chain2paf(const std::string* input, Output& out) {
   }
   if (g_gpus == 1 || recs.size() < 2) {
     if (!recs.empty())
-      chain2paf_range(d, in, true, 0, recs.size(),
-                      [&](Dev& dg, const uint8_t* d_out, size_t bytes) { stream_out(dg, out, d_out, bytes); });
+      chain2paf_range(d, in, true, 0, recs.size(), [&](Dev& dg, const uint8_t* d_out, size_t bytes) {
+        dg.check(wga_sync(dg.ctx));
+        g_timer.mark("chain2paf records (host)");
+        stream_out(dg, out, d_out, bytes, false);
+        g_timer.mark("copy out + write");
+      });
   } else { /* --gpus N: the chains in contiguous ranges over the devices, the rows meet in input order */
     const int ng = g_gpus;
     const size_t n = recs.size();
@@ -560,6 +631,7 @@ int cmd_chain2paf(const std::string* input, Output& out) {
         if (bytes) dd.download((uint8_t*)&part[g][at], d_out, bytes);
       });
     });
+    g_timer.mark("chain2paf records (host)");
     for (const std::string& t : part) out.write(t);
   }
   out.close();

@@ -1440,6 +1440,9 @@ static int run_command(int argc, char** argv) {
     if (cmd == "__chain_filter_path") { /* which path `filter -f chain` takes for this file */
       return chain_filter_path(rest.empty() ? nullptr : &rest[0]);
     }
+    if (cmd == "__chain2paf_path") { /* which path `chain2paf` takes for this file */
+      return chain2paf_path(rest.empty() ? nullptr : &rest[0]);
+    }
     if (cmd == "__parse_paf" || cmd == "__parse_maf") { /* echo the parsed records */
       std::string text = read_all(rest.empty() ? nullptr : &rest[0]);
       if (cmd == "__parse_paf") {
