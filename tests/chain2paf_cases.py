@@ -12,6 +12,7 @@ import numpy as np
 
 import chain2paf_ref as ref
 import chain_split_cases as cs
+import text_items_cases as ti
 from chain_filter_cases import Split, chain, head, lines
 
 U64 = (1 << 64) - 1
@@ -204,6 +205,31 @@ def check_abi_arguments(eng):
     assert raw(eng, sp, d_off=eng.upload(np.array([0, 3, U64], dtype=np.uint64))) == E_INVALID_ARG
     assert int(eng.lib.wga_chain2paf_work_bytes(0, 0)) >= 8
     assert int(eng.lib.wga_chain2paf_work_bytes(1000, 30000)) == 8 * (3 * 1000 + 31000 + 1 + 2 * 30001 + 31000 // 1024 + 4)
+
+
+def item_stream(eng):
+    """one chain of 300 data lines and one of 298: 600 items, three blocks of the fill.  The scan of the item sizes stands behind
+    the plan and the sums in d_work, at word 3 n_chains (capi_chain2paf.inc)"""
+    data = chain(300) + chain(298, 1, tname=b"second")
+    sp = Split(eng, data)
+    work = eng.empty(int(eng.lib.wga_chain2paf_work_bytes(sp.nc, sp.nd)), np.uint8)
+    want = ref.chain2paf_ref(sp.heads, sp.triples, sp.off, data)
+    assert eng.chain2paf_count(*sp.args(), work) == len(want)
+
+    def fill(total_bytes, d_out):
+        tot = C.c_uint64(total_bytes)
+        assert eng.lib.wga_chain2paf(eng.ctx, sp.d_text.ptr, len(data), sp.d_heads.ptr, sp.nc, sp.d_lines.ptr, sp.d_off.ptr, work.ptr,
+                                     C.byref(tot), d_out) == 0
+        assert tot.value == total_bytes
+    return ti.Stream(eng, work, 3 * sp.nc, sp.nc + sp.nd, want, fill)
+
+
+def check_abi_fill_short_total(eng):
+    ti.check_short_total(item_stream(eng))
+
+
+def check_abi_fill_scan_one_off(eng):
+    ti.check_scan_one_off(item_stream(eng), size_checked=False)
 
 
 def random_file(seed):

@@ -11,6 +11,7 @@ import numpy as np
 import chain_filter_ref as ref
 import chain_split_cases as cs
 import maf_rewrite_ref as mr
+import text_items_cases as ti
 from wgatools_amd import _lib
 from wgatools_amd.engine import CHAIN_FILTER_PARAMS_DTYPE, CHAIN_HEAD_DTYPE, CHAIN_OK
 
@@ -230,6 +231,33 @@ def check_abi_count_fill(eng):
     assert eng.chain_filter(*sp.args(), 81, 0, work=work) == want[81]
     assert eng.chain_filter(*sp.args(), 0, 0, work=work) == want[0]
     assert want[81] == (b"", 0) and want[0][1] == 120
+
+
+def item_stream(eng):
+    """one chain of 300 data lines and one of 298: 600 items, three blocks of the fill.  The scan of the item sizes stands behind
+    the plan in d_work, at word n_chains (capi_chain_write.inc)"""
+    data = chain(300) + chain(298, 1, tname=b"second")
+    sp = Split(eng, data)
+    work = eng.empty(int(eng.lib.wga_chain_filter_work_bytes(sp.nc, sp.nd)), np.uint8)
+    total, kept = eng.chain_filter_count(*sp.args(), work)
+    want = ref.filter_ref(sp.heads, sp.triples, sp.off, data, 0, 0)[0]
+    assert (total, kept) == (len(want), 2)
+    par = np.zeros(1, dtype=CHAIN_FILTER_PARAMS_DTYPE)
+
+    def fill(total_bytes, d_out):
+        tot, k = C.c_uint64(total_bytes), C.c_uint64(kept)
+        assert eng.lib.wga_chain_filter(eng.ctx, sp.d_text.ptr, len(data), sp.d_heads.ptr, sp.nc, sp.d_lines.ptr, sp.d_off.ptr,
+                                        par.ctypes.data, work.ptr, C.byref(tot), C.byref(k), d_out) == 0
+        assert (tot.value, k.value) == (total_bytes, kept)
+    return ti.Stream(eng, work, sp.nc, sp.nc + sp.nd, want, fill)
+
+
+def check_abi_fill_short_total(eng):
+    ti.check_short_total(item_stream(eng))
+
+
+def check_abi_fill_scan_one_off(eng):
+    ti.check_scan_one_off(item_stream(eng), size_checked=False)
 
 
 def random_file(seed):

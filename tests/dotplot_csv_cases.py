@@ -12,6 +12,7 @@ import numpy as np
 
 import dotplot_csv_ref as ref
 import oracle_py as orc
+import text_items_cases as ti
 from helpers import GOLDEN
 from wgatools_amd import synth
 
@@ -203,6 +204,26 @@ def check_abi_count_fill(eng):
         fills.append(got[lead:lead + total].tobytes())
     assert fills[0] == fills[1] == rows.want
     assert eng.dotplot_csv(*rows.args(), work=work) == rows.want          # the same workspace under another pair of calls
+
+
+def item_stream(eng):
+    """two records of 300 rows: 600 items, three blocks of the fill.  The scan of the row sizes leads d_work: word 0
+    (capi_dotplot_csv.inc)"""
+    rows = Rows(eng, segs_of(600), [300, 300], [b",chrT,chrQ\n", b",second,q\n"])
+    work = eng.empty(int(eng.lib.wga_dotplot_csv_work_bytes(600)), np.uint8)
+    assert eng.dotplot_csv_count(*rows.args(), work) == len(rows.want)
+
+    def fill(total_bytes, d_out):
+        assert raw(eng, rows, work=work, out=d_out, total=total_bytes) == (0, total_bytes)
+    return ti.Stream(eng, work, 0, 600, rows.want, fill)
+
+
+def check_abi_fill_short_total(eng):
+    ti.check_short_total(item_stream(eng))
+
+
+def check_abi_fill_scan_one_off(eng):
+    ti.check_scan_one_off(item_stream(eng), size_checked=True)
 
 
 def random_rows(seed):

@@ -57,6 +57,14 @@ def test_chain_filter_abi_count_fill_consistency(eng):
     cf.check_abi_count_fill(eng)
 
 
+def test_chain_filter_abi_fill_short_total(eng):
+    cf.check_abi_fill_short_total(eng)
+
+
+def test_chain_filter_abi_fill_scan_one_off(eng):
+    cf.check_abi_fill_scan_one_off(eng)
+
+
 @pytest.mark.parametrize("lo", range(0, 12, 3))
 def test_chain_filter_abi_random_files(eng, lo):
     cf.check_abi_random_files(eng, range(lo, lo + 3))

@@ -52,6 +52,14 @@ def test_dotplot_csv_abi_count_fill_consistency(eng):
     dc.check_abi_count_fill(eng)
 
 
+def test_dotplot_csv_abi_fill_short_total(eng):
+    dc.check_abi_fill_short_total(eng)
+
+
+def test_dotplot_csv_abi_fill_scan_one_off(eng):
+    dc.check_abi_fill_scan_one_off(eng)
+
+
 @pytest.mark.parametrize("lo", range(0, 12, 3))
 def test_dotplot_csv_abi_random(eng, lo):
     dc.check_abi_random(eng, range(lo, lo + 3))

@@ -62,6 +62,14 @@ def test_chain2paf_abi_count_fill_consistency(eng):
     c2p.check_abi_count_fill(eng)
 
 
+def test_chain2paf_abi_fill_short_total(eng):
+    c2p.check_abi_fill_short_total(eng)
+
+
+def test_chain2paf_abi_fill_scan_one_off(eng):
+    c2p.check_abi_fill_scan_one_off(eng)
+
+
 def test_chain2paf_abi_arguments(eng):
     c2p.check_abi_arguments(eng)
 

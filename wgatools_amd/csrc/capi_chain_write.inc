@@ -1,5 +1,5 @@
 /* capi_chain_write.inc — K25: the chain record writer of `filter -f chain` (wga_k25_chain_write.h).
- * A part of wga_capi.cpp (included there: one translation unit). */
+ * A part of wga_capi.cpp (included there: one translation unit; chain_items_open is there). */
 /* d_work in u64 words, N = n_chains + n_data_lines items: the plan (a head's bytes, 0 = dropped) [n_chains] | the scan of the
  * item sizes [N + 1] | the kept chains [1] (behind the scan's total: both come back in one copy) | the scan's partials
  * [N / 1024 + 4] */
@@ -20,38 +20,26 @@ int wga_chain_filter(wga_ctx* c, const uint8_t* d_text, uint64_t n_bytes, const 
   if (rc) return rc;
   static_assert(sizeof(wga_chain_filter_params) == 16 && sizeof(wga_chain_filter_params) == sizeof(wga_chain_filter_params_dev),
                 "K25 params layout");
-  static_assert(sizeof(wga_chain_head) == sizeof(wga_chain_head_dev), "wga_chain_head layout");
   if (!params || !total_bytes || !n_kept) return fail(WGA_E_INVALID_ARG, "null argument", nullptr);
-  if (!d_work) return fail(WGA_E_INVALID_ARG, "d_work null", nullptr);
-  if (n_chains > 0xFFFFFFF0ull || n_bytes >= 0xFFFFFFF0ull) return fail(WGA_E_INVALID_ARG, "a text within wga_chain_split's limits", nullptr);
-  if (n_chains && (!d_text || !d_heads || !d_line_off)) return fail(WGA_E_INVALID_ARG, "null array", nullptr);
-  if (!d_out) *total_bytes = 0, *n_kept = 0;
-  if (n_chains == 0 || (d_out && *total_bytes == 0)) return WGA_OK;
-  u64 nd = 0; /* the data lines: the last offset */
-  RT_CHECK(rt_d2h(&nd, d_line_off + n_chains, sizeof nd, c->stream));
-  if (nd > 0xFFFFFFF0ull || n_chains + nd > 0xFFFFFFF0ull) return fail(WGA_E_INVALID_ARG, "more than 0xFFFFFFF0 chains and data lines", nullptr);
-  if (nd && !d_lines) return fail(WGA_E_INVALID_ARG, "d_lines null", nullptr);
-  const u32 nc = (u32)n_chains, n_items = (u32)(n_chains + nd);
+  ScanItems<ChainWriteFmt> f;
+  u32 n_items;
+  if ((rc = chain_items_open(c, d_text, n_bytes, d_heads, n_chains, d_lines, d_line_off, d_work, d_out, total_bytes, n_kept, &f.f,
+                             &n_items)) || !n_items)
+    return rc;
+  f.f.text = d_text;
+  f.f.heads = (const wga_chain_head_dev*)d_heads;
+  const u32 nc = f.f.n_rec;
   u64* plan = (u64*)d_work;
   u64* isc = plan + nc;
   u64* kept = isc + (size_t)n_items + 1;
   u64* partial = kept + 1;
-  ChainItems it;
-  it.lines = (const u64*)d_lines;
-  it.line_off = (const u64*)d_line_off;
-  it.plan = plan;
-  it.n_chains = nc;
-  it.n_lines = nd;
   if (!d_out) {
     wga_chain_filter_params_dev P;
     P.min_block_size = params->min_block_size;
     P.min_query_size = params->min_query_size;
     RT_CHECK(rt_memset(kept, 0, sizeof(u64), c->stream));
-    WGA_LAUNCH(k_chain_write_plan, (nc + 255u) / 256u, WGA_BLOCK, c->stream, d_text, (const wga_chain_head_dev*)d_heads, nc, P,
-               plan, kept);
+    WGA_LAUNCH(k_chain_write_plan, (nc + 255u) / 256u, WGA_BLOCK, c->stream, d_text, f.f.heads, nc, P, plan, kept);
     LAUNCH_CHECK();
-    ScanChainItem f;
-    f.it = it;
     if ((rc = run_scan_ws(c, f, n_items, isc, partial))) return rc;
     u64 tot[2] = {0, 0};
     RT_CHECK(rt_d2h(tot, isc + n_items, sizeof tot, c->stream));
@@ -60,10 +48,7 @@ int wga_chain_filter(wga_ctx* c, const uint8_t* d_text, uint64_t n_bytes, const 
     return WGA_OK;
   }
   if (*n_kept == 0 || *n_kept > n_chains) return fail(WGA_E_INVALID_ARG, "the counts are not the first call's", nullptr);
-  WGA_LAUNCH(k_chain_write_fill, (u32)(((u64)n_items + WGA_CHAIN_WRITE_ITEMS - 1u) / WGA_CHAIN_WRITE_ITEMS), WGA_BLOCK, c->stream, it,
-             (u64)n_items, d_text, (const wga_chain_head_dev*)d_heads, (const u64*)isc, (u64)*total_bytes, d_out);
-  LAUNCH_CHECK();
-  return WGA_OK;
+  return run_text_items_fill(c, f.f, n_items, isc, (u64)*total_bytes, d_out);
 }
 
 } /* extern "C" */

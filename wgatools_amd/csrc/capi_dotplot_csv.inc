@@ -25,13 +25,12 @@ int wga_dotplot_csv(wga_ctx* c, uint32_t n, const uint64_t* d_segs, const uint64
   R.seg_off = (const u64*)d_seg_off;
   R.tails = (const u8*)d_tails;
   R.tail_off = (const u64*)d_tail_off;
-  R.n = n;
+  R.n_rec = n;
   R.n_rows = n_rows;
   u64* rsc = (u64*)d_work;
   u64* partial = rsc + (size_t)n_rows + 1;
-  const u32 nb = (u32)((n_rows + WGA_DOTPLOT_CSV_ROWS - 1u) / WGA_DOTPLOT_CSV_ROWS);
   if (!d_out) {
-    WGA_LAUNCH(k_dotplot_csv_count, nb, WGA_BLOCK, c->stream, R, rsc);
+    WGA_LAUNCH(k_dotplot_csv_count, (u32)((n_rows + WGA_TEXT_ITEMS - 1u) / WGA_TEXT_ITEMS), WGA_BLOCK, c->stream, R, rsc);
     LAUNCH_CHECK();
     /* the exclusive scan in place (k_scan_final reads its four values, then writes them) */
     ScanPlain f;
@@ -40,9 +39,7 @@ int wga_dotplot_csv(wga_ctx* c, uint32_t n, const uint64_t* d_segs, const uint64
     RT_CHECK(rt_d2h(total_bytes, rsc + n_rows, sizeof(u64), c->stream));
     return WGA_OK;
   }
-  WGA_LAUNCH(k_dotplot_csv_fill, nb, WGA_BLOCK, c->stream, R, (const u64*)rsc, (u64)*total_bytes, d_out);
-  LAUNCH_CHECK();
-  return WGA_OK;
+  return run_text_items_fill(c, R, (u32)n_rows, rsc, (u64)*total_bytes, d_out);
 }
 
 } /* extern "C" */

@@ -26,6 +26,7 @@
 #include "wga_k7_paf_call.h"
 #include "wga_k8_tokenise.h"
 #include "wga_text_out.h"      /* what the text writers share: decimals, sinks, the staged stretch */
+#include "wga_chain_items.h"   /* the items of a stream of chains (K25, K27), a data line's CIGAR text (K11, K27) */
 #include "wga_k9_bed.h"
 #include "wga_k10_chain.h"
 #include "wga_k11_bridges.h"
@@ -239,6 +240,42 @@ static int run_scan(wga_ctx* c, F f, u32 n, u64* d_out /* n+1 */) {
   int rc = ctx_scratch(c, ((size_t)(n + 1023u) / 1024u + 1) * sizeof(u64), &ws);
   if (rc) return rc;
   return run_scan_ws(c, f, n, d_out, (u64*)ws);
+}
+/* the text of a stream of n items of format f behind isc, the scan of their sizes over ScanItems<F> (wga_text_out.h) */
+template <typename F>
+static int run_text_items_fill(wga_ctx* c, const F& f, u32 n, const u64* isc, u64 total, uint8_t* d_out) {
+  WGA_LAUNCH(k_text_items_fill<F>, (u32)(((u64)n + WGA_TEXT_ITEMS - 1u) / WGA_TEXT_ITEMS), WGA_BLOCK, c->stream, f, (u64)n, isc, total,
+             d_out);
+  LAUNCH_CHECK();
+  return WGA_OK;
+}
+/* What wga_chain_filter and wga_chain2paf do alike behind their own null checks: the checks of the arrays and limits, the count
+ * call's zeroed results (n_kept: K25's, else null), the read of the data lines' number and the items of the stream (the plan leads
+ * d_work in both layouts).  *n_items == 0 when it returns WGA_OK: nothing is left to do. */
+static int chain_items_open(wga_ctx* c, const uint8_t* d_text, uint64_t n_bytes, const wga_chain_head* d_heads, uint64_t n_chains,
+                            const uint64_t* d_lines, const uint64_t* d_line_off, void* d_work, const uint8_t* d_out,
+                            uint64_t* total_bytes, uint64_t* n_kept, ChainItemBase* it, u32* n_items) {
+  static_assert(sizeof(wga_chain_head) == sizeof(wga_chain_head_dev), "wga_chain_head layout");
+  *n_items = 0;
+  if (!d_work) return fail(WGA_E_INVALID_ARG, "d_work null", nullptr);
+  if (n_chains > 0xFFFFFFF0ull || n_bytes >= 0xFFFFFFF0ull) return fail(WGA_E_INVALID_ARG, "a text within wga_chain_split's limits", nullptr);
+  if (n_chains && (!d_text || !d_heads || !d_line_off)) return fail(WGA_E_INVALID_ARG, "null array", nullptr);
+  if (!d_out) {
+    *total_bytes = 0;
+    if (n_kept) *n_kept = 0;
+  }
+  if (n_chains == 0 || (d_out && *total_bytes == 0)) return WGA_OK;
+  u64 nd = 0; /* the data lines: the last offset */
+  RT_CHECK(rt_d2h(&nd, d_line_off + n_chains, sizeof nd, c->stream));
+  if (nd > 0xFFFFFFF0ull || n_chains + nd > 0xFFFFFFF0ull) return fail(WGA_E_INVALID_ARG, "more than 0xFFFFFFF0 chains and data lines", nullptr);
+  if (nd && !d_lines) return fail(WGA_E_INVALID_ARG, "d_lines null", nullptr);
+  it->lines = (const u64*)d_lines;
+  it->line_off = (const u64*)d_line_off;
+  it->plan = (const u64*)d_work;
+  it->n_rec = (u32)n_chains;
+  it->n_lines = nd;
+  *n_items = (u32)(n_chains + nd);
+  return WGA_OK;
 }
 
 static int check_batch(const wga_cigar_batch* b) {

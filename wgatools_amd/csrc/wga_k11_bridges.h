@@ -5,7 +5,8 @@
 #ifndef WGA_K11_BRIDGES_H
 #define WGA_K11_BRIDGES_H
 
-#include "wga_text_out.h" /* dec_digits, dec_write, lds_text_flush, csr_find_in */
+#include "wga_text_out.h"    /* the sinks, lds_text_flush, csr_find_in */
+#include "wga_chain_items.h" /* c2p_line_emit: a data line's part of the CIGAR text */
 
 /* ============================================================================================ */
 /* K11: bridges between the run / data-line lists and the packed-op and CIGAR-text forms        */
@@ -32,12 +33,6 @@ __device__ __forceinline__ u32* put_split(u32* p, u64 len, u32 code, u32 cont) {
     first = false;
   }
   return p;
-}
-__device__ __forceinline__ u8* put_len_op(u8* p, u64 len, u8 op) {
-  const u32 nd = dec_digits(len);
-  dec_write(p, len, nd);
-  p[nd] = op;
-  return p + nd + 1u;
 }
 
 /* K3 runs (start_column << 3 | class, class 0 '=' 1 I 2 D 3 X) of MAF column pairs */
@@ -66,13 +61,23 @@ struct MafRunOps {
   }
 };
 /* -> the cg:Z: text of maf2paf, "<len><=|I|D|X>" per run (maf.rs:484-520, cigar.rs:400-401) */
+template <typename S>
+__device__ __forceinline__ void maf_run_emit(S& s, const MafRunSrc& m, u64 x, u32 r) {
+  const u32 c = m.cls(x);
+  s.dec(m.len(x, r));
+  s.c(c == 0u ? (u8)'=' : c == 1u ? (u8)'I' : c == 2u ? (u8)'D' : (u8)'X');
+}
 struct MafRunText {
   typedef u8 out_t;
   MafRunSrc s;
-  __device__ u64 size(u64 x, u32 r) const { return dec_digits(s.len(x, r)) + 1u; }
+  __device__ u64 size(u64 x, u32 r) const {
+    TextCount c;
+    maf_run_emit(c, s, x, r);
+    return c.n;
+  }
   __device__ void write(u64 x, u32 r, u8* p) const {
-    const u32 c = s.cls(x);
-    put_len_op(p, s.len(x, r), c == 0u ? (u8)'=' : c == 1u ? (u8)'I' : c == 2u ? (u8)'D' : (u8)'X');
+    TextPut w = {p};
+    maf_run_emit(w, s, x, r);
   }
 };
 /* chain data lines, three u64 each: size, 2nd column (bases only in the target: D), 3rd column
@@ -98,19 +103,18 @@ struct ChainLineOps {
     put_split(p, s.del_(x), (u32)WGA_OP_D, (u32)WGA_OP_D_CONT);
   }
 };
-/* -> chain2paf's CIGAR text: "<size>M" always, "<n>I" / "<n>D" when non-zero (cigar.rs:576-606) */
+/* -> chain2paf's CIGAR text: c2p_line_emit (wga_chain_items.h) per line */
 struct ChainLineText {
   typedef u8 out_t;
   ChainLineSrc s;
   __device__ u64 size(u64 x, u32) const {
-    const u64 i = s.ins_(x), d = s.del_(x);
-    return (u64)dec_digits(s.size_(x)) + 1u + (i ? dec_digits(i) + 1u : 0u) + (d ? dec_digits(d) + 1u : 0u);
+    TextCount c;
+    c2p_line_emit(c, s.lines + 3u * x);
+    return c.n;
   }
   __device__ void write(u64 x, u32, u8* p) const {
-    const u64 i = s.ins_(x), d = s.del_(x);
-    p = put_len_op(p, s.size_(x), (u8)'M');
-    if (i) p = put_len_op(p, i, (u8)'I');
-    if (d) put_len_op(p, d, (u8)'D');
+    TextPut w = {p};
+    c2p_line_emit(w, s.lines + 3u * x);
   }
 };
 

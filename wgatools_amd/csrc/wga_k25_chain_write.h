@@ -6,27 +6,25 @@
 #ifndef WGA_K25_CHAIN_WRITE_H
 #define WGA_K25_CHAIN_WRITE_H
 
-#include "wga_text_out.h"        /* the sinks, TextStretch, csr_find_in */
+#include "wga_text_out.h"        /* the sinks, ScanItems and k_text_items_fill */
+#include "wga_chain_items.h"     /* ChainItemBase: the item numbering */
 #include "wga_k23_chain_split.h" /* wga_chain_head_dev */
 
 /* ============================================================================================ */
 /* K25: chain record writer                                                                     */
 /* ============================================================================================ */
-/* The text of the kept chains is ONE contiguous byte stream, so it is written as a stream of ITEMS in file order: the head of
- * chain 0, its data lines, the head of chain 1, its data lines, ...  The head of chain r is item line_off[r] + r, data line l
- * of chain r is item l + r + 1.  A head item is the header line without its newline ("chain\t<score>\t<tname>\t...\t<id>"), a
- * line item is "\n<size>\t<col2>\t<col3>"; the item that ends a chain (its last line, or the head of a chain without lines)
- * also carries the "\n\n" behind the chain.  Items of dropped chains have size 0.
+/* The text of the kept chains is ONE contiguous byte stream, so it is written as a stream of ITEMS in file order, numbered as
+ * wga_chain_items.h says.  A head item is the header line without its newline ("chain\t<score>\t<tname>\t...\t<id>"), a line
+ * item is "\n<size>\t<col2>\t<col3>"; the item that ends a chain also carries the "\n\n" behind it.  Items of dropped chains
+ * have size 0.
  *   plan   one thread per chain: the keep flag (filter.rs:96-101, both compare with `<`, the span wraps) and the head's byte
  *          count (0 = dropped; a kept head has at least 30 bytes), the kept chains counted by one atomicAdd per block.
- *   scan   the exclusive scan of the item sizes (ScanChainItem: an item's chain by bisection in line_off[r] + r).
- *   fill   256 consecutive items per block = one contiguous stretch of the text, whatever record borders lie inside it, staged
- *          and flushed as wga_text_out.h describes.  256 line items are at most 256 x 65 bytes: that is the stage.  A block whose
- *          stretch is longer (a head with names of kilobytes) writes its items directly.
- * The chain of item x is csr_find_in(line_off, lo, hi, x, true): the largest r with line_off[r] + r <= x.  The emitters run into a
- * TextCount for the plan and the scan, into a TextPut for the fill. */
-#define WGA_CHAIN_WRITE_ITEMS 256u
-#define WGA_CHAIN_WRITE_STAGE (WGA_CHAIN_WRITE_ITEMS * 65u)
+ *   scan   the exclusive scan of the item sizes (ScanItems<ChainWriteFmt>: an item's chain by bisection in line_off[r] + r).
+ *   fill   k_text_items_fill<ChainWriteFmt> (wga_text_out.h): 256 consecutive items per block, staged and flushed as that file
+ *          describes.  256 line items are at most 256 x 65 bytes: that is the stage.  A block whose stretch is longer (a head
+ *          with names of kilobytes) writes its items directly.  kCheckSize is off: an item's span is checked, its size is not.
+ * The emitters run into a TextCount for the plan and the scan, into a TextPut for the fill. */
+#define WGA_CHAIN_WRITE_STAGE (WGA_TEXT_ITEMS * 65u)
 
 struct wga_chain_filter_params_dev {
   u64 min_block_size, min_query_size;
@@ -64,12 +62,13 @@ __device__ __forceinline__ void chain_head_emit(S& s, const wga_chain_head_dev& 
 /* chain.rs:92-100: always three columns */
 template <typename S>
 __device__ __forceinline__ void chain_line_emit(S& s, const u64* __restrict__ v) {
+  const u64 a = v[0], b = v[1], c = v[2]; /* all three before the first byte is written */
   s.c((u8)'\n');
-  s.dec(v[0]);
+  s.dec(a);
   s.c((u8)'\t');
-  s.dec(v[1]);
+  s.dec(b);
   s.c((u8)'\t');
-  s.dec(v[2]);
+  s.dec(c);
 }
 template <typename S>
 __device__ __forceinline__ void chain_end_emit(S& s) {
@@ -88,7 +87,6 @@ __global__ __launch_bounds__(256) void k_chain_write_plan(const u8* __restrict__
     const wga_chain_head_dev H = heads[r];
     const bool keep = !(H.num[3] - H.num[2] < P.min_block_size || H.num[4] < P.min_query_size);
     TextCount c;
-    c.n = 0;
     if (keep) chain_head_emit(c, H, text);
     plan[r] = c.n;
     kept = keep ? 1u : 0u;
@@ -98,65 +96,25 @@ __global__ __launch_bounds__(256) void k_chain_write_plan(const u8* __restrict__
   if (threadIdx.x == 0 && tot) atomicAdd(n_kept, tot);
 }
 
-/* item x of chain r: its bytes.  n_lines bounds the data-line index for offsets that are not a splitter's */
-struct ChainItems {
-  const u64* lines;
-  const u64* line_off;
-  const u64* plan;
-  u32 n_chains;
-  u64 n_lines;
+/* K25's format: every item of a dropped chain (plan[r] == 0) has no bytes */
+struct ChainWriteFmt : ChainItemBase {
+  static constexpr u32 kStage = WGA_CHAIN_WRITE_STAGE;
+  static constexpr bool kCheckSize = false;
+  const u8* text;
+  const wga_chain_head_dev* heads;
+  template <typename S>
+  __device__ __forceinline__ void head_emit(S& s, u32 r) const { chain_head_emit(s, heads[r], text); }
+  template <typename S>
+  __device__ __forceinline__ void line_emit(S& s, u64 l) const { chain_line_emit(s, lines + 3u * l); }
+  template <typename S>
+  __device__ __forceinline__ void end_emit(S& s) const { chain_end_emit(s); }
   __device__ __forceinline__ u64 size(u64 x, u32 r) const {
-    const u64 head = plan[r];
-    if (head == 0u) return 0u;
-    const u64 first = line_off[r], end = line_off[r + 1u];
-    if (x == first + (u64)r) return head + (first == end ? 2u : 0u);
-    const u64 l = x - (u64)r - 1u;
-    if (l >= n_lines) return 0u;
-    TextCount c;
-    c.n = 0;
-    chain_line_emit(c, lines + 3u * l);
-    return c.n + (l + 1u == end ? 2u : 0u);
+    const u64 head = plan[r]; /* read with the chain's offsets, not behind them */
+    const ChainItem i = chain_item(*this, x, r);
+    return head == 0u ? 0u : chain_item_size(*this, i, head);
   }
+  template <typename S>
+  __device__ __forceinline__ void emit(S& s, u64 x, u32 r) const { chain_item_emit(*this, s, x, r); }
 };
-struct ScanChainItem { /* scan functor: the bytes of item x */
-  ChainItems it;
-  __device__ u64 operator()(u32 x) const { return it.size((u64)x, csr_find_in(it.line_off, 0u, it.n_chains, (u64)x, true)); }
-};
-
-/* items [256 b, 256 b + 256) of n_items; isc = the exclusive scan of their sizes (isc[n_items] = the text's length).  Nothing is
- * written outside out[0, total): a block whose stretch ends behind `total` (a scan that is not this call's) writes nothing. */
-__global__ __launch_bounds__(256) void k_chain_write_fill(ChainItems it, u64 n_items, const u8* __restrict__ text,
-                                                          const wga_chain_head_dev* __restrict__ heads,
-                                                          const u64* __restrict__ isc, u64 total, u8* __restrict__ out) {
-  __shared__ u32x4_a16 s_buf[(WGA_CHAIN_WRITE_STAGE + 32u) / 16u];
-  __shared__ u32 s_r[2];
-  const u32 tid = threadIdx.x;
-  const u64 x0 = (u64)blockIdx.x * WGA_CHAIN_WRITE_ITEMS;
-  const u64 x1 = x0 + WGA_CHAIN_WRITE_ITEMS < n_items ? x0 + WGA_CHAIN_WRITE_ITEMS : n_items;
-  const u64 e0 = isc[x0], e1 = isc[x1]; /* bytes in front of the block, and behind it */
-  if (e1 <= e0 || e1 > total) return;   /* block-uniform: every chain of the block is dropped */
-  if (tid < 2u) s_r[tid] = csr_find_in(it.line_off, 0u, it.n_chains, tid ? x1 - 1u : x0, true);
-  __syncthreads();
-  const TextStretch st(s_buf, WGA_CHAIN_WRITE_STAGE, out + e0, e1 - e0); /* block-uniform */
-  const u64 x = x0 + tid;
-  if (x < x1) {
-    const u64 at = isc[x], sz = isc[x + 1u] - at;
-    if (sz) { /* a kept chain's item */
-      const u32 r = csr_find_in(it.line_off, s_r[0], s_r[1] + 1u, x, true);
-      TextPut w;
-      w.p = st.at(at - e0);
-      const u64 first = it.line_off[r], end = it.line_off[r + 1u];
-      if (x == first + (u64)r) {
-        chain_head_emit(w, heads[r], text);
-        if (first == end) chain_end_emit(w);
-      } else {
-        const u64 l = x - (u64)r - 1u;
-        chain_line_emit(w, it.lines + 3u * l);
-        if (l + 1u == end) chain_end_emit(w);
-      }
-    }
-  }
-  st.flush_block(tid);
-}
 
 #endif /* WGA_K25_CHAIN_WRITE_H */

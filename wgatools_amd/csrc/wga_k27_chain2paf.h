@@ -6,30 +6,29 @@
 #ifndef WGA_K27_CHAIN2PAF_H
 #define WGA_K27_CHAIN2PAF_H
 
-#include "wga_text_out.h"        /* the sinks, TextStretch, csr_find_in */
-#include "wga_k23_chain_split.h" /* wga_chain_head_dev */
+#include "wga_text_out.h"         /* the sinks, ScanItems and k_text_items_fill */
+#include "wga_k23_chain_split.h"  /* wga_chain_head_dev */
+#include "wga_chain_items.h"      /* ChainItemBase: the item numbering; c2p_line_emit: a data line's part of the CIGAR text */
 
 /* ============================================================================================ */
 /* K27: chain2paf record writer                                                                 */
 /* ============================================================================================ */
-/* One PAF record per chain, the records back to back: ONE contiguous byte stream, written as a stream of ITEMS in file order
- * exactly as K25 numbers them: the head of chain r is item line_off[r] + r, data line l of chain r is item l + r + 1.  A head item
- * is the twelve columns and the tag's name ("<qname>\t...\t255\tcg:Z:"), a line item is the line's part of the CIGAR text
- * ("<size>M", "<col3>I" and "<col2>D" when non-zero: at most 63 bytes); the item that ends a chain (its last line, or the head of
- * a chain without lines) also carries the record's "\n".
+/* One PAF record per chain, the records back to back: ONE contiguous byte stream, written as a stream of ITEMS in file order,
+ * numbered as wga_chain_items.h says.  A head item is the twelve columns and the tag's name ("<qname>\t...\t255\tcg:Z:"), a line
+ * item is the line's part of the CIGAR text ("<size>M", "<col3>I" and "<col2>D" when non-zero: at most 63 bytes); the item that
+ * ends a chain also carries the record's "\n".
  *   sums   columns 10 and 11 need no op walk (mismatch is 0, a deletion counts once whichever strand books it): matches = the
  *          sum of the chain's sizes, block_length = matches + the sum of its 2nd columns, both mod 2^64.  Two wrapping exclusive
  *          scans over ALL data lines (the context's scan driver), a chain's sums are differences of them: no thread's work
  *          depends on a chain's length.
  *   plan   one thread per chain: the two sums and the head's byte count, kept for the fill.
- *   scan   the exclusive scan of the item sizes (ScanC2pItem: an item's chain by bisection in line_off[r] + r).
- *   fill   256 consecutive items per block = one contiguous stretch of the text, whatever record borders lie inside it, staged
- *          and flushed as wga_text_out.h describes.  256 line items are at most 256 x 64 bytes: that is the stage (16 KiB + 32:
- *          nine blocks' worth fit a CU's 160 KiB, so the LDS does not bound the occupancy of 256-thread blocks; it leaves in
- *          16-byte stores).  A block whose stretch is longer (a head with names of kilobytes) writes its items directly.
+ *   scan   the exclusive scan of the item sizes (ScanItems<Chain2PafFmt>: an item's chain by bisection in line_off[r] + r).
+ *   fill   k_text_items_fill<Chain2PafFmt> (wga_text_out.h): 256 consecutive items per block, staged and flushed as that file
+ *          describes.  256 line items are at most 256 x 64 bytes: that is the stage (16 KiB + 32: nine blocks' worth fit a CU's
+ *          160 KiB, so the LDS does not bound the occupancy of 256-thread blocks; it leaves in 16-byte stores).  A block whose
+ *          stretch is longer (a head with names of kilobytes) writes its items directly.  kCheckSize is off, as in K25.
  * The emitters run into a TextCount for the plan and the scan, into a TextPut for the fill. */
-#define WGA_C2P_ITEMS 256u
-#define WGA_C2P_STAGE (WGA_C2P_ITEMS * 64u)
+#define WGA_C2P_STAGE (WGA_TEXT_ITEMS * 64u)
 
 /* a field as the csv writer writes it under QuoteStyle::Necessary: as it is, unless it holds the delimiter, a quote, CR or LF;
  * then between quotes with every quote inside doubled */
@@ -90,21 +89,6 @@ __device__ __forceinline__ void c2p_head_emit(S& s, const wga_chain_head_dev& H,
   paf_head_emit(s, text + (ql ? H.qname_off : 0u), ql, H.num + 4, H.qstrand_neg != 0, text + (tl ? H.tname_off : 0u), tl, H.num + 1,
                 matches, block_length, 255u);
 }
-/* cigar.rs:576-610: "<size>M" always, the 3rd column as I and the 2nd as D when non-zero */
-template <typename S>
-__device__ __forceinline__ void c2p_line_emit(S& s, const u64* __restrict__ v) {
-  s.dec(v[0]);
-  s.c((u8)'M');
-  if (v[2]) {
-    s.dec(v[2]);
-    s.c((u8)'I');
-  }
-  if (v[1]) {
-    s.dec(v[1]);
-    s.c((u8)'D');
-  }
-}
-
 /* scan functor: column `col` of data line x (the sums wrap) */
 struct ScanChainCol {
   const u64* lines;
@@ -125,71 +109,31 @@ __global__ __launch_bounds__(256) void k_chain2paf_plan(const u8* __restrict__ t
   b = b < n_lines ? b : n_lines;
   const u64 matches = ps[b] - ps[a], block_length = matches + (pd[b] - pd[a]);
   TextCount c;
-  c.n = 0;
   c2p_head_emit(c, heads[r], text, n_bytes, matches, block_length);
   plan[r] = c.n;
   sums[2u * r] = matches;
   sums[2u * r + 1u] = block_length;
 }
 
-/* item x of chain r: its bytes.  n_lines bounds the data-line index for offsets that are not a splitter's */
-struct C2pItems {
-  const u64* lines;
-  const u64* line_off;
-  const u64* plan;
-  u32 n_chains;
-  u64 n_lines;
-  __device__ __forceinline__ u64 size(u64 x, u32 r) const {
-    const u64 first = line_off[r], end = line_off[r + 1u];
-    if (x == first + (u64)r) return plan[r] + (first == end ? 1u : 0u);
-    const u64 l = x - (u64)r - 1u;
-    if (l >= n_lines) return 0u;
-    TextCount c;
-    c.n = 0;
-    c2p_line_emit(c, lines + 3u * l);
-    return c.n + (l + 1u == end ? 1u : 0u);
+/* K27's format over the chain items' numbering: the head's columns need the chain's two sums */
+struct Chain2PafFmt : ChainItemBase {
+  static constexpr u32 kStage = WGA_C2P_STAGE;
+  static constexpr bool kCheckSize = false;
+  const u8* text;
+  u64 n_bytes;
+  const wga_chain_head_dev* heads;
+  const u64* sums;
+  template <typename S>
+  __device__ __forceinline__ void head_emit(S& s, u32 r) const {
+    c2p_head_emit(s, heads[r], text, n_bytes, sums[2u * (u64)r], sums[2u * (u64)r + 1u]);
   }
+  template <typename S>
+  __device__ __forceinline__ void line_emit(S& s, u64 l) const { c2p_line_emit(s, lines + 3u * l); }
+  template <typename S>
+  __device__ __forceinline__ void end_emit(S& s) const { s.c((u8)'\n'); }
+  __device__ __forceinline__ u64 size(u64 x, u32 r) const { return chain_item_size(*this, chain_item(*this, x, r), plan[r]); }
+  template <typename S>
+  __device__ __forceinline__ void emit(S& s, u64 x, u32 r) const { chain_item_emit(*this, s, x, r); }
 };
-struct ScanC2pItem { /* scan functor: the bytes of item x */
-  C2pItems it;
-  __device__ u64 operator()(u32 x) const { return it.size((u64)x, csr_find_in(it.line_off, 0u, it.n_chains, (u64)x, true)); }
-};
-
-/* items [256 b, 256 b + 256) of n_items; isc = the exclusive scan of their sizes (isc[n_items] = the text's length).  Nothing is
- * written outside out[0, total): a block whose stretch ends behind `total` (a scan that is not this call's) writes nothing. */
-__global__ __launch_bounds__(256) void k_chain2paf_fill(C2pItems it, u64 n_items, const u8* __restrict__ text, u64 n_bytes,
-                                                        const wga_chain_head_dev* __restrict__ heads,
-                                                        const u64* __restrict__ sums, const u64* __restrict__ isc, u64 total,
-                                                        u8* __restrict__ out) {
-  __shared__ u32x4_a16 s_buf[(WGA_C2P_STAGE + 32u) / 16u];
-  __shared__ u32 s_r[2];
-  const u32 tid = threadIdx.x;
-  const u64 x0 = (u64)blockIdx.x * WGA_C2P_ITEMS;
-  const u64 x1 = x0 + WGA_C2P_ITEMS < n_items ? x0 + WGA_C2P_ITEMS : n_items;
-  const u64 e0 = isc[x0], e1 = isc[x1]; /* bytes in front of the block, and behind it */
-  if (e1 <= e0 || e1 > total) return;   /* block-uniform */
-  if (tid < 2u) s_r[tid] = csr_find_in(it.line_off, 0u, it.n_chains, tid ? x1 - 1u : x0, true);
-  __syncthreads();
-  const TextStretch st(s_buf, WGA_C2P_STAGE, out + e0, e1 - e0); /* block-uniform */
-  const u64 x = x0 + tid;
-  if (x < x1) {
-    const u64 at = isc[x], sz = isc[x + 1u] - at;
-    if (sz && at >= e0 && at <= e1 && sz <= e1 - at) { /* inside the stretch also for a scan that is not this call's */
-      const u32 r = csr_find_in(it.line_off, s_r[0], s_r[1] + 1u, x, true);
-      TextPut w;
-      w.p = st.at(at - e0);
-      const u64 first = it.line_off[r], end = it.line_off[r + 1u];
-      if (x == first + (u64)r) {
-        c2p_head_emit(w, heads[r], text, n_bytes, sums[2u * (u64)r], sums[2u * (u64)r + 1u]);
-        if (first == end) w.c((u8)'\n');
-      } else {
-        const u64 l = x - (u64)r - 1u;
-        c2p_line_emit(w, it.lines + 3u * l);
-        if (l + 1u == end) w.c((u8)'\n');
-      }
-    }
-  }
-  st.flush_block(tid);
-}
 
 #endif /* WGA_K27_CHAIN2PAF_H */

@@ -1,6 +1,7 @@
 /*
  * wga_text_out.h — what the kernels that write text share: decimal numbers, the count / put sink pair, the staged stretch and
- * its flush, and the bisection that finds an element's record.  Nothing here knows a format or a kernel.
+ * its flush, the bisection that finds an element's record, and the fill kernel of the texts that are a stream of items (at the
+ * end of the file).  Nothing here knows a format.
  *
  * ONE EMITTER, TWO SINKS.  A format is one function template `xxx_emit(S& s, ...)` that names its bytes in order through
  * s.c / s.dec / s.str.  Run into a TextCount it is the size the scan adds up, run into a TextPut it is the text: what the count
@@ -69,7 +70,7 @@ __device__ __forceinline__ void lds_text_flush(const u8* tbuf, u32 a, u32 total,
 
 /* the two sinks of an emitter */
 struct TextCount {
-  u64 n;
+  u64 n = 0;
   __device__ __forceinline__ void c(u8) { n++; }
   __device__ __forceinline__ void dec(u64 v) { n += dec_digits(v); }
   __device__ __forceinline__ void str(const u8*, u32 len) { n += len; }
@@ -123,6 +124,66 @@ __device__ __forceinline__ u32 csr_find_in(const u64* __restrict__ off, u32 lo, 
     if (off[mid] + (bias ? (u64)mid : 0ull) <= x) lo = mid; else hi = mid;
   }
   return lo;
+}
+
+/* ITEM STREAMS.  A text that is ONE contiguous byte stream of variable-size items (K25's and K27's heads and lines, K26's rows)
+ * is sized by a scan over ScanItems<F> and written by k_text_items_fill<F>, 256 consecutive items per block = one contiguous
+ * stretch, whatever record borders lie inside it.  The format F is a plain struct passed by value:
+ *   static constexpr u32 kStage            the bytes of a block's stretch that go through LDS (a longer one is written directly)
+ *   static constexpr bool kCheckSize       the fill compares size(x, r) with the scan's span before it writes item x
+ *   u32 n_rec                              records
+ *   u32 rec(u64 x, u32 lo, u32 hi) const   the record of item x, known to lie in [lo, hi): csr_find_in over F's offsets
+ *   u64 size(u64 x, u32 r) const           the bytes of item x of record r: its emitter into a TextCount
+ *   void emit(S& s, u64 x, u32 r) const    the emitter */
+#define WGA_TEXT_ITEMS 256u
+
+template <typename F>
+struct ScanItems { /* scan functor: the bytes of item x */
+  F f;
+  __device__ u64 operator()(u32 x) const { return f.size((u64)x, f.rec((u64)x, 0u, f.n_rec)); }
+};
+
+/* items [256 b, 256 b + 256) of n_items; isc = the exclusive scan of their sizes (isc[n_items] = the text's length).  ONE GUARD
+ * for a scan that is not this call's: a block whose stretch ends behind `total` writes nothing, and an item is written only into
+ * a span [isc[x], isc[x + 1]) that is not empty and lies inside the block's stretch — and, where F::kCheckSize is set, has the
+ * size the emitter is about to write: then nothing is written outside out[0, total) and nothing into a span but its item's text,
+ * whatever the scan holds.  Without it (K25, K27: their fills cannot pay a second walk over an item's digits,
+ * profiles/text_items_refactor.txt) an item longer than its span runs on into the bytes behind it, as it always did there.
+ * A span that is refused keeps its bytes: in a staged block its thread copies what memory holds there into the stage and the
+ * flush puts it back (the intervals between isc[x] and isc[x + 1] cover the stretch whatever the scan holds, so every byte of the
+ * stage is some item's text or what memory held; where a scan that does not ascend lays a refused span over a written item's,
+ * which of the two lands in a byte that both cover is not determined). */
+template <typename F>
+__global__ __launch_bounds__(256) void k_text_items_fill(F f, u64 n_items, const u64* __restrict__ isc, u64 total,
+                                                         u8* __restrict__ out) {
+  __shared__ u32x4_a16 s_buf[(F::kStage + 32u) / 16u];
+  __shared__ u32 s_r[2];
+  const u32 tid = threadIdx.x;
+  const u64 x0 = (u64)blockIdx.x * WGA_TEXT_ITEMS;
+  const u64 x1 = x0 + WGA_TEXT_ITEMS < n_items ? x0 + WGA_TEXT_ITEMS : n_items;
+  const u64 e0 = isc[x0], e1 = isc[x1]; /* bytes in front of the block, and behind it */
+  if (e1 <= e0 || e1 > total) return;   /* block-uniform: nothing to write (K25: every chain of the block is dropped) */
+  if (tid < 2u) s_r[tid] = f.rec(tid ? x1 - 1u : x0, 0u, f.n_rec); /* the records of the first and the last item */
+  __syncthreads();
+  const TextStretch st(s_buf, F::kStage, out + e0, e1 - e0); /* block-uniform */
+  const u64 x = x0 + tid;
+  if (x < x1) {
+    const u64 at = isc[x], end = isc[x + 1u];
+    bool put = at >= e0 && end <= e1 && end > at;
+    if (F::kCheckSize || put) {
+      const u32 r = f.rec(x, s_r[0], s_r[1] + 1u);
+      if (F::kCheckSize) put = (end - at == f.size(x, r)) && put; /* the size first: its reads go with the scan's */
+      if (put) {
+        TextPut w = {st.at(at - e0)};
+        f.emit(w, x, r);
+      }
+    }
+    if (!put && end != at && st.staged) { /* end == at: an item without bytes (K25: of a dropped chain) */
+      const u64 lo = at < end ? at : end, hi = at < end ? end : at; /* the span, and of it what lies in the stretch */
+      for (u64 k = lo > e0 ? lo : e0; k < (hi < e1 ? hi : e1); k++) *st.at(k - e0) = out[k];
+    }
+  }
+  st.flush_block(tid);
 }
 
 #endif /* WGA_TEXT_OUT_H */

@@ -474,6 +474,27 @@ class Engine:
         self._check(self.lib.wga_chain_line_off_rebase(self.ctx, int(n), _p(line_off), _p(out)))
         return out
 
+    def _count_then_fill(self, name, what, args, n_outs, out_shift):
+        """both calls of the text writer `name`: args, then n_outs u64 results by reference (*total_bytes first), then d_out.
+        The fill goes into a buffer of 0xA5 and must leave the results (`what` names them) and the bytes around the text alone.
+        Returns (text, the results)."""
+        fn = getattr(self.lib, name)
+        outs = [C.c_uint64(0) for _ in range(n_outs)]
+        refs = [C.byref(o) for o in outs]
+        self._check(fn(*args, *refs, None))
+        first = tuple(int(o.value) for o in outs)
+        guard = 64  # bytes around the text that the fill call must leave alone
+        out = self.upload(np.full(first[0] + 2 * guard + 96, 0xA5, dtype=np.uint8))
+        lead = guard + (-out.ptr) % 64 + int(out_shift)
+        self._check(fn(*args, *refs, out.ptr + lead))
+        self.sync()
+        if tuple(int(o.value) for o in outs) != first:
+            raise _lib.WgaError("%s changed its %s in the second call" % (name, what))
+        got = out.numpy()
+        if not ((got[:lead] == 0xA5).all() and (got[lead + first[0]:] == 0xA5).all()):
+            raise _lib.WgaError("%s wrote outside d_out[0 .. total_bytes)" % name)
+        return got[lead:lead + first[0]].tobytes(), first
+
     def chain_filter_count(self, text, n_bytes, heads, n_chains, lines, line_off, work, min_block_size=0, min_query_size=0):
         """K25: the count call of wga_chain_filter alone, (total_bytes, n_kept); it leaves its plan and item scan in `work`"""
         par = np.zeros(1, dtype=CHAIN_FILTER_PARAMS_DTYPE)
@@ -496,22 +517,9 @@ class Engine:
             work = self.empty(max(int(self.lib.wga_chain_filter_work_bytes(n_chains, int(n_data_lines))), 16), np.uint8)
         par = np.zeros(1, dtype=CHAIN_FILTER_PARAMS_DTYPE)
         par["min_block_size"], par["min_query_size"] = int(min_block_size), int(min_query_size)
-        total, kept = C.c_uint64(0), C.c_uint64(0)
-        args = (self.ctx, _p(text), int(n_bytes), _p(heads), n_chains, _p(lines), _p(line_off), par.ctypes.data, _p(work),
-                C.byref(total), C.byref(kept))
-        self._check(self.lib.wga_chain_filter(*args, None))
-        first = (int(total.value), int(kept.value))
-        guard = 64  # bytes around the text that the fill call must leave alone
-        out = self.upload(np.full(first[0] + 2 * guard + 96, 0xA5, dtype=np.uint8))
-        lead = guard + (-out.ptr) % 64 + int(out_shift)
-        self._check(self.lib.wga_chain_filter(*args, out.ptr + lead))
-        self.sync()
-        if (int(total.value), int(kept.value)) != first:
-            raise _lib.WgaError("wga_chain_filter changed its counts in the second call")
-        got = out.numpy()
-        if not ((got[:lead] == 0xA5).all() and (got[lead + first[0]:] == 0xA5).all()):
-            raise _lib.WgaError("wga_chain_filter wrote outside d_out[0 .. total_bytes)")
-        return got[lead:lead + first[0]].tobytes(), first[1]
+        args = (self.ctx, _p(text), int(n_bytes), _p(heads), n_chains, _p(lines), _p(line_off), par.ctypes.data, _p(work))
+        text, (_, kept) = self._count_then_fill("wga_chain_filter", "counts", args, 2, out_shift)
+        return text, kept
 
     def chain2paf_count(self, text, n_bytes, heads, n_chains, lines, line_off, work):
         """K27: the count call of wga_chain2paf alone, total_bytes; it leaves its sums, plan and item scan in `work`"""
@@ -530,21 +538,8 @@ class Engine:
             if n_data_lines is None:
                 n_data_lines = int(line_off.numpy()[n_chains]) if n_chains else 0
             work = self.empty(max(int(self.lib.wga_chain2paf_work_bytes(n_chains, int(n_data_lines))), 16), np.uint8)
-        total = C.c_uint64(0)
-        args = (self.ctx, _p(text), int(n_bytes), _p(heads), n_chains, _p(lines), _p(line_off), _p(work), C.byref(total))
-        self._check(self.lib.wga_chain2paf(*args, None))
-        first = int(total.value)
-        guard = 64  # bytes around the text that the fill call must leave alone
-        out = self.upload(np.full(first + 2 * guard + 96, 0xA5, dtype=np.uint8))
-        lead = guard + (-out.ptr) % 64 + int(out_shift)
-        self._check(self.lib.wga_chain2paf(*args, out.ptr + lead))
-        self.sync()
-        if int(total.value) != first:
-            raise _lib.WgaError("wga_chain2paf changed its total in the second call")
-        got = out.numpy()
-        if not ((got[:lead] == 0xA5).all() and (got[lead + first:] == 0xA5).all()):
-            raise _lib.WgaError("wga_chain2paf wrote outside d_out[0 .. total_bytes)")
-        return got[lead:lead + first].tobytes()
+        args = (self.ctx, _p(text), int(n_bytes), _p(heads), n_chains, _p(lines), _p(line_off), _p(work))
+        return self._count_then_fill("wga_chain2paf", "total", args, 1, out_shift)[0]
 
     def dotplot_csv_count(self, n, segs, seg_off, tails, tail_off, work):
         """K26: the count call of wga_dotplot_csv alone, total_bytes; it leaves the scan of the row sizes in `work`"""
@@ -564,21 +559,8 @@ class Engine:
             if n_rows is None:
                 n_rows = int(seg_off.numpy()[n]) if n else 0
             work = self.empty(max(int(self.lib.wga_dotplot_csv_work_bytes(int(n_rows))), 16), np.uint8)
-        total = C.c_uint64(0)
-        args = (self.ctx, n, _p(segs), _p(seg_off), _p(tails), _p(tail_off), _p(work), C.byref(total))
-        self._check(self.lib.wga_dotplot_csv(*args, None))
-        first = int(total.value)
-        guard = 64  # bytes around the text that the fill call must leave alone
-        out = self.upload(np.full(first + 2 * guard + 96, 0xA5, dtype=np.uint8))
-        lead = guard + (-out.ptr) % 64 + int(out_shift)
-        self._check(self.lib.wga_dotplot_csv(*args, out.ptr + lead))
-        self.sync()
-        if int(total.value) != first:
-            raise _lib.WgaError("wga_dotplot_csv changed its total in the second call")
-        got = out.numpy()
-        if not ((got[:lead] == 0xA5).all() and (got[lead + first:] == 0xA5).all()):
-            raise _lib.WgaError("wga_dotplot_csv wrote outside d_out[0 .. total_bytes)")
-        return got[lead:lead + first].tobytes()
+        args = (self.ctx, n, _p(segs), _p(seg_off), _p(tails), _p(tail_off), _p(work))
+        return self._count_then_fill("wga_dotplot_csv", "total", args, 1, out_shift)[0]
 
     def cigar_tokenise_spans(self, n, text, beg, end, op_cnt=None, err=None, ops=None, op_off=None):
         """device tokeniser on spans text[beg[i], end[i]) (e.g. the cg:Z: texts inside a PAF file)"""
