@@ -5,7 +5,7 @@ placement of its output buffer (profiles/r02_k2_experiments.md, section 7), so b
   GPU box:  python scripts/gpu_k2_same_buffers.py run NAME[:param=val,...] ...  [--shape records,mean_ops,pool_mb]...
 
 Each candidate = a library build plus context parameters (e.g. expand_variant=2).  Every round times every candidate
-(6 launches each, library HIP events), rounds alternate the order; the table gives mean / min per candidate."""
+(6 launches each, library HIP events), rounds alternate the order; the table gives mean / min per candidate and every round's time."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -66,6 +66,7 @@ for rec, mean, pool in shapes:
     for label, eng, job, acc in jobs:
         m = sum(acc) / len(acc)
         print("  %-44s K2 mean %.3f ms  min %.3f  (%+.1f %% vs first)" % (label, m, min(acc), 100 * (m / base - 1)))
+        print("  %-44s rounds: %s" % ("", " ".join("%.4f" % v for v in acc)))
     for _l, eng, _j, _a in jobs:
         eng.close()
     del jobs, tb, out

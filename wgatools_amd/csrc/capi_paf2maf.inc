@@ -91,24 +91,39 @@ int wga_paf2maf_expand(wga_ctx* c, const wga_cigar_batch* b, const wga_cigar_cou
   void* ws;
   size_t rec_bytes = ((size_t)b->n * sizeof(wga_rec_desc) + 255) & ~(size_t)255;
   const size_t desc_bytes = (size_t)nt * sizeof(wga_tile_desc);
-  const size_t list_bytes = 256 + 2 * (size_t)nt * sizeof(u32); /* two counters + the lists of wide / huge tiles */
+  const size_t list_bytes = 2 * (size_t)nt * sizeof(u32); /* the lists of wide / huge tiles */
   const int variant = c->expand_variant >= 0 ? c->expand_variant : WGA_AUTO_LONG_VARIANT;
   c->expand_variant_used = variant;
-  const size_t plan_bytes = 0;
-  const size_t flag_bytes = variant == 3 ? (((size_t)nt + 255) & ~(size_t)255) : 0; /* streaming kernel: one byte per tile */
-  if ((rc = ctx_scratch(c, rec_bytes + desc_bytes + list_bytes + plan_bytes + flag_bytes, &ws))) return rc;
+  const bool stream = variant == 3;
+  const u32 job_tiles = job_tiles_for(c->expand_job_tiles, nt);
+  const u64 jobs = (nt + job_tiles - 1) / job_tiles;
+  /* cleared by ONE memset in front of the pre-pass: the lists' two counters, and for the streaming kernel a flag byte per tile
+   * and a skip word per job */
+  const size_t flag_bytes = stream ? (((size_t)nt + 255) & ~(size_t)255) : 0;
+  const size_t skip_bytes = stream ? (((size_t)jobs * sizeof(u32) + 255) & ~(size_t)255) : 0;
+  const size_t zero_bytes = 256 + flag_bytes + skip_bytes;
+  if ((rc = ctx_scratch(c, rec_bytes + desc_bytes + list_bytes + zero_bytes, &ws))) return rc;
   wga_rec_desc* recs = (wga_rec_desc*)ws;
   wga_tile_desc* tdesc = (wga_tile_desc*)((char*)ws + rec_bytes);
-  u32* const wide_counts = (u32*)((char*)ws + rec_bytes + desc_bytes);
-  u32* const wide_list = wide_counts + 64;
+  u32* const wide_list = (u32*)((char*)ws + rec_bytes + desc_bytes);
+  u32* const fast_list = wide_list + nt; /* the second half of the list area: tiles for v1's row emitters */
+  u32* const wide_counts = (u32*)((char*)ws + rec_bytes + desc_bytes + list_bytes);
+  u8* const tile_flag = stream ? (u8*)wide_counts + 256 : nullptr;
+  u32* const job_skip = stream ? (u32*)(tile_flag + flag_bytes) : nullptr;
+  /* part of the pre-pass for the streaming kernel: the tiles it leaves to v1 (records that are not clean, giant tiles) —
+   * k_rec_desc flags the tiles of such records, k_tile_base puts the flags into the descriptors, the jobs' skip words and
+   * v1's two lists */
+  if (stream) RT_CHECK(rt_memset(wide_counts, 0, zero_bytes, c->stream));
   WGA_LAUNCH(k_rec_desc, (b->n + 255u) / 256u, WGA_BLOCK, c->stream, b->n, d_counts,
              b->d_strand_neg, (const u64*)d_t_src_off, (const u64*)d_t_src_len,
              (const u64*)d_q_src_off, (const u64*)d_q_src_len, (const u64*)d_t_row_off,
-             (const u64*)d_q_row_off, recs);
+             (const u64*)d_q_row_off, recs, (const u64*)b->d_op_off, (u64)t_fa_bytes, (u64)q_fa_bytes, tile_flag);
   LAUNCH_CHECK();
   WGA_LAUNCH(k_tile_base, (u32)((nt + 255) / 256), WGA_BLOCK, c->stream, (const u64*)b->d_op_off,
-             (u64)b->n_ops, (const wga_tile_sum*)d_tile_ws, (const wga_rec_desc*)recs, tdesc, 0);
+             (u64)b->n_ops, (const wga_tile_sum*)d_tile_ws, (const wga_rec_desc*)recs, tdesc, 0, (const u8*)tile_flag,
+             job_tiles, c->expand_force_slow, job_skip, wide_counts, fast_list, wide_list);
   LAUNCH_CHECK();
+  if (stream) c->stream_counts = wide_counts;
   ExpandArgs a;
   a.ops = b->d_ops;
   a.op_off = (const u64*)b->d_op_off;
@@ -127,29 +142,14 @@ int wga_paf2maf_expand(wga_ctx* c, const wga_cigar_batch* b, const wga_cigar_cou
   a.tile_count = nullptr;
   a.tile_list = nullptr;
   a.n_rec = b->n;
-  a.job_tiles = job_tiles_for(c->expand_job_tiles, nt);
-  const bool stream = variant == 3;
-  /* when the gap-touching chunks are emitted (RowSrc::drain_min) */
+  a.job_tiles = job_tiles;
+  a.job_skip = job_skip;
   /* when v1's waves emit their queued gap-touching chunks (RowSrc::drain_min) */
   a.drain_min = c->expand_drain_min ? c->expand_drain_min : ((u64)t_fa_bytes + (u64)q_fa_bytes > WGA_DRAIN_POOL_BYTES ? 16u : 32u);
   c->expand_drain_min_used = a.drain_min;
-  u32* const fast_list = wide_list + nt; /* the second half of the list area: tiles for v1's row emitters */
-  if (stream) { /* part of the pre-pass: the tiles the streaming kernel leaves to v1 (records that are not clean, giant tiles) */
-    u8* const tile_flag = (u8*)ws + rec_bytes + desc_bytes + list_bytes + plan_bytes;
-    RT_CHECK(rt_memset(wide_counts, 0, 256, c->stream));
-    RT_CHECK(rt_memset(tile_flag, 0, flag_bytes, c->stream));
-    WGA_LAUNCH(k_stream_mark_rec, (b->n + 255u) / 256u, WGA_BLOCK, c->stream, b->n, (const wga_rec_desc*)recs,
-               (const u64*)b->d_op_off, (u64)t_fa_bytes, (u64)q_fa_bytes, tile_flag);
-    LAUNCH_CHECK();
-    WGA_LAUNCH(k_stream_mark_tile, (u32)((nt + 255) / 256), WGA_BLOCK, c->stream, tdesc, (u64)nt, (const u8*)tile_flag,
-               c->expand_force_slow, wide_counts, fast_list, wide_list);
-    LAUNCH_CHECK();
-    c->stream_counts = wide_counts;
-  }
   const uint32_t slot = c->ev_n % (uint32_t)wga_ctx::kTimingRing;
   if (c->timing) RT_CHECK(rt_event_record(c->ev[2 * slot], c->stream));
   if (stream) {
-    const u64 jobs = (nt + a.job_tiles - 1) / a.job_tiles;
     WGA_LAUNCH(k_paf2maf_expand_s, (u32)jobs, 128u, c->stream, a);
     LAUNCH_CHECK();
     const u32 side_grid = nt < 256 ? (u32)nt : 256u;

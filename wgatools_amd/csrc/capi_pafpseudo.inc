@@ -66,11 +66,16 @@ int wga_pafpseudo_fill(wga_ctx* c, const wga_cigar_batch* b, int base_mode, cons
   const size_t sums_bytes = kept ? 0 : ((size_t)b->n * sizeof(wga_class_sums) + 255) & ~(size_t)255;
   const size_t rec_bytes = stream ? ((size_t)b->n * sizeof(wga_rec_desc) + 255) & ~(size_t)255 : 0;
   const size_t desc_bytes = stream ? (size_t)nt * sizeof(wga_tile_desc) : 0;
-  const size_t list_bytes = stream ? 256 + 2 * (size_t)nt * sizeof(u32) : 0;
+  const size_t list_bytes = stream ? 2 * (size_t)nt * sizeof(u32) : 0;
+  const u32 job_tiles = job_tiles_for(c->expand_job_tiles, nt);
+  const u64 jobs = (nt + job_tiles - 1) / job_tiles;
+  /* cleared by one memset in front of the pre-pass: the lists' two counters, a flag byte per tile, a skip word per job */
   const size_t flag_bytes = stream ? (((size_t)nt + 255) & ~(size_t)255) : 0;
+  const size_t skip_bytes = stream ? (((size_t)jobs * sizeof(u32) + 255) & ~(size_t)255) : 0;
+  const size_t zero_bytes = stream ? 256 + flag_bytes + skip_bytes : 0;
   void* ws = nullptr;
-  if (tile_bytes + sums_bytes + rec_bytes + desc_bytes + list_bytes + flag_bytes)
-    if ((rc = ctx_scratch(c, tile_bytes + sums_bytes + rec_bytes + desc_bytes + list_bytes + flag_bytes, &ws))) return rc;
+  if (tile_bytes + sums_bytes + rec_bytes + desc_bytes + list_bytes + zero_bytes)
+    if ((rc = ctx_scratch(c, tile_bytes + sums_bytes + rec_bytes + desc_bytes + list_bytes + zero_bytes, &ws))) return rc;
   c->pseudo_counts = nullptr;
   if (kept) {
     tiles = t.tiles; /* what wga_cigar_class_sums left for this batch */
@@ -106,20 +111,18 @@ int wga_pafpseudo_fill(wga_ctx* c, const wga_cigar_batch* b, int base_mode, cons
     char* const base = (char*)ws + tile_bytes + sums_bytes;
     wga_rec_desc* const recs = (wga_rec_desc*)base;
     wga_tile_desc* const tdesc = (wga_tile_desc*)(base + rec_bytes);
-    u32* const counts = (u32*)(base + rec_bytes + desc_bytes);
-    u32* const list_wide = counts + 64;
+    u32* const list_wide = (u32*)(base + rec_bytes + desc_bytes);
     u32* const list_fast = list_wide + nt;
-    u8* const tile_flag = (u8*)(base + rec_bytes + desc_bytes + list_bytes);
-    RT_CHECK(rt_memset(counts, 0, 256, c->stream));
-    RT_CHECK(rt_memset(tile_flag, 0, flag_bytes, c->stream));
+    u32* const counts = (u32*)(base + rec_bytes + desc_bytes + list_bytes);
+    u8* const tile_flag = (u8*)counts + 256;
+    u32* const job_skip = (u32*)(tile_flag + flag_bytes);
+    RT_CHECK(rt_memset(counts, 0, zero_bytes, c->stream));
     WGA_LAUNCH(k_pseudo_rec_desc, (b->n + 255u) / 256u, WGA_BLOCK, c->stream, b->n, (const wga_class_sums*)rec_sums, b->d_strand_neg,
                base_mode ? (const u64*)d_q_src_off : nullptr, base_mode ? (const u64*)d_q_src_len : nullptr, (const u64*)d_skip,
                (const u64*)d_dst_off, (const u64*)b->d_op_off, (u64)q_fa_bytes, recs, tile_flag);
     LAUNCH_CHECK();
     WGA_LAUNCH(k_tile_base, (u32)((nt + 255) / 256), WGA_BLOCK, c->stream, (const u64*)b->d_op_off, (u64)b->n_ops,
-               (const wga_tile_sum*)tiles, (const wga_rec_desc*)recs, tdesc, 1);
-    LAUNCH_CHECK();
-    WGA_LAUNCH(k_stream_mark_tile, (u32)((nt + 255) / 256), WGA_BLOCK, c->stream, tdesc, (u64)nt, (const u8*)tile_flag, 0, counts,
+               (const wga_tile_sum*)tiles, (const wga_rec_desc*)recs, tdesc, 1, (const u8*)tile_flag, job_tiles, 0, job_skip, counts,
                list_fast, list_wide);
     LAUNCH_CHECK();
     c->pseudo_counts = counts;
@@ -135,8 +138,8 @@ int wga_pafpseudo_fill(wga_ctx* c, const wga_cigar_batch* b, int base_mode, cons
     e.out = d_out;
     e.diag = d_diag;
     e.n_rec = b->n;
-    e.job_tiles = job_tiles_for(c->expand_job_tiles, nt);
-    const u64 jobs = (nt + e.job_tiles - 1) / e.job_tiles;
+    e.job_tiles = job_tiles;
+    e.job_skip = job_skip;
     if (base_mode)
       WGA_LAUNCH(k_pafpseudo_stream, (u32)((jobs + 1) / 2), 128u, c->stream, e);
     else

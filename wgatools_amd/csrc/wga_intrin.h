@@ -233,4 +233,37 @@ __device__ __forceinline__ u32 bfi_b32(u32 mask, u32 a, u32 b) { return (a & mas
 
 #endif /* !WGA_EMU */
 
+/* ---- scalar reads of read-only arrays -------------------------------------------------------------------------------
+ * WGA_RO32 / WGA_RO64 / wga_ro16: one u32 / u64 / aligned 16-byte group of a device array, read through the constant address
+ * space: with a wave-uniform address that is an s_load_dword[x2|x4] — the value arrives in SGPRs (no v_readfirstlane, no VGPR
+ * temporary) and its wait is lgkmcnt, so it does NOT wait for the vector stores the wave has in flight (vmcnt counts stores as
+ * well as loads: a global_load + vmcnt(0) behind a burst of row stores waits for their write acknowledgements too).
+ * THE RULE: only for arrays that NO thread of the running kernel writes (the scalar cache is not coherent with vector stores
+ * of the same launch; what earlier kernels of the stream wrote is fine), and only with wave-uniform addresses (anything else
+ * becomes a per-lane load, or a readfirstlane loop).  Never for `diag` or anything else written during the kernel.
+ * Under the emulator and in every host compile these are plain loads. */
+struct wga_u64x2 {
+  u64 x, y;
+};
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(WGA_EMU)
+#define WGA_RO_SPACE __attribute__((address_space(4)))
+#define WGA_RO32(p) (*(const WGA_RO_SPACE u32*)(u64)(const u32*)(p))
+#define WGA_RO64(p) (*(const WGA_RO_SPACE u64*)(u64)(const u64*)(p))
+__device__ __forceinline__ wga_u64x2 wga_ro16(const u64* p) {
+  typedef u64 u64x2_v __attribute__((vector_size(16)));
+  const u64x2_v v = *(const WGA_RO_SPACE u64x2_v*)(u64)p;
+  return {v[0], v[1]};
+}
+/* the values of several such reads are wanted HERE: keeps the compiler from moving a read behind a branch that only needs
+ * another one (a second, dependent round trip) */
+#define WGA_RO_HERE2(a, b) asm volatile("" ::"s"(a), "s"(b))
+#define WGA_RO_HERE4(a, b, c, d) asm volatile("" ::"s"(a), "s"(b), "s"(c), "s"(d))
+#else
+#define WGA_RO32(p) (*(const u32*)(p))
+#define WGA_RO64(p) (*(const u64*)(p))
+__device__ __forceinline__ wga_u64x2 wga_ro16(const u64* p) { return {p[0], p[1]}; }
+#define WGA_RO_HERE2(a, b) ((void)0)
+#define WGA_RO_HERE4(a, b, c, d) ((void)0)
+#endif
+
 #endif /* WGA_INTRIN_H */

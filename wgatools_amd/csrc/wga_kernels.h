@@ -1194,7 +1194,8 @@ __global__ __launch_bounds__(256) void k_rec_desc(u32 n, const wga_cigar_counts*
                                                   const u8* strand_neg, const u64* t_src_off,
                                                   const u64* t_src_len, const u64* q_src_off,
                                                   const u64* q_src_len, const u64* t_row_off,
-                                                  const u64* q_row_off, wga_rec_desc* out) {
+                                                  const u64* q_row_off, wga_rec_desc* out, const u64* op_off,
+                                                  u64 t_fa_bytes, u64 q_fa_bytes, u8* tile_flag) {
   u32 r = blockIdx.x * 256u + threadIdx.x;
   if (r >= n) return;
   const wga_cigar_counts cn = counts[r];
@@ -1215,6 +1216,16 @@ __global__ __launch_bounds__(256) void k_rec_desc(u32 n, const wga_cigar_counts*
   d.neg = (strand_neg[r] != 0 ? 1u : 0u) | (d.t_src_len + d.I_total > d.L ? 2u : 0u) | (d.q_src_len + d.D_total > d.L ? 4u : 0u) |
           ((d.t_src_len + d.I_total < d.L || d.q_src_len + d.D_total < d.L) ? 8u : 0u);
   out[r] = d;
+  /* the streaming row kernel's pre-pass (tile_flag != NULL; wga_kernels_k2s.h): a record that is not clean (flags 2 / 4 / 8), or
+   * whose slices lie within 32 bytes of an edge of their pool (that kernel's sixteen-byte windows reach over a slice's ends; v1
+   * reads such rows byte by byte), marks every tile it has ops in */
+  if (!tile_flag) return;
+  const bool inside = d.t_src_off >= 32ull && d.t_src_off + d.t_src_len + 32ull <= t_fa_bytes && d.q_src_off >= 32ull &&
+                      d.q_src_off + d.q_src_len + 32ull <= q_fa_bytes;
+  if ((d.neg & 0xEull) == 0ull && inside) return;
+  const u64 a = op_off[r], b = op_off[r + 1];
+  if (b <= a) return;
+  for (u64 t = a / WGA_TILE; t <= (b - 1) / WGA_TILE; t++) tile_flag[t] = 1;
 }
 
 /* One thread per tile: class sums of the tile's first record before the tile = tail of the tile
@@ -1223,9 +1234,18 @@ __global__ __launch_bounds__(256) void k_rec_desc(u32 n, const wga_cigar_counts*
  * beyond 64 kop) are summed by the whole wave, one such tile at a time. */
 /* pseudo != 0 (pafpseudo's rows, wga_kernels_k2s.h): S ops count as I (both skip query bases without a column), and a tile's
  * "columns" are everything it makes a row kernel walk (M = X I D S). */
+/* The streaming row kernel's pre-pass (tile_flag != NULL): a tile one of its records flagged (k_rec_desc / k_pseudo_rec_desc),
+ * a tile wider than that kernel takes, and every tile under `all_slow` is left to v1: WGA_S_SKIP in its descriptor, bit
+ * (tile - first tile of its job) in the job's word of job_skip (all ones under all_slow) — the one word a wave of the streaming
+ * kernel reads — and an entry in v1's lists: counts[0] / list_fast its row emitters, counts[1] / list_slow (beyond 2^31 columns,
+ * all_slow) the op-serial walk.  The flags, the counters and the job words are cleared in front of the pre-pass. */
+#define WGA_S_MAX_TILE_COLS (1ull << 24) /* wider tiles are left to v1 */
+#define WGA_S_SKIP 0x100u                /* wga_tile_desc::neg: the streaming kernel leaves this tile to v1 */
 __global__ __launch_bounds__(256) void k_tile_base(const u64* op_off, u64 n_ops,
                                                    const wga_tile_sum* tiles,
-                                                   const wga_rec_desc* recs, wga_tile_desc* descs, int pseudo) {
+                                                   const wga_rec_desc* recs, wga_tile_desc* descs, int pseudo,
+                                                   const u8* tile_flag, u32 job_tiles, int all_slow, u32* job_skip,
+                                                   u32* counts, u32* list_fast, u32* list_slow) {
   const u32 lane = threadIdx.x & 63u;
   const u64 g = (u64)blockIdx.x * 256 + threadIdx.x;
   const u64 tile_start = g * WGA_TILE;
@@ -1279,6 +1299,17 @@ __global__ __launch_bounds__(256) void k_tile_base(const u64* op_off, u64 n_ops,
   d.tile_cols = ts.tot[CLS_MX] + ts.tot[CLS_I] + ts.tot[CLS_D] + (pseudo ? ts.tot[CLS_S] : 0ull);
   d.rec = (u32)ts.rec;
   d.neg = (u32)rd.neg;
+  if (tile_flag) {
+    const bool slow = all_slow || d.tile_cols > WGA_FAST_COL_LIMIT;
+    if (slow || tile_flag[g] || d.tile_cols > WGA_S_MAX_TILE_COLS) {
+      d.neg |= WGA_S_SKIP;
+      atomicOr(&job_skip[g / job_tiles], all_slow ? 0xFFFFFFFFu : 1u << (u32)(g % job_tiles));
+      if (slow)
+        list_slow[atomicAdd(&counts[1], 1u)] = (u32)g;
+      else
+        list_fast[atomicAdd(&counts[0], 1u)] = (u32)g;
+    }
+  }
   d.b_mx = p_mx;
   d.b_i = p_i;
   d.b_d = p_d;
@@ -1315,6 +1346,7 @@ struct ExpandArgs {
   const u32* tile_list;
   u32 n_rec;    /* records of the batch (op_off has n_rec + 1 entries) */
   u32 job_tiles;   /* streaming kernel: consecutive tiles one wave walks as one stream */
+  const u32* job_skip; /* ... one word per job: bit k = tile (first tile of the job) + k is left to v1 (k_tile_base) */
 };
 
 #ifndef WGA_K2_BLOCKS

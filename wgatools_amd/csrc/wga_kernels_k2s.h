@@ -33,8 +33,24 @@
  *
  * What it does NOT do: tiles whose records are not "clean" (a slice longer or shorter than the CIGAR consumes: tails to
  * append, rows that stop early, String::insert_str panics), records within 32 bytes of a pool's edge and tiles wider than
- * 2^24 columns are marked by a pre-pass (k_stream_mark_*) and left to v1 (k_paf2maf_expand_list), as the window kernel
- * leaves its giant tiles there.
+ * 2^24 columns are marked by the pre-pass (k_rec_desc / k_pseudo_rec_desc flag them, k_tile_base lists them) and left to v1
+ * (k_paf2maf_expand_list), as the window kernel leaves its giant tiles there.
+ *
+ * Descriptor reads.  A wave's time is its serial path (time x resident waves is constant), and every wave-uniform value it
+ * fetches between two super-steps is a memory round trip on that path with nothing of the wave to overlap it.  They are all
+ * SCALAR reads (WGA_RO32 / WGA_RO64 / wga_ro16, wga_intrin.h: s_load through the constant address space) of arrays the
+ * pre-pass wrote and this kernel never writes — tdesc, recs, op_off, job_skip; the kernel has no global_load left:
+ *   * stream start (once per job, and behind every run of tiles left to v1): the job's skip word is read at the top of the
+ *     wave; the fields of wga_tile_desc are read together, the sums in front of the tile unconditionally — one round trip
+ *     where there were three dependent ones;
+ *   * tile border (every 1 024 ops): bit (tile - first tile of the job) of the skip word, a register.  No memory access
+ *     (it was a load of tdesc[t].neg and a wait for it and for the stores in front, to find 5 tiles of 487 536);
+ *   * record switch: the next record is rec + 1 unless that one has no ops, so op_off[rec + 2] and the row's fields of
+ *     recs[rec + 1] are requested together and a switch is one round trip (it was two, the second waiting for the first);
+ *     a record without ops sends the loop round again.  WGA_RO_HERE keeps the compiler from sinking the fields' reads behind
+ *     the loop, which would make them a second trip again.
+ * What this does not remove: the compiler drains vmcnt (stores included) where the outer loop closes — the ops on their way
+ * live in VGPRs that are copied there — so a wave still waits for its stores once per intake and per switch.
  */
 #ifndef WGA_KERNELS_K2S_H
 #define WGA_KERNELS_K2S_H
@@ -42,48 +58,16 @@
 #include "wga_kernels.h"
 
 #define WGA_S_FIFO 320u                 /* gap events waiting for their columns to be written (256 of one intake + what is left) */
-#define WGA_S_MAX_TILE_COLS (1ull << 24) /* wider tiles are left to v1 */
 #define WGA_S_MAX_JOB_TILES 32u          /* 32 x 2^24 columns stay below 2^31 */
-#define WGA_S_SKIP 0x100u                /* wga_tile_desc::neg: the streaming kernel leaves this tile to v1 */
 #define WGA_S_U 4u /* kilobytes of a row one super-step writes: the queued granules of that many share one round of the merge code */
 #define WGA_S_WAVE_BYTES ((WGA_S_FIFO + 4u) * 8u + 1024u + 1024u + 256u + 272u + 16u)
 #ifndef WGA_AUTO_LONG_VARIANT
 #define WGA_AUTO_LONG_VARIANT 3 /* the row kernel of every other batch when "expand_variant" is -1: this one (0 = v1, for A/B builds) */
 #endif
 
-/* ---- pre-pass: which tiles the streaming kernel leaves to v1 ------------------------------------------------------- */
-/* one thread per record: a record that is not clean (k_rec_desc flags 2 / 4 / 8), or whose slices lie within 32 bytes of an
- * edge of their pool (the streaming kernel's sixteen-byte windows reach over a slice's ends; v1 reads such rows byte by byte),
- * marks every tile it has ops in */
-__global__ __launch_bounds__(256) void k_stream_mark_rec(u32 n, const wga_rec_desc* recs, const u64* op_off, u64 t_fa_bytes,
-                                                         u64 q_fa_bytes, u8* tile_flag) {
-  const u32 r = blockIdx.x * 256u + threadIdx.x;
-  if (r >= n) return;
-  const wga_rec_desc d = recs[r];
-  const bool inside = d.t_src_off >= 32ull && d.t_src_off + d.t_src_len + 32ull <= t_fa_bytes && d.q_src_off >= 32ull &&
-                      d.q_src_off + d.q_src_len + 32ull <= q_fa_bytes;
-  if ((d.neg & 0xEull) == 0ull && inside) return;
-  const u64 a = op_off[r], b = op_off[r + 1];
-  if (b <= a) return;
-  for (u64 t = a / WGA_TILE; t <= (b - 1) / WGA_TILE; t++) tile_flag[t] = 1;
-}
-/* one thread per tile: the flag goes into the tile's descriptor; flagged tiles are listed for v1's row emitters, tiles beyond
- * 2^31 columns for its op-serial walk.  counts[0] / list_fast: v1 fast path, counts[1] / list_slow: op-serial. */
-__global__ __launch_bounds__(256) void k_stream_mark_tile(wga_tile_desc* descs, u64 nt, const u8* tile_flag, int all_slow,
-                                                          u32* counts, u32* list_fast, u32* list_slow) {
-  const u64 g = (u64)blockIdx.x * 256 + threadIdx.x;
-  if (g >= nt) return;
-  const u64 cols = descs[g].tile_cols;
-  const bool slow = all_slow || cols > WGA_FAST_COL_LIMIT;
-  if (slow || tile_flag[g] || cols > WGA_S_MAX_TILE_COLS) {
-    descs[g].neg |= WGA_S_SKIP;
-    if (slow)
-      list_slow[atomicAdd(&counts[1], 1u)] = (u32)g;
-    else
-      list_fast[atomicAdd(&counts[0], 1u)] = (u32)g;
-  }
-}
-
+/* ---- pre-pass: which tiles the streaming kernel leaves to v1 -------------------------------------------------------
+ * k_rec_desc (paf2maf) / k_pseudo_rec_desc (pafpseudo) flag the tiles of records that are not clean or lie at a pool's edge,
+ * k_tile_base turns the flags (and the tiles' widths) into WGA_S_SKIP, the jobs' skip words and v1's lists (wga_kernels.h). */
 /* pafpseudo (MODE 2 below): the record descriptors of its base-mode rows in the row kernel's format.  The row of record r is
  * the query slice in TARGET coordinates (M = X D columns); column x >= skip goes to out + dst_off + x - skip, so the "row
  * offset" is dst_off - skip (it may wrap below zero: only columns >= skip are written) and skip rides in the unused t_src_len.
@@ -174,7 +158,9 @@ __device__ __forceinline__ u32 stream_glen(u32 c0, u32 c1) { /* gap characters o
 }
 __device__ __forceinline__ u32 stream_symbol(u32 cu) { return (cu & 1u) ? 0x2D2D2D2Du : 0x30303030u; } /* the run's character */
 template <int MODE>
-__device__ __forceinline__ void stream_row(const ExpandArgs& a, u8* const lds, const u32 lane, const u64 t0, const u64 t1) {
+__device__ __forceinline__ void stream_row(const ExpandArgs& a, u8* const lds, const u32 lane, const u64 job, const u64 t0,
+                                           const u64 t1) {
+  const u32 skipm = WGA_RO32(a.job_skip + job); /* bit k: tile t0 + k is v1's (one scalar read; tile borders test a register) */
   u32* const s_fifo = (u32*)lds;                                 /* (WGA_S_FIFO + 4) x (start column, cum)    */
   u32x4_a16* const s_P = (u32x4_a16*)(s_fifo + 2u * (WGA_S_FIFO + 4u)); /* 64 granules put together by the queue's lanes */
   u32* const s_q = (u32*)(s_P + 64);                             /* the queue: (event index, granule) of up to 256 granules */
@@ -500,28 +486,36 @@ __device__ __forceinline__ void stream_row(const ExpandArgs& a, u8* const lds, c
       u32 C_a, cum_a;
       if (bnd) {
         const u64 bnd_op = job_lo + re;
-        u64 ren;
-        do { /* records without ops have no rows here (v1 walks past them as well) */
+        u64 ren, skip = 0;
+        wga_u64x2 src;
+        u32 negw;
+        /* the next record's end and its row's fields: scalar reads issued together, ONE round trip (the fields used to be a
+         * second one that had to wait for the record's index).  Records without ops have no rows here (v1 walks past them as
+         * well): only they make this loop go round again */
+        do {
           rec++;
-          ren = WGA_UNI64(a.op_off[rec + 1]);
+          const wga_rec_desc* const rd = a.recs + rec;
+          ren = WGA_RO64(a.op_off + rec + 1);
+          row_off = WGA_RO64(QROW ? &rd->q_row_off : &rd->t_row_off);
+          src = wga_ro16(QROW ? &rd->q_src_off : &rd->t_src_off); /* offset and length lie side by side */
+          negw = WGA_RO32((const u32*)&rd->neg);
+          if (TCOORD) skip = WGA_RO64(&rd->t_src_len);
+          WGA_RO_HERE4(ren, row_off, src.x, src.y);
+          WGA_RO_HERE2(negw, skip);
         } while (ren <= bnd_op);
         re = ren - job_lo > (u64)q_end ? q_end : (u32)(ren - job_lo);
-        const wga_rec_desc* const rd = a.recs + rec;
-        row_off = WGA_UNI64(QROW ? rd->q_row_off : rd->t_row_off);
-        src_off = WGA_UNI64(QROW ? rd->q_src_off : rd->t_src_off);
-        src_len = WGA_UNI64(QROW ? rd->q_src_len : rd->t_src_len);
-        neg = (WGA_UNI64(rd->neg) & 1ull) != 0ull;
+        src_off = src.x;
+        src_len = src.y;
+        neg = (negw & 1u) != 0u;
         x_a = 0;
         sb = 0;
         C_a = C_b;
         cum_a = cum_b;
-        if (TCOORD) { /* the columns in front of `skip` (kept in the descriptor's unused t_src_len) are not written */
-          const u64 skip = WGA_UNI64(rd->t_src_len);
+        if (TCOORD) /* the columns in front of `skip` (kept in the descriptor's unused t_src_len) are not written */
           C_min = C_a + (u32)(skip < 0x40000000ull ? skip : 0x40000000ull);
-        }
       } else {
         /* (re)start: the next tile that is this kernel's */
-        while (t < t1 && (WGA_UNI32(a.tdesc[t].neg) & WGA_S_SKIP)) t++;
+        while (t < t1 && ((skipm >> (u32)(t - t0)) & 1u)) t++;
         if (t >= t1) break;
         const wga_tile_desc* const td = a.tdesc + t;
         const u64 tile_start = t * WGA_TILE;
@@ -535,21 +529,23 @@ __device__ __forceinline__ void stream_row(const ExpandArgs& a, u8* const lds, c
           s_fifo[2u * lane] = 0u;
           s_fifo[2u * lane + 1u] = 0u;
         }
-        rec = WGA_UNI32(td->rec);
-        const u64 ren = WGA_UNI64(td->re), rs = WGA_UNI64(td->rs);
+        /* the tile's descriptor: scalar reads issued together, one round trip (the sums in front are read whether the record
+         * began in an earlier tile or not: no read depends on another) */
+        rec = WGA_RO32(&td->rec);
+        const u64 ren = WGA_RO64(&td->re), rs = WGA_RO64(&td->rs);
+        const u64 d_mx = WGA_RO64(&td->b_mx), d_i = WGA_RO64(&td->b_i), d_d = WGA_RO64(&td->b_d);
+        row_off = WGA_RO64(QROW ? &td->q_row_off : &td->t_row_off);
+        src_off = WGA_RO64(QROW ? &td->q_src_off : &td->t_src_off);
+        src_len = WGA_RO64(QROW ? &td->q_src_len : &td->t_src_len);
+        neg = (WGA_RO32(&td->neg) & 1u) != 0u;
+        const u64 skip = TCOORD ? WGA_RO64(&td->t_src_len) : 0ull;
         re = ren - job_lo > (u64)q_end ? q_end : (u32)(ren - job_lo);
         const bool cont = rs < tile_start; /* the record began in an earlier tile */
-        const u64 b_mx = cont ? WGA_UNI64(td->b_mx) : 0ull, b_i = cont ? WGA_UNI64(td->b_i) : 0ull,
-                  b_d = cont ? WGA_UNI64(td->b_d) : 0ull;
-        row_off = WGA_UNI64(QROW ? td->q_row_off : td->t_row_off);
-        src_off = WGA_UNI64(QROW ? td->q_src_off : td->t_src_off);
-        src_len = WGA_UNI64(QROW ? td->q_src_len : td->t_src_len);
-        neg = (WGA_UNI32(td->neg) & 1u) != 0u;
+        const u64 b_mx = cont ? d_mx : 0ull, b_i = cont ? d_i : 0ull, b_d = cont ? d_d : 0ull;
         x_a = TCOORD ? b_mx + b_d : b_mx + b_i + b_d; /* pafpseudo: I (and S, folded into b_i) are no columns */
         sb = QROW ? b_mx + b_i : b_mx + b_d;
         C_a = cum_a = 0u;
         if (TCOORD) {
-          const u64 skip = WGA_UNI64(td->t_src_len);
           const u64 ahead = skip > x_a ? skip - x_a : 0ull;
           C_min = (u32)(ahead < 0x40000000ull ? ahead : 0x40000000ull);
         }
@@ -609,7 +605,7 @@ __device__ __forceinline__ void stream_row(const ExpandArgs& a, u8* const lds, c
     }
     if ((q & (WGA_TILE - 1u)) == 0u) { /* a tile border: is the next tile this kernel's? */
       t = (job_lo + q) / WGA_TILE;
-      if (WGA_UNI32(a.tdesc[t].neg) & WGA_S_SKIP) { /* v1's: finish what is under way, start again behind it */
+      if ((skipm >> (u32)(t - t0)) & 1u) { /* v1's: finish what is under way, start again behind it */
         if (pos != C_known) {
           fin = true;
           continue;
@@ -718,9 +714,9 @@ __device__ __forceinline__ void expand_stream(const ExpandArgs& a) {
   const u64 t1 = t0 + a.job_tiles < nt ? t0 + a.job_tiles : nt;
   u8* const lds = (u8*)s_mem + wave * WGA_S_WAVE_BYTES;
   if (wave == 0u)
-    stream_row<0>(a, lds, lane, t0, t1);
+    stream_row<0>(a, lds, lane, job, t0, t1);
   else
-    stream_row<1>(a, lds, lane, t0, t1);
+    stream_row<1>(a, lds, lane, job, t0, t1);
 }
 /* pafpseudo's rows (K6): every wave of the block walks a job of its own */
 template <int MODE>
@@ -728,10 +724,11 @@ __device__ __forceinline__ void pseudo_stream(const ExpandArgs& a) {
   __shared__ u32x4_a16 s_mem[2u * WGA_S_WAVE_BYTES / 16u];
   const u32 lane = threadIdx.x & 63u, wave = WGA_WAVE_ID(threadIdx.x);
   const u64 nt = (a.n_ops + WGA_TILE - 1) / WGA_TILE;
-  const u64 t0 = (2u * xcd_job_of_block() + wave) * a.job_tiles;
+  const u64 job = 2u * xcd_job_of_block() + wave;
+  const u64 t0 = job * a.job_tiles;
   if (t0 >= nt) return;
   const u64 t1 = t0 + a.job_tiles < nt ? t0 + a.job_tiles : nt;
-  stream_row<MODE>(a, (u8*)s_mem + wave * WGA_S_WAVE_BYTES, lane, t0, t1);
+  stream_row<MODE>(a, (u8*)s_mem + wave * WGA_S_WAVE_BYTES, lane, job, t0, t1);
 }
 #ifndef WGA_S_WAVES_PER_SIMD
 #define WGA_S_WAVES_PER_SIMD 5 /* launch bound: 96 VGPRs (the natural need is 102: two spill slots), LDS allows 31 waves per CU; 4: 6.0 ms, 5: 5.66 ms, 6 (61 spill slots): 7.4 ms */
