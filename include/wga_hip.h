@@ -872,6 +872,47 @@ uint64_t wga_chain2paf_work_bytes(uint64_t n_chains, uint64_t n_data_lines);
 int wga_chain2paf(wga_ctx*, const uint8_t* d_text, uint64_t n_bytes, const wga_chain_head* d_heads, uint64_t n_chains,
                   const uint64_t* d_lines, const uint64_t* d_line_off, void* d_work, uint64_t* total_bytes, uint8_t* d_out);
 
+/* ---- K28: `maf2paf` — the PAF record writer (replaces the record loop of the host's maf2paf_rows,
+ *      wgatools_amd/host/cmd_maf2paf.inc of the commit before it: the run offsets, the text sizes and the counters of every block
+ *      downloaded, twelve columns and NM:i: per record printed by host threads and scattered around the CIGAR text; in the
+ *      reference the record of maf.rs:484-520, written by the csv writer of converter.rs:29-54) --------------------------------
+ * d_counts[n] and d_runs, d_run_off[n + 1], d_cols[n] are wga_maf_pair_stat's results and arguments for n blocks, or arrays of
+ * the same meaning: d_run_off[0] = 0, d_run_off ascending, d_run_off[n] = the number of runs (the call reads it from there), a
+ * run = start column << 3 | class.  d_heads[n] holds the numbers the caller prints and the spans of the two names inside
+ * d_names[0 .. n_name_bytes).  For every block r, in input order, one record:
+ *   <qname>\t<q0>\t<q1>\t<q2>\t<+|->\t<tname>\t<t0>\t<t1>\t<t2>\t<matches>\t<block_length>\t255\tNM:i:<block_length - matches>\tcg:Z:
+ *   then per run   <length><=|I|D|X>
+ *   then           \n
+ * The numbers are q[0 .. 2] and t[0 .. 2] unchanged, in canonical decimal.  matches = d_counts[r].match, block_length = match +
+ * mismatch + ins_bp + inv_ins_bp + del_bp + inv_del_bp of d_counts[r], NM = block_length - matches, all mod 2^64.  A run's
+ * length is the next run's start (d_cols[r] for the block's last run) minus its own; its letter is its class, the low 3 bits:
+ * 0 `=`, 1 `I`, 2 `D`, anything else `X` — byte for byte what wga_maf_runs_cigar_text prints for the same arrays.  A name is
+ * written as the csv writer with a tab delimiter and QuoteStyle::Necessary writes it: as it is, unless it holds a tab, a
+ * quote, CR or LF; then between quotes with every quote inside doubled.  A name whose span does not lie inside d_names is
+ * written as empty.  A block with d_run_off[r] == d_run_off[r + 1] is legal here: its record ends in "cg:Z:\n".
+ *   d_out == NULL: the sums, the byte count of every head and run and their places (d_work); *total_bytes (a host value: the
+ *                  call reads d_run_off[n], then the total).
+ *   otherwise    : the text at d_out[0 .. *total_bytes) with the sums and places of the first call; d_out may have any
+ *                  alignment, the caller leaves 16 bytes of slack behind it; no byte in front of d_out and none from d_out +
+ *                  *total_bytes + 16 on is touched (this implementation writes none outside the text).  *total_bytes is read as
+ *                  the first call left it, so the two calls take the same arguments.
+ * n == 0: total 0, nothing written.  WGA_E_INVALID_ARG: n + runs > 0xFFFFFFF0 (refused before anything is read beyond
+ * d_run_off[n]), a null array with n > 0 (d_names only when n_name_bytes > 0, d_runs only when there are runs), a null d_work.
+ * d_work: wga_maf2paf_work_bytes(n, n_runs) bytes of device memory, 8-byte aligned, shared by the two calls
+ * = 8 * (3 n + N + 1 + N / 1024 + 4) with N = n + n_runs: 24 bytes per block (the head's byte count and the two sums), 8 per
+ * block and run (the scan of the item sizes), plus the scan's partial sums. */
+typedef struct {
+  uint64_t q[3];                 /* query_length, query_start, query_end as printed */
+  uint64_t t[3];                 /* target_length, target_start, target_end as printed */
+  uint64_t qname_off, tname_off; /* spans of d_names */
+  uint32_t qname_len, tname_len;
+  uint8_t strand_neg, pad[7];
+} wga_maf2paf_head; /* 80 bytes */
+uint64_t wga_maf2paf_work_bytes(uint64_t n, uint64_t n_runs);
+int wga_maf2paf(wga_ctx*, uint32_t n, const uint8_t* d_names, uint64_t n_name_bytes, const wga_maf2paf_head* d_heads,
+                const wga_cigar_counts* d_counts, const uint64_t* d_runs, const uint64_t* d_run_off, const uint64_t* d_cols,
+                void* d_work, uint64_t* total_bytes, uint8_t* d_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,7 +26,8 @@
 #include "wga_k7_paf_call.h"
 #include "wga_k8_tokenise.h"
 #include "wga_text_out.h"      /* what the text writers share: decimals, sinks, the staged stretch */
-#include "wga_chain_items.h"   /* the items of a stream of chains (K25, K27), a data line's CIGAR text (K11, K27) */
+#include "wga_chain_items.h"   /* the items of a stream of chains (K25, K27, K28), a data line's CIGAR text (K11, K27) */
+#include "wga_paf_head.h"      /* a PAF record's columns and csv quoting (K27, K28) */
 #include "wga_k9_bed.h"
 #include "wga_k10_chain.h"
 #include "wga_k11_bridges.h"
@@ -44,6 +45,7 @@
 #include "wga_k25_chain_write.h" /* K25: the chain record writer of filter on chain */
 #include "wga_k26_dotplot_csv.h" /* K26: the base-level csv rows of dotplot */
 #include "wga_k27_chain2paf.h" /* K27: the PAF record writer of chain2paf */
+#include "wga_k28_maf2paf.h" /* K28: the PAF record writer of maf2paf */
 
 /* A grow-only device buffer of a context.  reserve() leaves it with room for `need` bytes: one that is too small is freed
  * behind the work of the context's stream and allocated anew with `grow` (>= need) bytes — every site has its own growth rule —,
@@ -585,6 +587,7 @@ int wga_ctx_get_param(wga_ctx* c, const char* name, int64_t* value) {
 #include "capi_text.inc"
 #include "capi_chain_write.inc"
 #include "capi_chain2paf.inc"
+#include "capi_maf2paf.inc"
 #include "capi_dotplot_csv.inc"
 #include "capi_pafcov.inc"
 #include "capi_pafpseudo.inc"

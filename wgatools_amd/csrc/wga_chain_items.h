@@ -1,5 +1,5 @@
 /* wga_chain_items.h — what kernels over chain records share: the items of a stream of chains (K25's and K27's formats derive from
- * ChainItemBase) and a data line's part of chain2paf's CIGAR text (K11 and K27). */
+ * ChainItemBase; so does K28's, with a MAF block's runs in place of a chain's data lines) and a data line's part of chain2paf's CIGAR text (K11 and K27). */
 #ifndef WGA_CHAIN_ITEMS_H
 #define WGA_CHAIN_ITEMS_H
 
@@ -49,13 +49,13 @@ __device__ __forceinline__ ChainItem chain_item(const ChainItemBase& it, u64 x, 
   i.last = i.head ? first == end : i.l + 1u == end;
   return i;
 }
-/* item i of chain r of a format F over ChainItemBase with head_emit(s, r), line_emit(s, l) and end_emit(s): its bytes (`head`
+/* item i of chain r of a format F over ChainItemBase with head_emit(s, r), line_emit(s, l, r) and end_emit(s): its bytes (`head`
  * = the plan's bytes of r's head: names are read once), and its text */
 template <typename F>
-__device__ __forceinline__ u64 chain_item_size(const F& f, const ChainItem& i, u64 head) {
+__device__ __forceinline__ u64 chain_item_size(const F& f, const ChainItem& i, u32 r, u64 head) {
   if (i.none) return 0u;
   TextCount c;
-  if (i.head) c.n = head; else f.line_emit(c, i.l);
+  if (i.head) c.n = head; else f.line_emit(c, i.l, r);
   if (i.last) f.end_emit(c);
   return c.n;
 }
@@ -63,7 +63,7 @@ template <typename F, typename S>
 __device__ __forceinline__ void chain_item_emit(const F& f, S& s, u64 x, u32 r) {
   const ChainItem i = chain_item(f, x, r);
   if (i.none) return;
-  if (i.head) f.head_emit(s, r); else f.line_emit(s, i.l);
+  if (i.head) f.head_emit(s, r); else f.line_emit(s, i.l, r);
   if (i.last) f.end_emit(s);
 }
 

@@ -105,13 +105,13 @@ struct ChainWriteFmt : ChainItemBase {
   template <typename S>
   __device__ __forceinline__ void head_emit(S& s, u32 r) const { chain_head_emit(s, heads[r], text); }
   template <typename S>
-  __device__ __forceinline__ void line_emit(S& s, u64 l) const { chain_line_emit(s, lines + 3u * l); }
+  __device__ __forceinline__ void line_emit(S& s, u64 l, u32) const { chain_line_emit(s, lines + 3u * l); }
   template <typename S>
   __device__ __forceinline__ void end_emit(S& s) const { chain_end_emit(s); }
   __device__ __forceinline__ u64 size(u64 x, u32 r) const {
     const u64 head = plan[r]; /* read with the chain's offsets, not behind them */
     const ChainItem i = chain_item(*this, x, r);
-    return head == 0u ? 0u : chain_item_size(*this, i, head);
+    return head == 0u ? 0u : chain_item_size(*this, i, r, head);
   }
   template <typename S>
   __device__ __forceinline__ void emit(S& s, u64 x, u32 r) const { chain_item_emit(*this, s, x, r); }

@@ -9,6 +9,7 @@
 #include "wga_text_out.h"         /* the sinks, ScanItems and k_text_items_fill */
 #include "wga_k23_chain_split.h"  /* wga_chain_head_dev */
 #include "wga_chain_items.h"      /* ChainItemBase: the item numbering; c2p_line_emit: a data line's part of the CIGAR text */
+#include "wga_paf_head.h"         /* csv_field_emit, paf_head_emit: a record's columns */
 
 /* ============================================================================================ */
 /* K27: chain2paf record writer                                                                 */
@@ -30,62 +31,12 @@
  * The emitters run into a TextCount for the plan and the scan, into a TextPut for the fill. */
 #define WGA_C2P_STAGE (WGA_TEXT_ITEMS * 64u)
 
-/* a field as the csv writer writes it under QuoteStyle::Necessary: as it is, unless it holds the delimiter, a quote, CR or LF;
- * then between quotes with every quote inside doubled */
-template <typename S>
-__device__ __forceinline__ void csv_field_emit(S& s, const u8* __restrict__ p, u32 len, u8 delim) {
-  bool need = false;
-  for (u32 k = 0; k < len && !need; k++) {
-    const u8 b = p[k];
-    need = b == delim || b == (u8)'"' || b == (u8)'\n' || b == (u8)'\r';
-  }
-  if (!need) {
-    s.str(p, len);
-    return;
-  }
-  s.c((u8)'"');
-  for (u32 k = 0; k < len; k++) {
-    const u8 b = p[k];
-    if (b == (u8)'"') s.c(b);
-    s.c(b);
-  }
-  s.c((u8)'"');
-}
-
-/* the twelve columns of a PAF record whose CIGAR follows, up to and including the tag's name; q / t = size, start, end */
-template <typename S>
-__device__ __forceinline__ void paf_head_emit(S& s, const u8* __restrict__ qname, u32 qname_len, const u64* q, bool neg,
-                                              const u8* __restrict__ tname, u32 tname_len, const u64* t, u64 matches,
-                                              u64 block_length, u64 mapq) {
-  csv_field_emit(s, qname, qname_len, (u8)'\t');
-  for (u32 k = 0; k < 3u; k++) {
-    s.c((u8)'\t');
-    s.dec(q[k]);
-  }
-  s.c((u8)'\t');
-  s.c(neg ? (u8)'-' : (u8)'+');
-  s.c((u8)'\t');
-  csv_field_emit(s, tname, tname_len, (u8)'\t');
-  for (u32 k = 0; k < 3u; k++) {
-    s.c((u8)'\t');
-    s.dec(t[k]);
-  }
-  s.c((u8)'\t');
-  s.dec(matches);
-  s.c((u8)'\t');
-  s.dec(block_length);
-  s.c((u8)'\t');
-  s.dec(mapq);
-  const char* c = "\tcg:Z:";
-  for (u32 k = 0; k < 6u; k++) s.c((u8)c[k]);
-}
 /* chain.rs:436-451: the query's columns are num[4 .. 6], the target's num[1 .. 3]; the target's strand is not printed.  A name
  * span that does not lie inside the text (arrays that are not a splitter's) is empty. */
 template <typename S>
 __device__ __forceinline__ void c2p_head_emit(S& s, const wga_chain_head_dev& H, const u8* __restrict__ text, u64 n_bytes,
                                               u64 matches, u64 block_length) {
-  const u32 ql = H.qname_off <= n_bytes && (u64)H.qname_len <= n_bytes - H.qname_off ? H.qname_len : 0u;
-  const u32 tl = H.tname_off <= n_bytes && (u64)H.tname_len <= n_bytes - H.tname_off ? H.tname_len : 0u;
+  const u32 ql = name_span_len(H.qname_off, H.qname_len, n_bytes), tl = name_span_len(H.tname_off, H.tname_len, n_bytes);
   paf_head_emit(s, text + (ql ? H.qname_off : 0u), ql, H.num + 4, H.qstrand_neg != 0, text + (tl ? H.tname_off : 0u), tl, H.num + 1,
                 matches, block_length, 255u);
 }
@@ -128,10 +79,10 @@ struct Chain2PafFmt : ChainItemBase {
     c2p_head_emit(s, heads[r], text, n_bytes, sums[2u * (u64)r], sums[2u * (u64)r + 1u]);
   }
   template <typename S>
-  __device__ __forceinline__ void line_emit(S& s, u64 l) const { c2p_line_emit(s, lines + 3u * l); }
+  __device__ __forceinline__ void line_emit(S& s, u64 l, u32) const { c2p_line_emit(s, lines + 3u * l); }
   template <typename S>
   __device__ __forceinline__ void end_emit(S& s) const { s.c((u8)'\n'); }
-  __device__ __forceinline__ u64 size(u64 x, u32 r) const { return chain_item_size(*this, chain_item(*this, x, r), plan[r]); }
+  __device__ __forceinline__ u64 size(u64 x, u32 r) const { return chain_item_size(*this, chain_item(*this, x, r), r, plan[r]); }
   template <typename S>
   __device__ __forceinline__ void emit(S& s, u64 x, u32 r) const { chain_item_emit(*this, s, x, r); }
 };

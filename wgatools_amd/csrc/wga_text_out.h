@@ -126,9 +126,9 @@ __device__ __forceinline__ u32 csr_find_in(const u64* __restrict__ off, u32 lo, 
   return lo;
 }
 
-/* ITEM STREAMS.  A text that is ONE contiguous byte stream of variable-size items (K25's and K27's heads and lines, K26's rows)
- * is sized by a scan over ScanItems<F> and written by k_text_items_fill<F>, 256 consecutive items per block = one contiguous
- * stretch, whatever record borders lie inside it.  The format F is a plain struct passed by value:
+/* ITEM STREAMS.  A text that is ONE contiguous byte stream of variable-size items (K25's and K27's heads and lines, K28's heads
+ * and runs, K26's rows) is sized by a scan over ScanItems<F> and written by k_text_items_fill<F>, 256 consecutive items per block =
+ * one contiguous stretch, whatever record borders lie inside it.  The format F is a plain struct passed by value:
  *   static constexpr u32 kStage            the bytes of a block's stretch that go through LDS (a longer one is written directly)
  *   static constexpr bool kCheckSize       the fill compares size(x, r) with the scan's span before it writes item x
  *   u32 n_rec                              records
@@ -147,7 +147,7 @@ struct ScanItems { /* scan functor: the bytes of item x */
  * for a scan that is not this call's: a block whose stretch ends behind `total` writes nothing, and an item is written only into
  * a span [isc[x], isc[x + 1]) that is not empty and lies inside the block's stretch — and, where F::kCheckSize is set, has the
  * size the emitter is about to write: then nothing is written outside out[0, total) and nothing into a span but its item's text,
- * whatever the scan holds.  Without it (K25, K27: their fills cannot pay a second walk over an item's digits,
+ * whatever the scan holds.  Without it (K25, K27, and K28 after them: their fills cannot pay a second walk over an item's digits,
  * profiles/text_items_refactor.txt) an item longer than its span runs on into the bytes behind it, as it always did there.
  * A span that is refused keeps its bytes: in a staged block its thread copies what memory holds there into the stage and the
  * flush puts it back (the intervals between isc[x] and isc[x + 1] cover the stretch whatever the scan holds, so every byte of the

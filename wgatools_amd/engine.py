@@ -38,6 +38,10 @@ PAF_OK, PAF_SKIP, PAF_FALLBACK = 0, 1, 2
 PAF_FILTER_TILE = 8192
 # K25 (include/wga_hip.h wga_chain_filter_params)
 CHAIN_FILTER_PARAMS_DTYPE = np.dtype([("min_block_size", "<u8"), ("min_query_size", "<u8")])
+# K28 (include/wga_hip.h wga_maf2paf_head)
+MAF2PAF_HEAD_DTYPE = np.dtype([("q", np.uint64, 3), ("t", np.uint64, 3), ("qname_off", np.uint64), ("tname_off", np.uint64),
+                               ("qname_len", np.uint32), ("tname_len", np.uint32), ("strand_neg", np.uint8),
+                               ("pad", np.uint8, 7)])
 
 OP_CODES = {"M": 0, "I": 1, "D": 2, "N": 3, "S": 4, "H": 5, "P": 6, "=": 7, "X": 8}
 OP_I_CONT, OP_D_CONT, OP_OTHER = 9, 10, 11
@@ -540,6 +544,27 @@ class Engine:
             work = self.empty(max(int(self.lib.wga_chain2paf_work_bytes(n_chains, int(n_data_lines))), 16), np.uint8)
         args = (self.ctx, _p(text), int(n_bytes), _p(heads), n_chains, _p(lines), _p(line_off), _p(work))
         return self._count_then_fill("wga_chain2paf", "total", args, 1, out_shift)[0]
+
+    def maf2paf_count(self, n, names, n_name_bytes, heads, counts, runs, run_off, cols, work):
+        """K28: the count call of wga_maf2paf alone, total_bytes; it leaves its sums, plan and item scan in `work`"""
+        total = C.c_uint64(0)
+        self._check(self.lib.wga_maf2paf(self.ctx, int(n), _p(names), int(n_name_bytes), _p(heads), _p(counts), _p(runs), _p(run_off),
+                                         _p(cols), _p(work), C.byref(total), None))
+        return int(total.value)
+
+    def maf2paf(self, n, names, n_name_bytes, heads, counts, runs, run_off, cols, work=None, n_runs=None, out_shift=0):
+        """K28 (the record of maf.rs:484-520): the PAF records of n blocks from wga_maf_pair_stat's counters and runs and the
+        caller's heads (MAF2PAF_HEAD_DTYPE), both calls of wga_maf2paf.  Returns the text; the 64 bytes in front of and behind it
+        are checked.
+        work: a device buffer to use (else one of wga_maf2paf_work_bytes, for which n_runs is read from run_off when it is not
+        given); out_shift: d_out starts that many bytes behind a 64-byte aligned address"""
+        n = int(n)
+        if work is None:
+            if n_runs is None:
+                n_runs = int(run_off.numpy()[n]) if n else 0
+            work = self.empty(max(int(self.lib.wga_maf2paf_work_bytes(n, int(n_runs))), 16), np.uint8)
+        args = (self.ctx, n, _p(names), int(n_name_bytes), _p(heads), _p(counts), _p(runs), _p(run_off), _p(cols), _p(work))
+        return self._count_then_fill("wga_maf2paf", "total", args, 1, out_shift)[0]
 
     def dotplot_csv_count(self, n, segs, seg_off, tails, tail_off, work):
         """K26: the count call of wga_dotplot_csv alone, total_bytes; it leaves the scan of the row sizes in `work`"""

@@ -1,8 +1,18 @@
 /* cmd_maf2paf.inc — part of wgatools_main.cpp (included there, inside its namespace: the commands share the device helpers, readers and
  * writers defined in front of the include). */
 /* ---- maf2paf (converter.rs:29-54, maf.rs:484-520) ------------------------------------------------ */
-/* the PAF rows of blocks recs[0 .. n), whose rows stand on device d (p) */
-static std::string maf2paf_rows(Dev& d, const MafRows& p, const MafRecord* const* recs, uint32_t n) {
+/* WGA_MAF2PAF_WRITER=host: the records' fields are printed by host threads around the device's cg:Z: text, as before K28
+ * (measurements, and the cross-check of the device writer: same bytes) */
+static bool maf2paf_host_writer() {
+  const char* w = getenv("WGA_MAF2PAF_WRITER");
+  return w && strcmp(w, "host") == 0;
+}
+
+/* the PAF rows of blocks recs[0 .. n), whose rows stand on device d (p).  The records are written on the device (wga_maf2paf,
+ * K28): the host fills the numbers of every head and says where the two names stand — in the uploaded file where the device
+ * splitter took the piece and d holds it (p.names_in_rows), otherwise in a buffer the range's names are gathered in.  Only the
+ * number of runs and the text's length come back before the text. */
+static std::string maf2paf_rows(Dev& d, const MafRows& p, const MafRecord* const* recs, uint32_t n, bool host_writer) {
   std::string text;
   const uint8_t* d_rows = p.d_rows;
   auto *d_t = p.d_t, *d_q = p.d_q, *d_c = p.d_c;
@@ -12,10 +22,42 @@ static std::string maf2paf_rows(Dev& d, const MafRows& p, const MafRecord* const
   d.check(wga_maf_pair_stat(d.ctx, n, d_rows, d_t, d_q, d_c, d_s, d_counts, d_cnt, nullptr, nullptr));
   auto* d_roff = (uint64_t*)d.alloc(((size_t)n + 1) * 8);
   d.check(wga_exclusive_scan_u64(d.ctx, n, d_cnt, d_roff));
+  uint64_t n_runs = 0;
+  d.download(&n_runs, d_roff + n, 1);
+  auto* d_runs = (uint64_t*)d.alloc((n_runs + 1) * 8);
+  d.check(wga_maf_pair_stat(d.ctx, n, d_rows, d_t, d_q, d_c, d_s, d_counts, d_cnt, d_runs, d_roff));
+  if (!host_writer && (uint64_t)n + n_runs <= 0xFFFFFFF0ull) { /* beyond wga_maf2paf's limit: the host's fields */
+    std::vector<wga_maf2paf_head> heads(n);
+    std::string names;
+    auto span = [&](const MafSLine& l, uint64_t& off, uint32_t& len) {
+      off = p.names_in_rows ? l.name_off : names.size();
+      len = (uint32_t)l.name.size();
+      if (!p.names_in_rows) names += l.name;
+    };
+    for (uint32_t k = 0; k < n; k++) {
+      const MafRecord& r = *recs[k];
+      wga_maf2paf_head& h = heads[k];
+      memset(&h, 0, sizeof h);
+      h.q[0] = r.q().size, h.q[1] = r.query_start(), h.q[2] = r.query_end();
+      h.t[0] = r.t().size, h.t[1] = r.t().start, h.t[2] = r.t().start + r.t().align_size;
+      h.strand_neg = r.q().neg ? 1 : 0;
+      span(r.q(), h.qname_off, h.qname_len);
+      span(r.t(), h.tname_off, h.tname_len);
+    }
+    const uint8_t* d_names = p.names_in_rows ? d_rows : d.upload((const uint8_t*)names.data(), names.size());
+    const uint64_t n_name_bytes = p.names_in_rows ? p.n_row_bytes : names.size();
+    auto* d_heads = d.upload(heads);
+    void* d_work = d.alloc((size_t)wga_maf2paf_work_bytes(n, n_runs));
+    uint64_t total = 0;
+    d.check(wga_maf2paf(d.ctx, n, d_names, n_name_bytes, d_heads, d_counts, d_runs, d_roff, d_c, d_work, &total, nullptr));
+    auto* d_out = (uint8_t*)d.alloc(total + 64);
+    if (total) d.check(wga_maf2paf(d.ctx, n, d_names, n_name_bytes, d_heads, d_counts, d_runs, d_roff, d_c, d_work, &total, d_out));
+    text.resize((size_t)total);
+    if (total) d.download((uint8_t*)&text[0], d_out, total);
+    return text;
+  }
   std::vector<uint64_t> roff(n + 1);
   d.download(roff.data(), d_roff, n + 1);
-  auto* d_runs = (uint64_t*)d.alloc((roff[n] + 1) * 8);
-  d.check(wga_maf_pair_stat(d.ctx, n, d_rows, d_t, d_q, d_c, d_s, d_counts, d_cnt, d_runs, d_roff));
   /* the cg:Z: text is formatted on the device (wga_maf_runs_cigar_text) between the host's fields */
   auto* d_tb = (uint64_t*)d.alloc((size_t)n * 8);
   d.check(wga_maf_runs_cigar_text(d.ctx, n, roff[n], d_runs, d_roff, d_c, d_tb, nullptr, nullptr));
@@ -99,6 +141,7 @@ int cmd_maf2paf(const std::string* input, const std::string* query_name, Output&
   Dev d;
   MafDevices md(d); /* --gpus N: a piece's blocks in contiguous ranges over the devices, the rows meet in block order */
   MafChunks chunks(input);
+  const bool host_writer = maf2paf_host_writer();
   std::vector<std::string> all_text; /* converter.rs:40-52 collects every record before it writes the first: an error leaves no output
                                         (the pieces' rows are kept as they come — no 0.4 GB concatenation — and written at the end) */
   MafInput min;
@@ -111,9 +154,9 @@ int cmd_maf2paf(const std::string* input, const std::string* query_name, Output&
       const std::vector<const MafRecord*> all = all_records(recs);
       std::vector<std::string> part(md.count());
       md.run(min, all, false, [&](int g, Dev& dg, const MafRows& p, uint32_t lo, uint32_t cnt) {
-        part[g] = maf2paf_rows(dg, p, all.data() + lo, cnt);
+        part[g] = maf2paf_rows(dg, p, all.data() + lo, cnt, host_writer);
       });
-      g_timer.mark("kernels + host fields + download");
+      g_timer.mark(host_writer ? "maf2paf records (host)" : "maf2paf records (device)");
       for (std::string& t : part) all_text.push_back(std::move(t));
     }
     md.release_all();

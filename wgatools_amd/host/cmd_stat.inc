@@ -319,6 +319,8 @@ struct MafRows {
   uint64_t *d_t = nullptr, *d_q = nullptr, *d_c = nullptr;
   uint8_t* d_s = nullptr;
   std::vector<uint64_t> cols;
+  bool names_in_rows = false; /* d_rows is the uploaded file: MafSLine::name_off points into its n_row_bytes bytes */
+  uint64_t n_row_bytes = 0;
 };
 MafRows device_rows(Dev& d, const MafInput& in, const std::vector<const MafRecord*>& recs, bool cols_target) {
   MafRows m;
@@ -342,6 +344,8 @@ MafRows device_rows(Dev& d, const MafInput& in, const std::vector<const MafRecor
   }
   d.init();
   m.d_rows = in.on_device ? in.d_text : d.upload((const uint8_t*)blob.data(), blob.size());
+  m.names_in_rows = in.on_device;
+  m.n_row_bytes = in.on_device ? in.text->size() : blob.size();
   m.d_t = d.upload(t_off);
   m.d_q = d.upload(q_off);
   m.d_c = d.upload(m.cols);
