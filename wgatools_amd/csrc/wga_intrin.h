@@ -258,12 +258,29 @@ __device__ __forceinline__ wga_u64x2 wga_ro16(const u64* p) {
  * another one (a second, dependent round trip) */
 #define WGA_RO_HERE2(a, b) asm volatile("" ::"s"(a), "s"(b))
 #define WGA_RO_HERE4(a, b, c, d) asm volatile("" ::"s"(a), "s"(b), "s"(c), "s"(d))
+/* every vector memory operation of the wave issued so far has completed (s_waitcnt vmcnt(0); the other counters stay at their
+ * maxima).  The compiler places its own waits where a loaded register is first touched, and it takes this one into its
+ * bookkeeping: behind it nothing is pending, so a join of paths that all carry it (or a wait of the compiler's own) gets no
+ * further wait.  For a load issued in one round of a loop and consumed in a later one, on the paths where nothing else waits. */
+#define WGA_VM_LANDED() __builtin_amdgcn_s_waitcnt(0x0F70)
+/* ... all but the six issued last (vmcnt(6)): what was requested in front of six loads in a row has arrived */
+#define WGA_VM_LEFT6() __builtin_amdgcn_s_waitcnt(0x0F76)
 #else
 #define WGA_RO32(p) (*(const u32*)(p))
 #define WGA_RO64(p) (*(const u64*)(p))
 __device__ __forceinline__ wga_u64x2 wga_ro16(const u64* p) { return {p[0], p[1]}; }
 #define WGA_RO_HERE2(a, b) ((void)0)
 #define WGA_RO_HERE4(a, b, c, d) ((void)0)
+#define WGA_VM_LANDED() ((void)0)
+#define WGA_VM_LEFT6() ((void)0)
+#endif
+/* a byte store to global memory by name (global_store_byte).  Through a generic pointer it is a flat_store, which counts in
+ * lgkmcnt as well as vmcnt and may complete out of order with either: while one is pending the compiler turns every counted
+ * vector wait (vmcnt(4) under six loads, say) into vmcnt(0) */
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(WGA_EMU)
+#define WGA_GLOBAL_STORE_U8(p, v) (*(__attribute__((address_space(1))) u8*)(p) = (v))
+#else
+#define WGA_GLOBAL_STORE_U8(p, v) (*(u8*)(p) = (v))
 #endif
 
 #endif /* WGA_INTRIN_H */

@@ -8,7 +8,7 @@
  * per kilobyte of row (2.9e9 VALU + 1.8e9 SALU per launch) and runs at 1.2 per cycle — it is at that ceiling, and so were the
  * staged, planned and window kernels of rounds 2-3 (line-complete stores, but as many instructions).  This kernel spends ~210:
  *   * a wave owns ONE row kind (target or query) of a run of consecutive tiles (a "job") and walks it as a stream: ops are
- *     taken in 256 at a time (one 16-byte load per lane, the next 256 already on their way), three wave scans give columns,
+ *     taken in 256 at a time (one 16-byte load per lane, requested a super-step ahead and parked in LDS), three wave scans give columns,
  *     gap bases and the row's gap events, which wait in a linear FIFO in LDS; no per-tile search, no block barriers;
  *   * output leaves in SUPER-STEPS of four kilobytes, each kilobyte one streaming store of the wave — whole 128-byte lines,
  *     once (v1 writes 60 % of its lines in two pieces).  The events of a super-step are counted per granule with one LDS
@@ -17,8 +17,10 @@
  *     its share of the store; sixteen dashes cost nothing more;
  *   * the granules a gap touches are QUEUED, and the queue's lanes put all of a super-step's (~30) together in one round of
  *     the merge code — two windows under byte masks, further gaps in a short loop — and hand them back through LDS to the
- *     lanes that store them: the expensive path runs once per four kilobytes instead of once per kilobyte.  This happens
- *     BEFORE the plain windows are requested, so that its registers are free again (96 VGPRs: five waves per SIMD);
+ *     lanes that store them: the expensive path runs once per four kilobytes instead of once per kilobyte.  Its windows
+ *     are requested together with the plain ones and it runs while those travel; what it computed for the request is
+ *     kept packed in one register and the rest read again, so that it fits beside the four granules' data (96 VGPRs:
+ *     five waves per SIMD);
  *   * no calls, no barriers, every rare path inline and not unrolled.
  * An earlier form staged the source through a per-wave LDS ring filled by LDS-DMA (global_load_lds_dwordx4, counted vmcnt;
  * scripts/micro/stream_dma_copy.hip shows the mechanism at the rate of a plain copy): correct, but its 8-14 KB of LDS per wave
@@ -49,8 +51,22 @@
  *     recs[rec + 1] are requested together and a switch is one round trip (it was two, the second waiting for the first);
  *     a record without ops sends the loop round again.  WGA_RO_HERE keeps the compiler from sinking the fields' reads behind
  *     the loop, which would make them a second trip again.
- * What this does not remove: the compiler drains vmcnt (stores included) where the outer loop closes — the ops on their way
- * live in VGPRs that are copied there — so a wave still waits for its stores once per intake and per switch.
+ *
+ * Vector waits.  vmcnt is ONE in-order counter for loads and stores, and the compiler's bookkeeping of what is pending does not
+ * tell paths apart: a register that is pending on any path into a block is waited for there, with vmcnt(0) when anything
+ * stands behind it — stores included.  So the waits are laid out by where registers are touched:
+ *   * the next 256 ops are requested at the start of the first super-step behind an intake, in front of that step's windows,
+ *     and parked in LDS (s_ow) behind the wait that step has for its windows anyway; the intake reads them from LDS.  No
+ *     register is carried round the outer loop for them, nothing is copied where it closes and no wait stands there (it
+ *     used to drain the stores once per intake and per switch); a record switch reads the ops taken in last from LDS too.
+ *     Where no super-step runs between two intakes the ops are requested, waited for (WGA_VM_LANDED) and parked behind the
+ *     write loop: no fresh stores are in flight there;
+ *   * a super-step requests the queue's two windows and the four plain windows in a row — six loads with no branch between
+ *     them, out-of-range offsets where a lane has nothing to read — so its waits are counted ones: vmcnt(6) for the ops in
+ *     front, vmcnt(4) for the queue's lanes, which put their granules together while the plain windows travel;
+ *   * the byte stores of partial granules are global stores by name (WGA_GLOBAL_STORE_U8): behind a flat store the compiler
+ *     makes every counted wait a vmcnt(0).
+ * profiles/k2s_one_wait.md has the assembly facts and what each part gained.
  */
 #ifndef WGA_KERNELS_K2S_H
 #define WGA_KERNELS_K2S_H
@@ -60,7 +76,7 @@
 #define WGA_S_FIFO 320u                 /* gap events waiting for their columns to be written (256 of one intake + what is left) */
 #define WGA_S_MAX_JOB_TILES 32u          /* 32 x 2^24 columns stay below 2^31 */
 #define WGA_S_U 4u /* kilobytes of a row one super-step writes: the queued granules of that many share one round of the merge code */
-#define WGA_S_WAVE_BYTES ((WGA_S_FIFO + 4u) * 8u + 1024u + 1024u + 256u + 272u + 16u)
+#define WGA_S_WAVE_BYTES ((WGA_S_FIFO + 4u) * 8u + 1024u + 1024u + 256u + 272u + 16u + 2u * 1024u)
 #ifndef WGA_AUTO_LONG_VARIANT
 #define WGA_AUTO_LONG_VARIANT 3 /* the row kernel of every other batch when "expand_variant" is -1: this one (0 = v1, for A/B builds) */
 #endif
@@ -114,12 +130,13 @@ __device__ __forceinline__ u32 comp4s(u32 x, u32* bad) {
  *      They are inlined all the same: a call anywhere in the loop makes the compiler wait for every outstanding memory
  *      operation around it — each of a super-step's four stores then waited for the one in front. ---- */
 #define WGA_S_NOINLINE __forceinline__
-/* bytes [lo, hi) of a granule: byte stores, never read-modify-write */
+/* bytes [lo, hi) of a granule: byte stores, never read-modify-write.  Global stores by name: through a generic pointer they
+ * would be flat stores, and behind a flat operation the compiler makes every counted wait for vector memory a vmcnt(0) */
 __device__ WGA_S_NOINLINE void stream_store_bytes(u8* p, u32 o0, u32 o1, u32 o2, u32 o3, int lo, int hi) {
 #pragma clang loop vectorize(disable) unroll(disable)
   for (int j = lo; j < hi; j++) {
     const u32 wj = j < 4 ? o0 : j < 8 ? o1 : j < 12 ? o2 : o3;
-    p[j] = (u8)(wj >> (8 * (j & 3)));
+    WGA_GLOBAL_STORE_U8(p + j, (u8)(wj >> (8 * (j & 3))));
   }
 }
 /* InvalidBase (utils.rs:97) in bytes [lo, hi) of the granule at column Cl: the first offender in reversed order = the smallest
@@ -167,6 +184,7 @@ __device__ __forceinline__ void stream_row(const ExpandArgs& a, u8* const lds, c
   u32* const s_T = s_q + 256;                                    /* events per granule of a super-step, a byte per kilobyte */
   u32x4_a16* const s_lm = (u32x4_a16*)(s_T + 64);                /* bytes [0, n) of a granule, n = 0 .. 16    */
   u64* const s_k = (u64*)(s_lm + 17);                            /* rarely used wave-uniform state: [0] Kseg  */
+  u32x4_a16* const s_ow = (u32x4_a16*)(s_k + 2);                 /* 2 x 64 x four ops: slot `par` the ops taken in last, the other the next */
   if (lane < 17u) {
     u32x4_a16 m;
     for (int d = 0; d < 4; d++) m[d] = bytemask(0, (int)lane - 4 * d);
@@ -203,8 +221,16 @@ __device__ __forceinline__ void stream_row(const ExpandArgs& a, u8* const lds, c
   u32 C_b = 0, cum_b = 0;
   u32 C_min = 0;       /* pafpseudo: the record's first column that is written (its overlap with the record in front is trimmed) */
   u64 t = t0;          /* tile of op q                                                            */
-  u32 ow[4] = {0, 0, 0, 0}, xl0 = 0, xg0 = 0; /* the ops taken in last, the columns / gap bases in front of each lane's first */
-  u32 own[4] = {0, 0, 0, 0}; /* the next 256 ops, on their way */
+  u32 xl0 = 0, xg0 = 0; /* the columns / gap bases in front of each lane's first op of the ops taken in last */
+  /* The next 256 ops.  They are requested at the start of the first super-step behind an intake, in front of that step's
+   * windows, and PARKED in LDS (slot par ^ 1 of s_ow) behind the step's wait for its plain windows — vmcnt is one in-order
+   * counter, so that wait covers them and they cost no wait of their own; the next intake reads the parked ops.  The registers
+   * live inside one super-step: nothing is carried, copied or waited for where the outer loop closes, and no wait for ops
+   * stands where row stores are in flight.  Where no super-step runs between two intakes (and in front of a stream's first)
+   * they are requested, waited for and parked behind the write loop.  The ops taken in last stay in slot `par` for the one
+   * reader they have left, a record switch. */
+  u32 par = 0;         /* slot of s_ow that holds the ops taken in last                            */
+  bool parked = true;  /* ops q .. q + 255 wait in slot par ^ 1                                    */
 
   /* pafpseudo only: skip events are no columns, so any number of them can stand on ONE column (consecutive I / S ops) and
    * neither the byte counters of a super-step nor the FIFO's flush get past them.  Of a run of skip events on one column only
@@ -240,7 +266,13 @@ __device__ __forceinline__ void stream_row(const ExpandArgs& a, u8* const lds, c
     {
       const u32 lim = bnd ? C_b : C_known;
       const bool all = bnd || fin;
-      while ((int)(lim - pos) > 0) {
+      /* is there a super-step to write from `pos`: columns that fill its kilobytes, or everything when the record or the job ends */
+      auto step_due = [&]() -> bool {
+        if ((int)(lim - pos) <= 0) return false;
+        if (TCOORD && (int)(C_min - pos) > 0) return true;
+        return all || (lim - pos) >= WGA_S_U * 1024u - ((u32)(u64)(dst_seg + pos) & 1023u);
+      };
+      if (step_due()) do {
         if (TCOORD && (int)(C_min - pos) > 0) { /* the record's columns in front of its first written one */
           const u32 to = (int)(lim - C_min) > 0 ? C_min : lim;
           u32 c;
@@ -256,7 +288,6 @@ __device__ __forceinline__ void stream_row(const ExpandArgs& a, u8* const lds, c
         const u32 mis = (u32)(u64)A & 1023u;
         u8* const B = A - mis;
         const u32 room = WGA_S_U * 1024u - mis;
-        if (!all && (lim - pos) < room) break;
         const u32 Cs = pos;
         u32 Ce = (lim - pos) < room ? lim : pos + room;
         const u32 Cl0 = Cs - mis; /* column of the first granule of the kilobyte Cs lies in (wraps below zero at a stream's start) */
@@ -268,6 +299,10 @@ __device__ __forceinline__ void stream_row(const ExpandArgs& a, u8* const lds, c
             continue;
           }
         }
+
+        const bool fetch = !parked; /* the first super-step behind an intake takes the next ops along */
+        u32 own[4];
+        buf_load16(obuf, fetch && q < q_end ? q * 4u + lane * 16u : WGA_BUF_OOB, own);
 
         /* ---- (1) the super-step's events, counted per granule: byte u of T[l] = events that start in granule l of kilobyte u ---- */
         s_T[lane] = 0u;
@@ -344,9 +379,14 @@ __device__ __forceinline__ void stream_row(const ExpandArgs& a, u8* const lds, c
         }
         const BufRsrc dbuf = buf_make(B, WGA_S_U * 1024u);
 
-        /* ---- (3) the queued granules: put together from two windows under byte masks, handed back through LDS ---- */
+        /* ---- (3) the queued granules: put together from two windows under byte masks, handed back through LDS.  First where
+         *      each one is cut and which two windows it needs; then ALL the step's windows are requested; then the merge ---- */
         WGA_WAVE_SYNC();
-        if (lane < qn) {
+        const bool mq = lane < qn;
+        u32 cuts = 0; /* a1, b1, e1 (a byte each) and bit 24: more events inside the granule */
+        u32 W0[4], W1[4];
+        u32 off0 = WGA_BUF_OOB, off1 = WGA_BUF_OOB;
+        if (mq) {
           const u32 ent = s_q[lane];
           const u32 k = ent >> 8, Cl = Cl0 + 16u * (ent & 255u);
           int lo = (int)(Cs - Cl), hi = (int)(Ce - Cl);
@@ -363,12 +403,43 @@ __device__ __forceinline__ void stream_row(const ExpandArgs& a, u8* const lds, c
           const u32 gl1 = stream_glen<MODE>(cu1, cu2);
           int e1 = gl1 >= 16u ? 16 : b1 + (int)gl1;
           e1 = e1 > hi ? hi : e1;
-          bool more = (int)(gs2 - Cl) < hi;
-          u32 W0[4], W1[4];
-          if (!SYM) {
-            buf_load16(sbuf, b1 > a1 ? (rc ? S32 - Cl + cu1 : S32 + Cl - cu1) : WGA_BUF_OOB, W0);
-            buf_load16(sbuf, hi > e1 ? (rc ? S32 - Cl + cu2 : S32 + Cl - cu2) : WGA_BUF_OOB, W1);
+          if (b1 > a1) off0 = rc ? S32 - Cl + cu1 : S32 + Cl - cu1;
+          if (hi > e1) off1 = rc ? S32 - Cl + cu2 : S32 + Cl - cu2;
+          cuts = (u32)a1 | ((u32)b1 << 8) | ((u32)e1 << 16) | ((int)(gs2 - Cl) < hi ? 1u << 24 : 0u);
+        }
+        /* the queue's two windows and the four plain windows: six loads in a row, no branch between them, so that the queue's
+         * lanes wait for the first two only (vmcnt(4)) and put their granules together while the plain windows travel */
+        if (!SYM) {
+          buf_load16(sbuf, off0, W0);
+          buf_load16(sbuf, off1, W1);
+        }
+        u32 dat[WGA_S_U][4];
+        const u32 wsp2 = Ce - Cs - 16u; /* Ce may have moved */
+        if (!SYM) {
+#pragma unroll
+          for (u32 u = 0; u < WGA_S_U; u++) {
+            const u32 Cl = Cl0 + 1024u * u + 16u * lane;
+            const bool pl = ((cls >> (4u * u)) & 1u) != 0u && (int)(Cl - Ce) < 0;
+            buf_load16(sbuf, pl ? (rc ? S32 - Cl + adjv[u] : S32 + Cl - adjv[u]) : WGA_BUF_OOB, dat[u]); /* the others: zeros */
           }
+        }
+        /* what was requested in front of these six is here when six are left in flight: the next ops, and (the counter is in
+         * order) the stores of the super-step in front, which the first wait for a window would wait for as well */
+        if (!SYM) WGA_VM_LEFT6();
+        if (!SYM && fetch) {
+          const u32x4_a16 nx = {own[0], own[1], own[2], own[3]};
+          s_ow[64u * (par ^ 1u) + lane] = nx;
+          parked = true;
+        }
+        if (mq) { /* the cuts were kept; the rest is read again (it would hold ten registers while six windows travel) */
+          const u32 ent = s_q[lane];
+          const u32 k = ent >> 8, Cl = Cl0 + 16u * (ent & 255u);
+          int lo = (int)(Cs - Cl), hi = (int)(Ce - Cl);
+          lo = lo < 0 ? 0 : (lo > 16 ? 16 : lo);
+          hi = hi > 16 ? 16 : (hi < 0 ? 0 : hi);
+          const u32 cu0 = s_fifo[2u * (k - 1u) + 1u], cu1 = s_fifo[2u * k + 1u];
+          const int a1 = (int)(cuts & 255u), b1 = (int)((cuts >> 8) & 255u), e1 = (int)((cuts >> 16) & 255u);
+          bool more = (cuts >> 24) != 0u;
           const u32x4_a16 La = s_lm[a1], Lb = s_lm[b1], Le = s_lm[e1];
           u32 o[4], bad[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
@@ -418,20 +489,19 @@ __device__ __forceinline__ void stream_row(const ExpandArgs& a, u8* const lds, c
         }
         WGA_WAVE_SYNC();
 
-        /* ---- (4) the plain granules' windows, all requested at once; what the queue made replaces the queued ones; whole
-         *      granules leave in one streaming store of the wave per kilobyte, partial ones (at most two) in byte stores ---- */
-        u32 dat[WGA_S_U][4];
-        const u32 wsp2 = Ce - Cs - 16u; /* Ce may have moved */
+        /* ---- (4) the plain granules' windows arrive; sixteen dashes where the class says so; what the queue made replaces the
+         *      queued ones; whole granules leave in one streaming store of the wave per kilobyte, partial ones (at most two) in
+         *      byte stores ---- */
 #pragma unroll
         for (u32 u = 0; u < WGA_S_U; u++) {
-          const u32 Cl = Cl0 + 1024u * u + 16u * lane;
           const u32 c = (cls >> (4u * u)) & 15u;
           if (SYM) { /* sixteen of the run's character, or of '1' */
             dat[u][0] = dat[u][1] = dat[u][2] = dat[u][3] = (c & 2u) ? ((c & 8u) ? 0x2D2D2D2Du : 0x30303030u) : 0x31313131u;
             continue;
           }
-          dat[u][0] = dat[u][1] = dat[u][2] = dat[u][3] = (c & 2u) ? 0x2D2D2D2Du : 0u;
-          if ((c & 1u) && (int)(Cl - Ce) < 0) buf_load16(sbuf, rc ? S32 - Cl + adjv[u] : S32 + Cl - adjv[u], dat[u]);
+          const u32 dash = (c & 2u) ? 0x2D2D2D2Du : 0u; /* a granule of dashes had no window: it read zeros */
+#pragma unroll
+          for (int d = 0; d < 4; d++) dat[u][d] |= dash;
         }
         if (rc) { /* the windows arrive: reverse complement ('-' and what the queue replaces pass through) */
 #pragma unroll
@@ -450,6 +520,11 @@ __device__ __forceinline__ void stream_row(const ExpandArgs& a, u8* const lds, c
                                   adjv[u]);
             }
           }
+        }
+        if (SYM && fetch) { /* no windows in this mode: the compiler waits for them here */
+          const u32x4_a16 nx = {own[0], own[1], own[2], own[3]};
+          s_ow[64u * (par ^ 1u) + lane] = nx;
+          parked = true;
         }
 #pragma unroll
         for (u32 u = 0; u < WGA_S_U; u++) {
@@ -474,6 +549,14 @@ __device__ __forceinline__ void stream_row(const ExpandArgs& a, u8* const lds, c
         WGA_WAVE_SYNC(); /* the patch buffer and the queue are rewritten by the next super-step */
         e0 += nE;
         pos = Ce;
+      } while (step_due());
+      if (!parked) { /* no super-step since the intake (or the stream's start): requested and waited for here */
+        u32 own[4];
+        buf_load16(obuf, q < q_end ? q * 4u + lane * 16u : WGA_BUF_OOB, own);
+        WGA_VM_LANDED();
+        const u32x4_a16 nx = {own[0], own[1], own[2], own[3]};
+        s_ow[64u * (par ^ 1u) + lane] = nx;
+        parked = true;
       }
       fin = false;
     }
@@ -549,7 +632,7 @@ __device__ __forceinline__ void stream_row(const ExpandArgs& a, u8* const lds, c
           const u64 ahead = skip > x_a ? skip - x_a : 0ull;
           C_min = (u32)(ahead < 0x40000000ull ? ahead : 0x40000000ull);
         }
-        buf_load16(obuf, q * 4u + lane * 16u, own); /* the first 256 ops */
+        parked = false; /* the first 256 ops are requested where all the others are */
         live = true;
       }
       /* the segment: column C_a (cum_a gap bases in front) is column x_a of the record's row, sb bases of its slice used.
@@ -581,6 +664,7 @@ __device__ __forceinline__ void stream_row(const ExpandArgs& a, u8* const lds, c
       if (sw && re < q_hi) {
         const u32 kb = re - q_lo, e = kb & 3u; /* the columns / gap bases in front of op kb: its lane's prefix + its ops in front */
         u32 vl = xl0, vg = xg0;
+        const u32x4_a16 ow = s_ow[64u * par + lane]; /* this lane's own four of the ops taken in last */
 #pragma unroll
         for (u32 i = 0; i < 3u; i++) {
           const bool valid = q_lo + 4u * lane + i < q_hi && i < e;
@@ -642,8 +726,9 @@ __device__ __forceinline__ void stream_row(const ExpandArgs& a, u8* const lds, c
     q_lo = q;
     q_hi = q + 256u < q_end ? q + 256u : q_end;
     q = q_hi;
-    ow[0] = own[0], ow[1] = own[1], ow[2] = own[2], ow[3] = own[3];
-    buf_load16(obuf, q_hi < q_end ? q_hi * 4u + lane * 16u : WGA_BUF_OOB, own); /* the next 256 travel while these are worked on */
+    par ^= 1u;
+    parked = false;
+    const u32x4_a16 ow = s_ow[64u * par + lane]; /* parked by this lane itself */
     u32 l[4], g[4], sl = 0, sg = 0, sc = 0;
 #pragma unroll
     for (int e = 0; e < 4; e++) {
@@ -684,10 +769,8 @@ __device__ __forceinline__ void stream_row(const ExpandArgs& a, u8* const lds, c
       u32 vl = xl0, vg = xg0;
 #pragma unroll
       for (u32 i = 0; i < 3u; i++) {
-        const bool valid = q_lo + 4u * lane + i < q_hi && i < e;
-        const u32 len = valid ? ow[i] >> 4 : 0u, code = ow[i] & 15u;
-        vl += len & bit_mask(COL_MASK, code);
-        vg += (len & bit_mask(GAP_MASK, code)) - (len & bit_mask(SKIP_MASK, code));
+        vl += i < e ? l[i] : 0u;
+        vg += i < e ? g[i] : 0u;
       }
       C_b = wave_get_u32_dyn(vl, kb >> 2);
       cum_b = wave_get_u32_dyn(vg, kb >> 2);
@@ -731,7 +814,7 @@ __device__ __forceinline__ void pseudo_stream(const ExpandArgs& a) {
   stream_row<MODE>(a, (u8*)s_mem + wave * WGA_S_WAVE_BYTES, lane, job, t0, t1);
 }
 #ifndef WGA_S_WAVES_PER_SIMD
-#define WGA_S_WAVES_PER_SIMD 5 /* launch bound: 96 VGPRs (the natural need is 102: two spill slots), LDS allows 31 waves per CU; 4: 6.0 ms, 5: 5.66 ms, 6 (61 spill slots): 7.4 ms */
+#define WGA_S_WAVES_PER_SIMD 5 /* launch bound: 96 VGPRs; LDS (7.1 KB per wave) allows 22 waves per CU, five per SIMD are 20; 4: 6.0 ms, 5: 5.66 ms, 6 (61 spill slots): 7.4 ms */
 #endif
 __global__ __launch_bounds__(128, WGA_S_WAVES_PER_SIMD) void k_paf2maf_expand_s(ExpandArgs a) { expand_stream(a); }
 __global__ __launch_bounds__(128, WGA_S_WAVES_PER_SIMD) void k_pafpseudo_stream(ExpandArgs a) { pseudo_stream<WGA_S_PSEUDO>(a); }
