@@ -35,7 +35,7 @@ MUTANTS = [
     ("k7_scan", CSRC + "wga_k7_paf_call.h",
      "tl = wave_incl_scan_u32(tsum & 0xFFFFu), th = wave_incl_scan_u32(tsum >> 16);",
      "tl = wave_incl_scan_u32(tsum), th = 0;", "paf_call"),
-    ("k1_wide", CSRC + "wga_kernels.h",
+    ("k1_wide", CSRC + "wga_k1_stat.h",
      "if (__ballot(s_t >= (1u << 26)) == 0ull) { /* wave-uniform */",
      "if (true) {", "stat"),
     ("kclass_wide", CSRC + "wga_k_class.h",

@@ -1,7 +1,7 @@
 /*
  * simt_emu.h — a tiny single-threaded SIMT emulator.  TEST INFRASTRUCTURE ONLY.
  *
- * The HIP kernels in wgatools_amd/csrc/wga_kernels.h are written against a small surface
+ * The HIP kernels in wgatools_amd/csrc (wga_kernels.h and one header per kernel family) are written against a small surface
  * (threadIdx/blockIdx, __shared__, __syncthreads, __shfl*, __ballot, atomics).  This header
  * provides that surface for a plain g++ build so the *same kernel source* can be executed on the
  * CPU by the `-m "not gpu"` tests (tests/emu/libwgaemu.so) and compared with the oracle before a

@@ -2082,7 +2082,7 @@ def check_bgzf_inflate(eng):
 # ones by the status they must get, every truncation of one stream and every single-bit mutant of it.  zlib is the judge
 # (deflate_craft.zlib_verdict) of every member; where a case names a status, that status is asserted on top.
 # ------------------------------------------------------------------------------------------------
-INF_OK, INF_INPUT, INF_TYPE, INF_CODES, INF_SYMBOL, INF_DIST, INF_SIZE = range(7)    # WGA_INF_* (wga_kernels3.h)
+INF_OK, INF_INPUT, INF_TYPE, INF_CODES, INF_SYMBOL, INF_DIST, INF_SIZE = range(7)    # WGA_INF_* (wga_k17_bgzf_inflate.h)
 INF_GAP = 32                                                                         # guard bytes around every member's output
 
 

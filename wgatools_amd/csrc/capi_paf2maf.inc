@@ -7,6 +7,49 @@ static inline u32 job_tiles_for(int param, u64 nt) {
   return nt < 200000ull ? 4u : 8u;
 }
 
+/* The workspace of the row pre-pass (k_rec_desc / k_pseudo_rec_desc, then k_tile_base), carved from the context's scratch: the
+ * record descriptors, the tile descriptors, v1's two tile lists (beyond 2^31 columns; its row emitters), and behind them what ONE
+ * memset clears in front of the pre-pass — the lists' two counters, and for the streaming kernel a flag byte per tile and a skip
+ * word per job (without it: the counters alone, no flags, no skip words, and nothing to clear) */
+struct PrepassWs {
+  u64 nt, jobs;
+  u32 job_tiles;
+  size_t rec_bytes, desc_bytes, list_bytes, flag_bytes, skip_bytes, zero_bytes, total;
+  wga_rec_desc* recs = nullptr;
+  wga_tile_desc* tdesc = nullptr;
+  u32 *wide_list = nullptr, *fast_list = nullptr, *counts = nullptr;
+  u8* tile_flag = nullptr;
+  u32* job_skip = nullptr;
+  PrepassWs(u32 n, u64 nt_, u32 job_tiles_, bool stream) : nt(nt_), jobs((nt_ + job_tiles_ - 1) / job_tiles_), job_tiles(job_tiles_) {
+    rec_bytes = ((size_t)n * sizeof(wga_rec_desc) + 255) & ~(size_t)255;
+    desc_bytes = (size_t)nt * sizeof(wga_tile_desc);
+    list_bytes = 2 * (size_t)nt * sizeof(u32);
+    flag_bytes = stream ? (((size_t)nt + 255) & ~(size_t)255) : 0;
+    skip_bytes = stream ? (((size_t)jobs * sizeof(u32) + 255) & ~(size_t)255) : 0;
+    zero_bytes = 256 + flag_bytes + skip_bytes;
+    total = rec_bytes + desc_bytes + list_bytes + zero_bytes;
+  }
+  void carve(void* base) {
+    char* const p = (char*)base;
+    recs = (wga_rec_desc*)p;
+    tdesc = (wga_tile_desc*)(p + rec_bytes);
+    wide_list = (u32*)(p + rec_bytes + desc_bytes);
+    fast_list = wide_list + nt; /* the second half of the list area */
+    counts = (u32*)(p + rec_bytes + desc_bytes + list_bytes);
+    tile_flag = flag_bytes ? (u8*)counts + 256 : nullptr;
+    job_skip = flag_bytes ? (u32*)(tile_flag + flag_bytes) : nullptr;
+  }
+};
+/* k_tile_base on a carved workspace: mode 0 paf2maf's columns, 1 pafpseudo's (S ops count as I) */
+static int launch_tile_base(wga_ctx* c, const wga_cigar_batch* b, const PrepassWs& w, const wga_tile_sum* tiles, int mode,
+                            int force_slow) {
+  WGA_LAUNCH(k_tile_base, (u32)((w.nt + 255) / 256), WGA_BLOCK, c->stream, (const u64*)b->d_op_off, (u64)b->n_ops, tiles,
+             (const wga_rec_desc*)w.recs, w.tdesc, mode, (const u8*)w.tile_flag, w.job_tiles, force_slow, w.job_skip, w.counts,
+             w.fast_list, w.wide_list);
+  LAUNCH_CHECK();
+  return WGA_OK;
+}
+
 extern "C" {
 
 size_t wga_tile_ws_bytes(uint64_t n_ops) { return (size_t)(n_tiles(n_ops) * sizeof(wga_tile_sum)) + 16; }
@@ -88,48 +131,30 @@ int wga_paf2maf_expand(wga_ctx* c, const wga_cigar_batch* b, const wga_cigar_cou
   u64 nt = n_tiles(b->n_ops);
   if (nt > 0x7FFFFFFFull) return fail(WGA_E_INVALID_ARG, "batch too large for one launch", nullptr);
   /* pre-pass: per-record descriptors and per-tile base sums, in the context's scratch arena */
-  void* ws;
-  size_t rec_bytes = ((size_t)b->n * sizeof(wga_rec_desc) + 255) & ~(size_t)255;
-  const size_t desc_bytes = (size_t)nt * sizeof(wga_tile_desc);
-  const size_t list_bytes = 2 * (size_t)nt * sizeof(u32); /* the lists of wide / huge tiles */
   const int variant = c->expand_variant >= 0 ? c->expand_variant : WGA_AUTO_LONG_VARIANT;
   c->expand_variant_used = variant;
   const bool stream = variant == 3;
-  const u32 job_tiles = job_tiles_for(c->expand_job_tiles, nt);
-  const u64 jobs = (nt + job_tiles - 1) / job_tiles;
-  /* cleared by ONE memset in front of the pre-pass: the lists' two counters, and for the streaming kernel a flag byte per tile
-   * and a skip word per job */
-  const size_t flag_bytes = stream ? (((size_t)nt + 255) & ~(size_t)255) : 0;
-  const size_t skip_bytes = stream ? (((size_t)jobs * sizeof(u32) + 255) & ~(size_t)255) : 0;
-  const size_t zero_bytes = 256 + flag_bytes + skip_bytes;
-  if ((rc = ctx_scratch(c, rec_bytes + desc_bytes + list_bytes + zero_bytes, &ws))) return rc;
-  wga_rec_desc* recs = (wga_rec_desc*)ws;
-  wga_tile_desc* tdesc = (wga_tile_desc*)((char*)ws + rec_bytes);
-  u32* const wide_list = (u32*)((char*)ws + rec_bytes + desc_bytes);
-  u32* const fast_list = wide_list + nt; /* the second half of the list area: tiles for v1's row emitters */
-  u32* const wide_counts = (u32*)((char*)ws + rec_bytes + desc_bytes + list_bytes);
-  u8* const tile_flag = stream ? (u8*)wide_counts + 256 : nullptr;
-  u32* const job_skip = stream ? (u32*)(tile_flag + flag_bytes) : nullptr;
+  PrepassWs w(b->n, nt, job_tiles_for(c->expand_job_tiles, nt), stream);
+  void* ws;
+  if ((rc = ctx_scratch(c, w.total, &ws))) return rc;
+  w.carve(ws);
   /* part of the pre-pass for the streaming kernel: the tiles it leaves to v1 (records that are not clean, giant tiles) —
    * k_rec_desc flags the tiles of such records, k_tile_base puts the flags into the descriptors, the jobs' skip words and
    * v1's two lists */
-  if (stream) RT_CHECK(rt_memset(wide_counts, 0, zero_bytes, c->stream));
+  if (stream) RT_CHECK(rt_memset(w.counts, 0, w.zero_bytes, c->stream));
   WGA_LAUNCH(k_rec_desc, (b->n + 255u) / 256u, WGA_BLOCK, c->stream, b->n, d_counts,
              b->d_strand_neg, (const u64*)d_t_src_off, (const u64*)d_t_src_len,
              (const u64*)d_q_src_off, (const u64*)d_q_src_len, (const u64*)d_t_row_off,
-             (const u64*)d_q_row_off, recs, (const u64*)b->d_op_off, (u64)t_fa_bytes, (u64)q_fa_bytes, tile_flag);
+             (const u64*)d_q_row_off, w.recs, (const u64*)b->d_op_off, (u64)t_fa_bytes, (u64)q_fa_bytes, w.tile_flag);
   LAUNCH_CHECK();
-  WGA_LAUNCH(k_tile_base, (u32)((nt + 255) / 256), WGA_BLOCK, c->stream, (const u64*)b->d_op_off,
-             (u64)b->n_ops, (const wga_tile_sum*)d_tile_ws, (const wga_rec_desc*)recs, tdesc, 0, (const u8*)tile_flag,
-             job_tiles, c->expand_force_slow, job_skip, wide_counts, fast_list, wide_list);
-  LAUNCH_CHECK();
-  if (stream) c->stream_counts = wide_counts;
+  if ((rc = launch_tile_base(c, b, w, (const wga_tile_sum*)d_tile_ws, 0, c->expand_force_slow))) return rc;
+  if (stream) c->stream_counts = w.counts;
   ExpandArgs a;
   a.ops = b->d_ops;
   a.op_off = (const u64*)b->d_op_off;
   a.n_ops = b->n_ops;
-  a.tdesc = tdesc;
-  a.recs = recs;
+  a.tdesc = w.tdesc;
+  a.recs = w.recs;
   a.t_fa = d_t_fa;
   a.t_fa_bytes = t_fa_bytes;
   a.q_fa = d_q_fa;
@@ -138,28 +163,27 @@ int wga_paf2maf_expand(wga_ctx* c, const wga_cigar_batch* b, const wga_cigar_cou
   a.diag = d_diag;
   a.force_slow = c->expand_force_slow;
   a.no_table = c->expand_no_table;
-  a.drain_min = 0; /* below */
+  /* when v1's waves emit their queued gap-touching chunks (RowSrc::drain_min) */
+  a.drain_min = c->expand_drain_min ? c->expand_drain_min : ((u64)t_fa_bytes + (u64)q_fa_bytes > WGA_DRAIN_POOL_BYTES ? 16u : 32u);
   a.tile_count = nullptr;
   a.tile_list = nullptr;
   a.n_rec = b->n;
-  a.job_tiles = job_tiles;
-  a.job_skip = job_skip;
-  /* when v1's waves emit their queued gap-touching chunks (RowSrc::drain_min) */
-  a.drain_min = c->expand_drain_min ? c->expand_drain_min : ((u64)t_fa_bytes + (u64)q_fa_bytes > WGA_DRAIN_POOL_BYTES ? 16u : 32u);
+  a.job_tiles = w.job_tiles;
+  a.job_skip = w.job_skip;
   c->expand_drain_min_used = a.drain_min;
   const uint32_t slot = c->ev_n % (uint32_t)wga_ctx::kTimingRing;
   if (c->timing) RT_CHECK(rt_event_record(c->ev[2 * slot], c->stream));
   if (stream) {
-    WGA_LAUNCH(k_paf2maf_expand_s, (u32)jobs, 128u, c->stream, a);
+    WGA_LAUNCH(k_paf2maf_expand_s, (u32)w.jobs, 128u, c->stream, a);
     LAUNCH_CHECK();
     const u32 side_grid = nt < 256 ? (u32)nt : 256u;
-    a.tile_count = wide_counts; /* tiles of records that are not clean, tiles beyond 2^24 columns: v1's row emitters */
-    a.tile_list = fast_list;
+    a.tile_count = w.counts; /* tiles of records that are not clean, tiles beyond 2^24 columns: v1's row emitters */
+    a.tile_list = w.fast_list;
     WGA_LAUNCH(k_paf2maf_expand_list, side_grid, WGA_BLOCK, c->stream, a);
     LAUNCH_CHECK();
     a.force_slow = 1; /* beyond 2^31 columns (and everything under "expand_force_slow"): the op-serial walk */
-    a.tile_count = wide_counts + 1;
-    a.tile_list = wide_list;
+    a.tile_count = w.counts + 1;
+    a.tile_list = w.wide_list;
     WGA_LAUNCH(k_paf2maf_expand_list, side_grid, WGA_BLOCK, c->stream, a);
     LAUNCH_CHECK();
   } else {

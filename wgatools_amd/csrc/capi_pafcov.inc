@@ -179,11 +179,7 @@ static int pafcov_run(wga_ctx* c, const wga_cigar_batch* b, const uint32_t* d_ta
     WGA_LAUNCH(k_cov_windows<true>, (u32)nw, WGA_COV_BLOCK, c->stream, d_ops, n_ops, (const wga_cov_desc*)c->cov.pieces.mem,
                (const wga_cov_piece*)c->cov.tile_list.mem, (const wga_cov_piece*)c->cov.list.mem, woff,
                (int*)d_cov, (u64)n_cov, (const u64*)rng_lo, (const u64*)rng_hi, n_rng, win_state,
-#ifdef WGA_COV_NO_ORDER /* A/B builds: the windows in index order */
-               (const u32*)nullptr);
-#else
                (const u32*)c->cov.order.mem);
-#endif
     LAUNCH_CHECK();
   } else if (n_pieces) {
     WGA_LAUNCH(k_cov_windows<false>, (u32)nw, WGA_COV_BLOCK, c->stream, d_ops, n_ops, (const wga_cov_desc*)c->cov.pieces.mem,

@@ -64,18 +64,11 @@ int wga_pafpseudo_fill(wga_ctx* c, const wga_cigar_batch* b, int base_mode, cons
   const bool stream = c->pseudo_variant == 3;
   const size_t tile_bytes = kept ? 0 : ((size_t)nt * sizeof(wga_tile_sum) + 255) & ~(size_t)255;
   const size_t sums_bytes = kept ? 0 : ((size_t)b->n * sizeof(wga_class_sums) + 255) & ~(size_t)255;
-  const size_t rec_bytes = stream ? ((size_t)b->n * sizeof(wga_rec_desc) + 255) & ~(size_t)255 : 0;
-  const size_t desc_bytes = stream ? (size_t)nt * sizeof(wga_tile_desc) : 0;
-  const size_t list_bytes = stream ? 2 * (size_t)nt * sizeof(u32) : 0;
-  const u32 job_tiles = job_tiles_for(c->expand_job_tiles, nt);
-  const u64 jobs = (nt + job_tiles - 1) / job_tiles;
-  /* cleared by one memset in front of the pre-pass: the lists' two counters, a flag byte per tile, a skip word per job */
-  const size_t flag_bytes = stream ? (((size_t)nt + 255) & ~(size_t)255) : 0;
-  const size_t skip_bytes = stream ? (((size_t)jobs * sizeof(u32) + 255) & ~(size_t)255) : 0;
-  const size_t zero_bytes = stream ? 256 + flag_bytes + skip_bytes : 0;
+  PrepassWs w(b->n, nt, job_tiles_for(c->expand_job_tiles, nt), true); /* behind the sums; the block kernel alone has none */
+  const size_t ws_bytes = tile_bytes + sums_bytes + (stream ? w.total : 0);
   void* ws = nullptr;
-  if (tile_bytes + sums_bytes + rec_bytes + desc_bytes + list_bytes + zero_bytes)
-    if ((rc = ctx_scratch(c, tile_bytes + sums_bytes + rec_bytes + desc_bytes + list_bytes + zero_bytes, &ws))) return rc;
+  if (ws_bytes)
+    if ((rc = ctx_scratch(c, ws_bytes, &ws))) return rc;
   c->pseudo_counts = nullptr;
   if (kept) {
     tiles = t.tiles; /* what wga_cigar_class_sums left for this batch */
@@ -108,53 +101,43 @@ int wga_pafpseudo_fill(wga_ctx* c, const wga_cigar_batch* b, int base_mode, cons
   a.tile_count = nullptr;
   a.tile_list = nullptr;
   if (stream) {
-    char* const base = (char*)ws + tile_bytes + sums_bytes;
-    wga_rec_desc* const recs = (wga_rec_desc*)base;
-    wga_tile_desc* const tdesc = (wga_tile_desc*)(base + rec_bytes);
-    u32* const list_wide = (u32*)(base + rec_bytes + desc_bytes);
-    u32* const list_fast = list_wide + nt;
-    u32* const counts = (u32*)(base + rec_bytes + desc_bytes + list_bytes);
-    u8* const tile_flag = (u8*)counts + 256;
-    u32* const job_skip = (u32*)(tile_flag + flag_bytes);
-    RT_CHECK(rt_memset(counts, 0, zero_bytes, c->stream));
+    w.carve((char*)ws + tile_bytes + sums_bytes);
+    RT_CHECK(rt_memset(w.counts, 0, w.zero_bytes, c->stream));
     WGA_LAUNCH(k_pseudo_rec_desc, (b->n + 255u) / 256u, WGA_BLOCK, c->stream, b->n, (const wga_class_sums*)rec_sums, b->d_strand_neg,
                base_mode ? (const u64*)d_q_src_off : nullptr, base_mode ? (const u64*)d_q_src_len : nullptr, (const u64*)d_skip,
-               (const u64*)d_dst_off, (const u64*)b->d_op_off, (u64)q_fa_bytes, recs, tile_flag);
+               (const u64*)d_dst_off, (const u64*)b->d_op_off, (u64)q_fa_bytes, w.recs, w.tile_flag);
     LAUNCH_CHECK();
-    WGA_LAUNCH(k_tile_base, (u32)((nt + 255) / 256), WGA_BLOCK, c->stream, (const u64*)b->d_op_off, (u64)b->n_ops,
-               (const wga_tile_sum*)tiles, (const wga_rec_desc*)recs, tdesc, 1, (const u8*)tile_flag, job_tiles, 0, job_skip, counts,
-               list_fast, list_wide);
-    LAUNCH_CHECK();
-    c->pseudo_counts = counts;
+    if ((rc = launch_tile_base(c, b, w, (const wga_tile_sum*)tiles, 1, 0))) return rc;
+    c->pseudo_counts = w.counts;
     ExpandArgs e;
     memset(&e, 0, sizeof(e));
     e.ops = b->d_ops;
     e.op_off = (const u64*)b->d_op_off;
     e.n_ops = b->n_ops;
-    e.tdesc = tdesc;
-    e.recs = recs;
+    e.tdesc = w.tdesc;
+    e.recs = w.recs;
     e.q_fa = base_mode ? d_q_fa : nullptr;
     e.q_fa_bytes = base_mode ? q_fa_bytes : 0;
     e.out = d_out;
     e.diag = d_diag;
     e.n_rec = b->n;
-    e.job_tiles = job_tiles;
-    e.job_skip = job_skip;
+    e.job_tiles = w.job_tiles;
+    e.job_skip = w.job_skip;
     if (base_mode)
-      WGA_LAUNCH(k_pafpseudo_stream, (u32)((jobs + 1) / 2), 128u, c->stream, e);
+      WGA_LAUNCH(k_pafpseudo_stream, (u32)((w.jobs + 1) / 2), 128u, c->stream, e);
     else
-      WGA_LAUNCH(k_pafpseudo_stream_sym, (u32)((jobs + 1) / 2), 128u, c->stream, e);
+      WGA_LAUNCH(k_pafpseudo_stream_sym, (u32)((w.jobs + 1) / 2), 128u, c->stream, e);
     LAUNCH_CHECK();
     const u32 side_grid = nt < 256 ? (u32)nt : 256u;
-    a.tile_count = counts; /* tiles of records that are not clean or lie at a pool's edge, tiles beyond 2^24 bases */
-    a.tile_list = list_fast;
+    a.tile_count = w.counts; /* tiles of records that are not clean or lie at a pool's edge, tiles beyond 2^24 bases */
+    a.tile_list = w.fast_list;
     if (base_mode)
       WGA_LAUNCH(k_pafpseudo_fill_list<true>, side_grid, WGA_BLOCK, c->stream, a);
     else
       WGA_LAUNCH(k_pafpseudo_fill_list<false>, side_grid, WGA_BLOCK, c->stream, a);
     LAUNCH_CHECK();
-    a.tile_count = counts + 1; /* ... beyond 2^31: the block kernel decides on its op-serial walk itself */
-    a.tile_list = list_wide;
+    a.tile_count = w.counts + 1; /* ... beyond 2^31: the block kernel decides on its op-serial walk itself */
+    a.tile_list = w.wide_list;
     if (base_mode)
       WGA_LAUNCH(k_pafpseudo_fill_list<true>, side_grid, WGA_BLOCK, c->stream, a);
     else

@@ -17,9 +17,13 @@
  * of the ones in front of it */
 #include <type_traits>
 
-#include "wga_kernels.h"       /* K1 stat, v1 of the row kernel, scans, layout */
+#include "wga_kernels.h"       /* the core: types, wave and block scans, the row pre-pass, the paf2maf layout */
+#include "wga_k1_stat.h"       /* K1: the stat walk */
+#include "wga_scan.h"          /* the generic scan of every count -> fill launcher (run_scan) */
+#include "wga_k2_v1.h"         /* v1 of the row kernel: expand_variant 0 and the tiles K2s leaves */
 #include "wga_kernels_k2s.h"   /* K2s: the streaming row kernel (paf2maf, pafpseudo's rows) */
 #include "wga_k_class.h"
+#include "wga_k_peers.h"       /* the multi-GPU counter reduction */
 #include "wga_k5_pafcov.h"
 #include "wga_k6_pafpseudo.h"
 #include "wga_k3_maf.h"        /* K3 / K4: the MAF walks */
@@ -35,7 +39,8 @@
 #include "wga_k13_splitters.h"
 #include "wga_k15_fasta.h"
 #include "wga_k18_bgzf_deflate.h"
-#include "wga_kernels3.h"      /* K16 VCF rows of call on PAF, K17 BGZF inflate */
+#include "wga_k16_paf_call_vcf.h" /* K16: the VCF rows of call on PAF */
+#include "wga_k17_bgzf_inflate.h" /* K17: BGZF inflate */
 #include "wga_k19_maf_call.h"  /* K19: rules and VCF rows of call on MAF */
 #include "wga_k20_maf_chunk.h" /* K20: chunk on MAF */
 #include "wga_k21_maf_slice.h" /* K21: maf-ext's slices */
@@ -114,7 +119,7 @@ struct wga_ctx {
   DevBuf maf_tab;                  /* K3 / K4: the table of a call's long blocks (header, list, pieces) */
   bool maf_hdr_clean = false;      /* the header's append counters are zero (the plan kernel leaves them so) */
   CallCache maf_cache;             /* the table of a count call, for the fill call on the same arrays */
-  int expand_variant = -1; /* the row kernel: -1 / 3 the streaming kernel (wga_kernels_k2s.h), 0 v1 (wga_kernels.h: what the
+  int expand_variant = -1; /* the row kernel: -1 / 3 the streaming kernel (wga_kernels_k2s.h), 0 v1 (wga_k2_v1.h: what the
                               streaming kernel leaves is v1's in either case).  The window kernel of rounds 3-5 (2) is gone: it was
                               ahead only below 100 ops per record (30-op records 6.1 against 7.3 ms) */
   int expand_variant_used = 0;

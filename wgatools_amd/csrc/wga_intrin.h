@@ -24,13 +24,8 @@
 
 /* index of the wave inside its block.  threadIdx.x >> 6 is the same in all 64 lanes, but the compiler's
  * divergence analysis does not know: everything derived from it (tile / record index, offsets loaded with it,
- * loop bounds) would be treated as per-lane — vector loads, exec-masked loops, VGPR-held "uniform" values.
- * WGA_WAVE_ID(t) can be switched back to the plain shift with -DWGA_WAVE_ID_PLAIN for A/B measurements. */
-#ifdef WGA_WAVE_ID_PLAIN
-#define WGA_WAVE_ID(t) ((u32)(t) >> 6)
-#else
+ * loop bounds) would be treated as per-lane — vector loads, exec-masked loops, VGPR-held "uniform" values. */
 #define WGA_WAVE_ID(t) ((u32)__builtin_amdgcn_readfirstlane((int)((u32)(t) >> 6)))
-#endif
 
 /* keep the computation of a value where it is written (the compiler otherwise sinks LDS reads into
  * exec-masked branches "to save them", which costs more in branch overhead than the reads); the 4- and 7-value forms
@@ -135,26 +130,15 @@ __device__ __forceinline__ u32 wave_get_u32_dyn(u32 v, u32 k) { return (u32)__bu
 /* lanes of a wave exchange data through LDS: hardware runs them in lockstep, only the compiler must not reorder */
 #define WGA_WAVE_SYNC() __builtin_amdgcn_wave_barrier()
 
-/* set bits of m below this lane's (v_mbcnt_lo / v_mbcnt_hi; -DWGA_MBCNT=0: popcount of the masked word, for A/B) */
-#ifndef WGA_MBCNT
-#define WGA_MBCNT 1
-#endif
+/* set bits of m below this lane's (v_mbcnt_lo / v_mbcnt_hi) */
 __device__ __forceinline__ u32 lane_rank(u64 m, u32 lane) {
-#if WGA_MBCNT
   (void)lane;
   return (u32)__builtin_amdgcn_mbcnt_hi((u32)(m >> 32), __builtin_amdgcn_mbcnt_lo((u32)m, 0u));
-#else
-  return (u32)__popcll(m & ((1ull << lane) - 1ull));
-#endif
 }
 
-/* four packed ops of a tile (-DWGA_OPS_NT: as a non-temporal load, for A/B) */
+/* four packed ops of a tile */
 __device__ __forceinline__ u32x4_a16 ops_load16(const u32* p) {
-#ifdef WGA_OPS_NT
-  return __builtin_nontemporal_load((const u32x4_a16*)p);
-#else
   return *(const u32x4_a16*)p;
-#endif
 }
 
 /* all ones when bit idx of bits is set (v_bfe_i32) */

@@ -5,7 +5,8 @@
 #ifndef WGA_K10_CHAIN_H
 #define WGA_K10_CHAIN_H
 
-#include "wga_kernels.h"
+#include "wga_text_out.h"    /* dec_digits, dec_write */
+#include "wga_k7_paf_call.h" /* piece_span: the piece table of the op walks */
 
 /* ============================================================================================ */
 /* K10: paf2chain data lines                                              */

@@ -5,7 +5,7 @@
 #ifndef WGA_K12_DOTPLOT_H
 #define WGA_K12_DOTPLOT_H
 
-#include "wga_kernels.h"
+#include "wga_k7_paf_call.h" /* piece_span: the piece table of the op walks */
 
 /* ============================================================================================ */
 /* K12: dotplot base-level segments (emit_baseplotdatas, cigar.rs:815-914) */

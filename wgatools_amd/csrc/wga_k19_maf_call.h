@@ -18,7 +18,7 @@
  *   * rows: one per column of an X run with `-s` (:570-603), one per I / D run longer than `svlen` behind an '=' / X run
  *     (:464-569), one <INV> row in front of a '-' block's chunk with `inv` (:423-440).
  * One wave per block; a chunk is three passes over its runs, 64 runs a step (boundary; the run the chunk ends in; the rows).
- * Text as K16 writes it (wga_kernels3.h: the sinks, the row frame, the step's staged stretch).  Two-call protocol: bytes per
+ * Text as K16 writes it (wga_k16_paf_call_vcf.h: the sinks, the row frame, the step's staged stretch).  Two-call protocol: bytes per
  * block and the first bad base (noodles-vcf's parse error: a REF / ALT character outside ACGTN in either case), then the text.
  * A block's text ends in front of the CHUNK that holds its first bad base: the reference collects a chunk's records before it
  * writes any of them (:137-141).  The fill pass writes block k's bytes into [out_off[k], out_off[k + 1]) and nothing else: it
@@ -27,7 +27,7 @@
 #ifndef WGA_K19_MAF_CALL_H
 #define WGA_K19_MAF_CALL_H
 
-#include "wga_kernels3.h"
+#include "wga_k16_paf_call_vcf.h"
 
 struct wga_maf_vcf_rec_dev { /* = wga_maf_vcf_rec (wga_hip.h) */
   u64 t_name_off, q_name_off; /* into `names` */

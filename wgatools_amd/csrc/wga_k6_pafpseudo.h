@@ -5,7 +5,7 @@
 #ifndef WGA_K6_PAFPSEUDO_H
 #define WGA_K6_PAFPSEUDO_H
 
-#include "wga_kernels.h"
+#include "wga_k2_v1.h" /* the windows, the granule table, emit_row and emit_tail of the block kernel */
 
 /* ============================================================================================ */
 /* K6: pafpseudo                                                                                */

@@ -1,5 +1,6 @@
 /*
- * wga_k_class.h — class sums of the op stream per tile and per record (shared first pass of pafcov and pafpseudo), the stat totals.
+ * wga_k_class.h — class sums of the op stream per tile and per record (shared first pass of pafcov and pafpseudo), the stat totals,
+ * and the two small copies of the launchers (k_copy_u64, k_scatter_bytes).
  * One header per kernel family; wga_capi.cpp includes them in dependency order (a header may use helpers of the ones in front of it).
  */
 #ifndef WGA_K_CLASS_H
@@ -40,7 +41,7 @@ __global__ __launch_bounds__(256) void k_class_tiles(const u32* __restrict__ ops
   const u32 r_first = r;
   u64 cur = tile_start;
   u64 tot[5] = {0, 0, 0, 0, 0}, tail[5] = {0, 0, 0, 0, 0};
-  /* The sums as K1 makes them since round 6 (wga_kernels.h): a class sum is `len & mask`, the mask one v_bfe_i32 of a class
+  /* The sums as K1 makes them since round 6 (wga_k1_stat.h): a class sum is `len & mask`, the mask one v_bfe_i32 of a class
    * constant (its 16 bits standing twice) by the packed op itself; the fifth class is what the four others leave of the sum of
    * all lengths; the whole tile is summed first, without a range test, and a tile's last segment is what the segments in front
    * leave of it; one 32-bit reduction per sum when no lane's lengths reach 2^26.  14 vector instructions per op (17 with the
@@ -139,6 +140,17 @@ __global__ __launch_bounds__(256) void k_class_tiles(const u32* __restrict__ ops
 __global__ __launch_bounds__(256) void k_copy_u64(u64 n, const u64* __restrict__ src, u64* __restrict__ dst) {
   const u64 i = (u64)blockIdx.x * WGA_BLOCK + threadIdx.x;
   if (i < n) dst[i] = src[i];
+}
+
+/* copy n variable-length snippets (MAF line text between the rows) */
+__global__ __launch_bounds__(256) void k_scatter_bytes(u32 n, const u8* src, const u64* src_off,
+                                                       u8* dst, const u64* dst_off) {
+  /* one wave per snippet; snippets are tens of bytes */
+  const u32 lane = threadIdx.x & 63u;
+  const u64 i = (u64)blockIdx.x * 4 + WGA_WAVE_ID(threadIdx.x);
+  if (i >= n) return;
+  const u64 s0 = src_off[i], s1 = src_off[i + 1], d0 = dst_off[i];
+  for (u64 k = s0 + lane; k < s1; k += 64) dst[d0 + (k - s0)] = src[k];
 }
 
 /* ============================================================================================ */
