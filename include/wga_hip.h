@@ -783,6 +783,53 @@ int wga_paf_filter(wga_ctx*, const uint8_t* d_text, uint64_t n_bytes, const wga_
                    const wga_paf_filter_params*, void* d_work, uint64_t* text_bytes, uint64_t* n_kept,
                    uint64_t* first_inexact_line, uint8_t* d_out);
 
+/* ---- K29: `validate --fix` — the plan and the end-fixing line writer (tools/validate.rs:71-141 with the csv writer of
+ *      parser/paf.rs:50-65; replaces the record loop of the host's cmd_validate, which parsed every tag of every record into a
+ *      string and printed every record again field by field) --------------------------------------------------------------
+ * K24's observation applies unchanged: for a plain line whose nine numbers are in canonical decimal the csv writer gives back
+ * the line's bytes, and `--fix` changes at most two of those numbers per record, column 4 (query_end) and column 9
+ * (target_end).  Both entries work on d_text, n_bytes and d_lines[n_lines] — the arguments and the result of wga_paf_split on
+ * the same text, with K24's limits: n_bytes < 0xFFFFFFF0, 16 bytes of slack behind the text, n_lines < 2^32.  Both are called
+ * twice with the same arguments; the two calls of an entry share d_work (wga_paf_fix_work_bytes(n_lines) bytes of device
+ * memory, 8-byte aligned) and keep nothing else between them; wga_paf_fix reads nothing wga_paf_fix_plan left there.
+ * n_lines == 0: zero counts and success.
+ *
+ * wga_paf_fix_plan decides whether the text is TAKEN and where its CIGARs are.  A line is UNTAKEN when it is INEXACT by K24's
+ * rule (WGA_PAF_FALLBACK, a byte >= 0x80, or WGA_PAF_OK with one of its nine numbers starting with `+` or with `0` and another
+ * digit), or when it is WGA_PAF_OK with cg_beg == WGA_NONE (validate.rs:79 unwraps an error there: that text is the caller's
+ * csv-semantics path's).  Every line is checked.
+ *   d_cg_beg == NULL and d_cg_end == NULL: *n_records = the number of WGA_PAF_OK lines, *first_untaken_line = the lowest
+ *              untaken line, WGA_NONE when the text is taken (host values; synchronises).  If a line is untaken,
+ *              *n_records = 0.
+ *   otherwise: d_cg_beg[*n_records] and d_cg_end[*n_records], the records' cg:Z: spans in line order (wga_cigar_tokenise_spans'
+ *              arguments); no other byte is written, and nothing at all when *n_records == 0.
+ *
+ * wga_paf_fix writes three texts from d_counts[n_records], wga_cigar_stat's counts of the records in line order (n_records =
+ * the number of WGA_PAF_OK lines, WGA_E_INVALID_ARG otherwise).  For record k on line i, wrapping mod 2^64 as the release build:
+ *   eq = num[1] + match + mismatch + ins_bp + inv_ins_bp,  et = num[4] + match + mismatch + del_bp + inv_del_bp
+ *   rows   for every WGA_PAF_OK line, in input order: the line's bytes from its first byte up to (not including) its `\n`, or
+ *          up to n_bytes for an unterminated last line, with column 4 replaced by the canonical decimal of eq when
+ *          eq != num[2] and column 9 by that of et when et != num[5], then `\n`.  WGA_PAF_SKIP lines are not written.  The
+ *          columns are found by their tabs from the line's first byte (a taken line has no tab inside a name).
+ *   qlist  for every record with eq != num[2], in input order: `<qname>:<num[1]>-<num[2]>\n` (the old end).
+ *   tlist  likewise `<tname>:<num[4]>-<num[5]>\n` for et != num[5].
+ *   d_rows == d_qlist == d_tlist == NULL: places and sizes; *sizes (host values; synchronises).
+ *   otherwise: every text whose pointer is not NULL at [0, *_bytes) of its buffer (16-byte aligned), no byte outside that
+ *              extent; *sizes is read as the first call left it.
+ * The call is meant for a text wga_paf_fix_plan takes; on any other it reads and writes nothing outside its arguments'
+ * extents, and its texts are not specified. */
+typedef struct {
+  uint64_t rows_bytes, qlist_bytes, tlist_bytes;
+  uint64_t n_records, n_q_bad, n_t_bad;
+} wga_paf_fix_sizes; /* 48 bytes */
+#define WGA_PAF_FIX_TILE_BYTES 8192 /* the rows leave in tiles of this many bytes, one per block (tests place edits by it) */
+uint64_t wga_paf_fix_work_bytes(uint64_t n_lines);
+int wga_paf_fix_plan(wga_ctx*, const uint8_t* d_text, uint64_t n_bytes, const wga_paf_line* d_lines, uint64_t n_lines, void* d_work,
+                     uint64_t* n_records, uint64_t* first_untaken_line, uint64_t* d_cg_beg, uint64_t* d_cg_end);
+int wga_paf_fix(wga_ctx*, const uint8_t* d_text, uint64_t n_bytes, const wga_paf_line* d_lines, uint64_t n_lines,
+                const wga_cigar_counts* d_counts, uint64_t n_records, void* d_work, wga_paf_fix_sizes* sizes, uint8_t* d_rows,
+                uint8_t* d_qlist, uint8_t* d_tlist);
+
 /* ---- K25: `filter -f chain` — the chain record writer (replaces the formatting loop of the host's cmd_filter_chain,
  *      wgatools_amd/host/cmd_filter.inc:345-382 of the commit before it: every data line downloaded as 24 bytes and printed by
  *      one CPU thread; in the reference chain.rs:92-100,185-204 behind the selection of tools/filter.rs:17-39,91-105) ---------

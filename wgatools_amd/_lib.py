@@ -101,6 +101,9 @@ PROTOTYPES = {
     "wga_paf_filter_work_bytes": (C.c_uint64, [C.c_uint64]),
     "wga_paf_filter": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                  C.POINTER(C.c_uint64), vp]),
+    "wga_paf_fix_work_bytes": (C.c_uint64, [C.c_uint64]),
+    "wga_paf_fix_plan": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp, vp]),
+    "wga_paf_fix": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp, vp, vp]),
     "wga_chain_filter_work_bytes": (C.c_uint64, [C.c_uint64, C.c_uint64]),
     "wga_chain_filter": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp, vp, C.POINTER(C.c_uint64),
                                    C.POINTER(C.c_uint64), vp]),

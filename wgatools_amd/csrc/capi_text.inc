@@ -78,6 +78,37 @@ static int split_lines(wga_ctx* c, const uint8_t* d_text, uint64_t n_bytes, uint
   return WGA_OK;
 }
 
+/* What the count calls of K24's filter and of K29's two entries (capi_paf_fix.inc) start with: the newline list of the text at
+ * nl_pos[n] and the first line with a byte >= 0x80 in *hdr (reset here).  The scratch holds the text blocks' newline counts,
+ * scanned in place (+ total), that scan's partials and room for the partials of scans over up to n values (*partial);
+ * *n_nl_p = the device's count of newlines (the line kernels read it). */
+static int paf_newline_list(wga_ctx* c, const uint8_t* d_text, uint64_t n_bytes, u32 n, u32* nl_pos, K24Hdr* hdr, const u64** n_nl_p,
+                            u64** partial) {
+  int rc;
+  const u32 nb = (u32)((n_bytes + 4095u) / 4096u);
+  void* ws = nullptr;
+  if ((rc = ctx_scratch(c, ((size_t)nb + 1 + (size_t)nb / 1024 + 4 + (size_t)n / 1024 + 4) * sizeof(u64), &ws))) return rc;
+  u64* blk = (u64*)ws;
+  u64* bpartial = blk + nb + 1;
+  *partial = bpartial + (size_t)nb / 1024 + 4;
+  *n_nl_p = blk + nb;
+  RT_CHECK(rt_memset(hdr, 0xFF, sizeof(K24Hdr), c->stream));
+  WGA_LAUNCH(k_paf_newlines<false>, nb, WGA_BLOCK, c->stream, d_text, (u64)n_bytes, blk, (const u64*)nullptr, (u32*)nullptr, (u64)0,
+             (K24Hdr*)nullptr);
+  LAUNCH_CHECK();
+  ScanPlain f;
+  f.in = blk;
+  if ((rc = run_scan_ws(c, f, nb, blk, bpartial))) return rc;
+  u64 n_nl = 0;
+  u8 last = 0;
+  RT_CHECK(rt_d2h(&n_nl, blk + nb, sizeof n_nl, c->stream));
+  RT_CHECK(rt_d2h(&last, d_text + n_bytes - 1, 1, c->stream));
+  if (n_nl + (last != (u8)0x0A ? 1u : 0u) != (u64)n) return fail(WGA_E_INVALID_ARG, "n_lines is not this text's", nullptr);
+  WGA_LAUNCH(k_paf_newlines<true>, nb, WGA_BLOCK, c->stream, d_text, (u64)n_bytes, (u64*)nullptr, (const u64*)blk, nl_pos, (u64)n, hdr);
+  LAUNCH_CHECK();
+  return WGA_OK;
+}
+
 extern "C" {
 
 int wga_cigar_tokenise(wga_ctx* c, uint32_t n, const uint8_t* d_text, const uint64_t* d_text_off,
@@ -147,36 +178,18 @@ int wga_paf_filter(wga_ctx* c, const uint8_t* d_text, uint64_t n_bytes, const wg
     *n_kept = 0;
     *first_inexact_line = WGA_NONE;
     if (n == 0) return WGA_OK;
-    /* scratch: the text blocks' newline counts, scanned in place (+ total) | that scan's partials | the line scan's partials */
-    const u32 nb = (u32)((n_bytes + 4095u) / 4096u);
-    void* ws = nullptr;
-    if ((rc = ctx_scratch(c, ((size_t)nb + 1 + (size_t)nb / 1024 + 4 + (size_t)n / 1024 + 4) * sizeof(u64), &ws))) return rc;
-    u64* blk = (u64*)ws;
-    u64* partial = blk + nb + 1;
-    u64* lpartial = partial + (size_t)nb / 1024 + 4;
-    RT_CHECK(rt_memset(hdr, 0xFF, sizeof(K24Hdr), c->stream));
-    WGA_LAUNCH(k_paf_newlines<false>, nb, WGA_BLOCK, c->stream, d_text, (u64)n_bytes, blk, (const u64*)nullptr, (u32*)nullptr,
-               (u64)0, (K24Hdr*)nullptr);
-    LAUNCH_CHECK();
-    ScanPlain f;
-    f.in = blk;
-    if ((rc = run_scan_ws(c, f, nb, blk, partial))) return rc;
-    u64 n_nl = 0;
-    u8 last = 0;
-    RT_CHECK(rt_d2h(&n_nl, blk + nb, sizeof n_nl, c->stream));
-    RT_CHECK(rt_d2h(&last, d_text + n_bytes - 1, 1, c->stream));
-    if (n_nl + (last != (u8)0x0A ? 1u : 0u) != n_lines) return fail(WGA_E_INVALID_ARG, "n_lines is not this text's", nullptr);
-    WGA_LAUNCH(k_paf_newlines<true>, nb, WGA_BLOCK, c->stream, d_text, (u64)n_bytes, (u64*)nullptr, (const u64*)blk, nl_pos,
-               (u64)n, hdr);
-    LAUNCH_CHECK();
+    const u64* n_nl_p = nullptr;
+    u64* lpartial = nullptr;
+    if ((rc = paf_newline_list(c, d_text, n_bytes, n, nl_pos, hdr, &n_nl_p, &lpartial))) return rc;
     wga_paf_filter_params_dev Pd;
     Pd.min_block_size = params->min_block_size;
     Pd.min_query_size = params->min_query_size;
     Pd.pair_of_line = params->d_pair_of_line;
     Pd.pair_keep = params->d_pair_keep;
-    WGA_LAUNCH(k_paf_filter_lines, (n + 255u) / 256u, WGA_BLOCK, c->stream, d_text, (u64)n_bytes, (u64)n, (const u64*)(blk + nb),
+    WGA_LAUNCH(k_paf_filter_lines, (n + 255u) / 256u, WGA_BLOCK, c->stream, d_text, (u64)n_bytes, (u64)n, n_nl_p,
                (const u32*)nl_pos, (const wga_paf_line_dev*)d_lines, Pd, ksrc, hdr);
     LAUNCH_CHECK();
+    ScanPlain f;
     f.in = ksrc;
     if ((rc = run_scan_ws(c, f, n, P, lpartial))) return rc;
     WGA_LAUNCH(k_paf_filter_compact, (n + 255u) / 256u, WGA_BLOCK, c->stream, (u64)n, (const u32*)nl_pos, (const u64*)P, koff, ksrc);

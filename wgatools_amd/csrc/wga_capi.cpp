@@ -51,6 +51,7 @@
 #include "wga_k26_dotplot_csv.h" /* K26: the base-level csv rows of dotplot */
 #include "wga_k27_chain2paf.h" /* K27: the PAF record writer of chain2paf */
 #include "wga_k28_maf2paf.h" /* K28: the PAF record writer of maf2paf */
+#include "wga_k29_paf_fix.h" /* K29: the end-fixing line writer of validate --fix */
 
 /* A grow-only device buffer of a context.  reserve() leaves it with room for `need` bytes: one that is too small is freed
  * behind the work of the context's stream and allocated anew with `grow` (>= need) bytes — every site has its own growth rule —,
@@ -590,6 +591,7 @@ int wga_ctx_get_param(wga_ctx* c, const char* name, int64_t* value) {
 #include "capi_maf.inc"
 #include "capi_opwalk.inc"
 #include "capi_text.inc"
+#include "capi_paf_fix.inc"
 #include "capi_chain_write.inc"
 #include "capi_chain2paf.inc"
 #include "capi_maf2paf.inc"

@@ -9,7 +9,7 @@
  *             of the newlines in order, which give every line its extent (wga_paf_line does not carry it); the fill pass also
  *             knows every byte's line and takes the first line with a byte >= 0x80 by atomicMin.
  *   lines     one thread per line: the keep flag (thresholds, or the pair's flag), the canonical-number check (reads up to the
- *             line's 12th tab) and the length of the line's text; one scan of (length | keep << 32) places the kept lines
+ *             line's 12th tab: WGA_PAF_NUMBERS_INEXACT, which K29's plan expands too) and the length of the line's text; one scan of (length | keep << 32) places the kept lines
  *             among the kept lines and in the text, k_paf_filter_compact lists them.
  *   fill      the text in tiles of WGA_PAF_FILTER_TILE bytes, one per block: the tile's lines by binary search in the kept
  *             lines' places, their bytes through maf_tile_slices (16-byte groups: one unaligned load + one aligned LDS store
@@ -93,6 +93,22 @@ __device__ __forceinline__ void paf_line_extent(const u32* __restrict__ nl_pos, 
   *e = i < n_newlines ? (u64)nl_pos[i] : n_bytes;
 }
 
+/* the exactness predicate's part on an OK line text[s, e), shared by K24's filter and K29's plan: the csv writer prints the nine
+ * numbers anew (u64 Display), so `+5`, `007` and `00` would change.  Sets `inexact`, never clears it.  A macro and not a function:
+ * k_paf_filter_lines keeps, instruction for instruction, the code it had when the loop stood in it. */
+#define WGA_PAF_NUMBERS_INEXACT(text, s, e, inexact)                                               \
+  {                                                                                                \
+    u64 fs = (s);                                                                                  \
+    for (u32 nf = 0; nf < 12u && fs <= (e); nf++) {                                                \
+      if (nf - 1u < 3u || nf - 6u < 6u) {                                                          \
+        const u32 c0 = fs < (e) ? (text)[fs] : 0u, c1 = fs + 1u < (e) ? (text)[fs + 1u] : 0u;      \
+        if (c0 == (u32)'+' || (c0 == (u32)'0' && c1 - 0x30u <= 9u)) (inexact) = true;              \
+      }                                                                                            \
+      while (fs < (e) && (text)[fs] != 0x09u) fs++;                                                \
+      fs++;                                                                                        \
+    }                                                                                              \
+  }
+
 /* val[i] = the bytes line i adds to the text (its own and a newline; 0 when it is dropped) | kept << 32 */
 __global__ __launch_bounds__(256) void k_paf_filter_lines(const u8* __restrict__ text, u64 n_bytes, u64 n_lines,
                                                           const u64* __restrict__ n_newlines_p,
@@ -107,16 +123,7 @@ __global__ __launch_bounds__(256) void k_paf_filter_lines(const u8* __restrict__
   const u32 status = lines[i].status;
   bool inexact = status == WGA_PAF_FALLBACK, keep = false;
   if (status == WGA_PAF_OK) {
-    /* the csv writer prints the nine numbers anew (u64 Display): `+5`, `007` and `00` would change */
-    u64 fs = s;
-    for (u32 nf = 0; nf < 12u && fs <= e; nf++) {
-      if (nf - 1u < 3u || nf - 6u < 6u) {
-        const u32 c0 = fs < e ? text[fs] : 0u, c1 = fs + 1u < e ? text[fs + 1u] : 0u;
-        if (c0 == (u32)'+' || (c0 == (u32)'0' && c1 - 0x30u <= 9u)) inexact = true;
-      }
-      while (fs < e && text[fs] != 0x09u) fs++;
-      fs++;
-    }
+    WGA_PAF_NUMBERS_INEXACT(text, s, e, inexact)
     if (P.pair_keep) {
       const u32 p = P.pair_of_line[i];
       keep = p != 0xFFFFFFFFu && P.pair_keep[p] != 0;

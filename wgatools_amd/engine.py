@@ -36,6 +36,9 @@ PAF_FILTER_PARAMS_DTYPE = np.dtype([("min_block_size", "<u8"), ("min_query_size"
                                     ("d_pair_keep", "<u8")])
 PAF_OK, PAF_SKIP, PAF_FALLBACK = 0, 1, 2
 PAF_FILTER_TILE = 8192
+# K29 (include/wga_hip.h wga_paf_fix_sizes; WGA_PAF_FIX_TILE_BYTES)
+PAF_FIX_SIZES_DTYPE = np.dtype([(k, "<u8") for k in ("rows_bytes", "qlist_bytes", "tlist_bytes", "n_records", "n_q_bad", "n_t_bad")])
+PAF_FIX_TILE = 8192
 # K25 (include/wga_hip.h wga_chain_filter_params)
 CHAIN_FILTER_PARAMS_DTYPE = np.dtype([("min_block_size", "<u8"), ("min_query_size", "<u8")])
 # K28 (include/wga_hip.h wga_maf2paf_head)
@@ -453,6 +456,58 @@ class Engine:
         if not ((got[:guard] == 0xA5).all() and (got[guard + first[0]:] == 0xA5).all()):
             raise _lib.WgaError("wga_paf_filter wrote outside d_out[0 .. text_bytes)")
         return got[guard:guard + first[0]].tobytes(), first[1], (None if first[2] == int(NONE) else first[2])
+
+    def paf_fix_plan(self, text, n_bytes, lines, n_lines):
+        """K29 (validate.rs:71-141): is the text of wga_paf_split's table taken, and where are its CIGARs: both calls of
+        wga_paf_fix_plan.  Returns (n_records, first untaken line or None, cg_beg, cg_end as device arrays of u64); the
+        words behind the two arrays, and all of them for an untaken text, are checked to be left alone."""
+        n_lines = int(n_lines)
+        work = self.empty(max(int(self.lib.wga_paf_fix_work_bytes(n_lines)), 16), np.uint8)
+        nr, bad = C.c_uint64(0), C.c_uint64(0)
+        args = (self.ctx, _p(text), int(n_bytes), _p(lines), n_lines, _p(work), C.byref(nr), C.byref(bad))
+        self._check(self.lib.wga_paf_fix_plan(*args, None, None))
+        first = (int(nr.value), int(bad.value))
+        cap = first[0] if first[1] == int(NONE) else n_lines     # an untaken text: room the second call must not use
+        beg = self.empty(cap + 2, np.uint64).fill(0xA5)
+        end = self.empty(cap + 2, np.uint64).fill(0xA5)
+        self._check(self.lib.wga_paf_fix_plan(*args, _p(beg), _p(end)))
+        self.sync()
+        if (int(nr.value), int(bad.value)) != first:
+            raise _lib.WgaError("wga_paf_fix_plan changed its counts in the second call")
+        a5 = np.uint64(0xA5A5A5A5A5A5A5A5)
+        if not ((beg.numpy()[first[0]:] == a5).all() and (end.numpy()[first[0]:] == a5).all()):
+            raise _lib.WgaError("wga_paf_fix_plan wrote outside its span arrays")
+        return first[0], (None if first[1] == int(NONE) else first[1]), beg, end
+
+    def paf_fix(self, text, n_bytes, lines, n_lines, counts, n_records, want=(True, True, True)):
+        """K29: the rows with corrected ends and the two invalid lists from wga_cigar_stat's counts of the records, both calls
+        of wga_paf_fix.  want = which of (rows, qlist, tlist) the second call is given a buffer for.  Returns (rows, qlist,
+        tlist, sizes as a dict), a text that was not asked for as None; the 64 bytes in front of and behind every text are
+        checked."""
+        n_lines = int(n_lines)
+        work = self.empty(max(int(self.lib.wga_paf_fix_work_bytes(n_lines)), 16), np.uint8)
+        sizes = np.zeros(1, dtype=PAF_FIX_SIZES_DTYPE)
+        args = (self.ctx, _p(text), int(n_bytes), _p(lines), n_lines, _p(counts), int(n_records), _p(work), sizes.ctypes.data)
+        self._check(self.lib.wga_paf_fix(*args, None, None, None))
+        first = sizes.copy()
+        guard = 64  # bytes around each text that the fill call must leave alone
+        nbytes = [int(first[k][0]) for k in ("rows_bytes", "qlist_bytes", "tlist_bytes")]
+        outs = [self.upload(np.full(nb + 2 * guard, 0xA5, dtype=np.uint8)) if w else None for nb, w in zip(nbytes, want)]
+        if any(want):
+            self._check(self.lib.wga_paf_fix(*args, *[o.ptr + guard if o is not None else None for o in outs]))
+        self.sync()
+        if sizes.tobytes() != first.tobytes():
+            raise _lib.WgaError("wga_paf_fix changed *sizes in the second call")
+        texts = []
+        for o, nb in zip(outs, nbytes):
+            if o is None:
+                texts.append(None)
+                continue
+            got = o.numpy()
+            if not ((got[:guard] == 0xA5).all() and (got[guard + nb:] == 0xA5).all()):
+                raise _lib.WgaError("wga_paf_fix wrote outside a text's extent")
+            texts.append(got[guard:guard + nb].tobytes())
+        return texts[0], texts[1], texts[2], {k: int(first[k][0]) for k in PAF_FIX_SIZES_DTYPE.names}
 
     def maf_split(self, text, n_bytes, lines=None):
         """K14: number of text lines (lines is None), or the wga_maf_line of every line"""

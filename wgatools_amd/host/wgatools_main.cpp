@@ -1437,6 +1437,9 @@ static int run_command(int argc, char** argv) {
     if (cmd == "__paf_filter_path") { /* which path `filter -f paf` takes for every piece of this file */
       return paf_filter_paths(rest.empty() ? nullptr : &rest[0]);
     }
+    if (cmd == "__validate_fix_path") { /* which path `validate --fix` takes for every piece of this file */
+      return validate_fix_paths(rest.empty() ? nullptr : &rest[0]);
+    }
     if (cmd == "__chain_filter_path") { /* which path `filter -f chain` takes for this file */
       return chain_filter_path(rest.empty() ? nullptr : &rest[0]);
     }
