@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""Mutation check of the op walks' 32-bit corners.  CPU ONLY: it builds the SIMT-emulator library and runs
+"""Mutation check of the kernels against the emulator suite: the op walks' 32-bit corners (--table walks, the default) and the
+file readers, the `.gz` writer and the MAF walks' long blocks (--table readers: K13, K14, K15, K18, K3 / K4).  CPU ONLY: it builds the SIMT-emulator library and runs
 tests/test_emu_parity.py on it; it is not part of pytest and is never run on a GPU machine.
 
-Each row of MUTANTS makes one kernel subtly wrong (one exact text edit in wgatools_amd/csrc).  The script copies the tree to a
+Each row of a table makes one kernel subtly wrong (one exact text edit in wgatools_amd/csrc).  The script copies the tree to a
 temporary directory, and for every row applies the edit there, rebuilds tests/emu/libwgaemu.so (build.build_emu(force=True)),
 runs `pytest tests/test_emu_parity.py -k <the row's expression>` in one process and prints KILLED (a test failed) or SURVIVED
 (all passed).  A first row without an edit must PASS: a suite that fails on the right kernels kills nothing.  Nothing outside
@@ -11,8 +12,10 @@ the temporary copy is touched.
     python scripts/emu_mutants.py                  # the working tree's tests
     python scripts/emu_mutants.py --tests-rev REV  # tests/parity_cases.py and tests/test_emu_parity.py as of commit REV
     python scripts/emu_mutants.py --only k5_hi k7_nxt
+    python scripts/emu_mutants.py --table readers  # MUTANTS_READERS instead of MUTANTS
 
-profiles/emu_mutants.txt holds both outputs for the commit that added the wide-step cases.
+profiles/emu_mutants.txt holds both outputs for the commit that added the wide-step cases, profiles/emu_mutants_readers.txt
+those of the readers' table for the commit that added it.
 """
 import argparse
 import os
@@ -65,6 +68,44 @@ MUTANTS = [
      "len[e] > (u32)svlen || cont_follows", "paf_call"),
 ]
 
+# The readers, the .gz writer and the long blocks of the MAF walks.  The K3 rows select `test_maf_ and not split`: `maf` alone
+# would take every paf2maf test along.
+K13, K15, K18, K3 = CSRC + "wga_k13_splitters.h", CSRC + "wga_k15_fasta.h", CSRC + "wga_k18_bgzf_deflate.h", CSRC + "wga_k3_maf.h"
+MAF_WALKS = "test_maf_ and not split"
+MUTANTS_READERS = [
+    ("k13_emptycg", K13, "if (fe - fs >= 5u && text[fs] == (u8)'c'", "if (fe - fs > 5u && text[fs] == (u8)'c'", "paf_split"),
+    ("k13_digits20", K13, "if (a >= b || b - a > 20u) return false;", "if (a >= b || b - a > 19u) return false;", "paf_split or maf_split"),
+    ("k15_lonecr", K15, "const bool eol = ch == (u8)'\\n' || (ch == (u8)'\\r' && nx == (u8)'\\n');",
+     "const bool eol = ch == (u8)'\\n' || ch == (u8)'\\r';", "fasta_pool"),
+    ("k15_hdr_gt", K15, "hm |= (ch == (u8)'>' && prev == (u8)'\\n') ? 1u << j : 0u;",
+     "hm |= (ch == (u8)'>' && (prev == (u8)'\\n' || prev == (u8)'\\r')) ? 1u << j : 0u;", "fasta_pool"),
+    ("k18_halve", K18, "if (s <= 256u && s_wt[s]) s_wt[s] = (s_wt[s] + 1u) >> 1;", "if (s <= 256u && s_wt[s]) s_wt[s] = 1u;", "bgzf_deflate"),
+    ("k18_rank", K18, "const u32 wv = s <= 256u ? s_wt[s] : 0u;", "const u32 wv = s <= 256u && s_wt[s] ? 1u + (s_wt[s] >> 3) : 0u;",
+     "bgzf_deflate"),
+    ("k18_tie", K18, "if (la <= nq) {", "if (la < nq) {", "bgzf_deflate"),
+    ("k3_short_max", K3, "#define WGA_MAF_SHORT_MAX 61440u", "#define WGA_MAF_SHORT_MAX 80000u", MAF_WALKS),
+    ("k3_fold", K3, "if (++since == WGA_MAF_FOLD_STEPS) {", "if (++since == 40u) {", MAF_WALKS),
+    ("k3_tail_lane", K3, "const u32 vidx = !in ? 32u : tail ? 32u - rem : 0u;", "const u32 vidx = !in ? 32u : tail ? 33u - rem : 0u;", MAF_WALKS),
+    ("k3_textpath", K3, "if (__ballot((hi & 0x80808080u) != 0u) == 0ull) { /* wave-uniform; text:", "if (true) { /* wave-uniform; text:",
+     MAF_WALKS),
+    ("scan_final", CSRC + "wga_scan.h", "u64 ex = block_excl_scan_u64(v, s_w, &tot) + partial[blockIdx.x];",
+     "u64 ex = block_excl_scan_u64(v, s_w, &tot);", "fasta_pool or scan_and_scatter"),
+    ("txt_digits10", CSRC + "wga_text_out.h", "if (w >= 10000u) return n + 4u;", "if (w >= 10000u) return n + 3u;", MAF_WALKS),
+    # rows chosen after reading the kernels
+    ("k13_plus", K13, "if (a < b && text[a] == (u8)'+') a++;", "if (false) a++;", "paf_split or maf_split"),
+    ("k14_token1", K13, "if (p > prev) { /* a token */", "if (p > prev + 1u) { /* a token */", "maf_split"),
+    ("k15_finish", K15, "if (contigs[k].hdr_end + 1u >= n_bytes) contigs[k].pool_off = total;",
+     "if (contigs[k].hdr_end + 1u > n_bytes) contigs[k].pool_off = total;", "fasta_pool"),
+    ("k15_block_hdr", K15, "while (k + 1 < (i64)nh && contigs[k + 1].hdr_start < c) k++;",
+     "while (k + 1 < (i64)nh && contigs[k + 1].hdr_start <= c) k++;", "fasta_pool"),
+    ("k18_stored", K18, "const bool stored = dyn >= sto;", "const bool stored = dyn > sto;", "bgzf_deflate"),
+    ("k18_depth16", K18, "const bool too_deep = __ballot(deepest > 15u) != 0ull;", "const bool too_deep = __ballot(deepest > 16u) != 0ull;",
+     "bgzf_deflate"),
+    ("k18_eob", K18, "      c = 1u;\n", "      c = 2u;\n", "bgzf_deflate"),
+]
+TABLES = {"walks": MUTANTS, "readers": MUTANTS_READERS}
+
+
 def copy_sources(work):
     """the files git tracks, and the new ones it does not ignore, as they stand in the working tree: no build product travels"""
     names = subprocess.run(["git", "-C", ROOT, "ls-files", "-z", "--cached", "--others", "--exclude-standard"], check=True,
@@ -100,6 +141,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--tests-rev", help="take %s and %s from this commit" % TEST_FILES)
     ap.add_argument("--only", nargs="*", help="names of the rows to run")
+    ap.add_argument("--table", choices=sorted(TABLES), default="walks", help="the table of mutants (default: walks)")
     a = ap.parse_args()
     tmp = tempfile.mkdtemp(prefix="emu_mutants_")
     work = os.path.join(tmp, "tree")
@@ -112,8 +154,8 @@ def main():
                                       stdout=subprocess.PIPE).stdout
                 with open(os.path.join(work, f), "wb") as fh:
                     fh.write(text)
-        print("# tests: %s" % (a.tests_rev or "working tree"))
-        rows = [m for m in MUTANTS if not a.only or m[0] in a.only]
+        print("# tests: %s, table: %s" % (a.tests_rev or "working tree", a.table))
+        rows = [m for m in TABLES[a.table] if not a.only or m[0] in a.only]
         exprs = sorted({m[4] for m in rows})
         t0 = time.time()
         verdict, tail = judge(work, " or ".join("(%s)" % e for e in exprs))

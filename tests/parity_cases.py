@@ -1866,9 +1866,44 @@ def check_paf_split(eng, text):
                 assert (a1[int(oo[k]):int(oo[k + 1])] == a2[int(oo[k]):int(oo[k + 1])]).all(), k
 
 
+def paf_short_tag_texts():
+    """tags at their shortest: a 12-column line and a tag that is exactly `cg:Z:` (an EMPTY span, which still wins over a later
+    cg:Z: and still keeps a cs:Z: from being a fallback), exactly `cs:Z:` (a fallback), one byte short of a tag, and a
+    `cg:Z:` that closes a file without a newline"""
+    base = b"q\t1\t2\t3\t+\tt\t4\t5\t6\t7\t8\t9"
+    assert base.count(b"\t") == 11
+    tags = [b"cg:Z:", b"cg:Z:\tcg:Z:5=", b"cs:Z:", b"cg:Z", b"xg:Z:5=\tcs:Z:\tcg:Z:3=", b"NM:i:1\tcg:Z:"]
+    lines = [base + b"\t" + t for t in tags]
+    texts = [ln + b"\n" for ln in lines] + [b"\n".join(lines) + b"\n", b"\n".join(lines[1:] + lines[:1])]
+    assert texts[-1].endswith(b"\tcg:Z:") and texts[0].endswith(b"\tcg:Z:\n")
+    want = expected_paf_lines(texts[-2])                # the reference sees what the comments say
+    assert [w["status"] for w in want] == [0, 0, 2, 0, 0, 0]
+    assert want[0]["cg"][0] == want[0]["cg"][1] and want[1]["cg"][0] == want[1]["cg"][1] and want[3]["cg"] is None
+    assert want[4]["cg"][1] - want[4]["cg"][0] == 2
+    return texts
+
+
 # ------------------------------------------------------------------------------------------------
 # K14 MAF line splitter
 # ------------------------------------------------------------------------------------------------
+def maf_one_byte_token_texts():
+    """s-lines whose name and whose seventh token (the row) are ONE byte long, each as the first and as the last byte of a
+    16-byte group of the text (what one thread of the delimiter pass reads)"""
+    out = []
+    for name_at in (0, 15):
+        for seq_at in (0, 15):
+            text = bytearray(b"##maf\na\ns")
+            text += b" " * ((name_at - len(text) - 1) % 16 + 1) + b"n 1 1 + 9"
+            text += b" " * ((seq_at - len(text) - 1) % 16 + 1) + b"A\ns m 0 1 - 9 C\n\n"
+            text = bytes(text)
+            n, a = text.index(b"n 1 1"), text.index(b"A\n")
+            assert (n % 16, a % 16) == (name_at, seq_at) and text[n - 1:n + 2] == b" n " and text[a - 1:a + 2] == b" A\n"
+            want = expected_maf_lines(text)
+            assert want[2]["name"] == (n, 1) and want[2]["seq"] == (a, 1) and want[3]["status"] == 0
+            out.append(text)
+    return out
+
+
 def expected_maf_lines(text):
     """what MAFReader + parse_sline (maf.rs:25-36,138-211,371-421) make of every line that needs no
     Unicode-aware splitting; status 0 s-line, 1 other, 2 fallback"""
@@ -1964,6 +1999,51 @@ FASTA_CASES = [
     b">x\r\nAC\r\nGT\r\n>y\r\nTT\r", b">e1\n>e2\n>e3\nA\n>e4\n", b">t\tname\nNNNNacgtRYKM\n\n\nAC\n",
     b">s\nAC>GT\n>\nTT\n> spaced\nGG\n", b">dup\nAAAA\n>dup\nCCCC\n",
 ]
+
+# a '\r' that does not stand in front of a '\n' is a byte like any other: kept in a sequence line, and no line start for a '>'
+FASTA_LONE_CR_CASES = [
+    b">a\nAC\rGT\n",                 # inside a sequence line: the byte is kept
+    b">a\nAC\r>b\nGG\n",             # in front of a '>': no header, one contig of seven bytes
+    b">a\nAC\r\r\nGT\n",             # \r\r\n: only the '\r' in front of the '\n' goes
+    b">a\r", b">a\r\n",              # a header and nothing else
+    b"\r>a\nAC\n",                   # junk in front: the '>' is no header, nothing is kept
+    b">a\nAC\n\r>b\nGG\n",           # ... and behind a contig: '\r>b' is a sequence line
+]
+for _t in FASTA_LONE_CR_CASES[:3] + FASTA_LONE_CR_CASES[5:]:
+    assert any(_t[k:k + 1] == b"\r" and _t[k + 1:k + 2] not in (b"\n", b"") for k in range(len(_t))), _t
+assert FASTA_LONE_CR_CASES[1][5:7] == b"\r>" and FASTA_LONE_CR_CASES[6][5:8] == b"\n\r>"
+
+
+def _fasta_border_cases():
+    """line ends and header starts at the borders of K15's 4 096-byte blocks and of a thread's 16 bytes; every case asserts
+    where its bytes fall"""
+    out = []
+    for B in (4096, 16):
+        t = b">a\n" + b"A" * (B - 4) + b"\n>b\nGG\n"            # the '\n' of a sequence line ends a block, '>' opens the next
+        assert t[B - 1:B + 1] == b"\n>"
+        out.append(t)
+        t = b">a\r\n" + b"A" * (B - 5) + b"\r\n>b\r\nGG\r\n"      # a \r\n pair split across the border
+        assert t[B - 1:B + 1] == b"\r\n" and t[B + 1:B + 2] == b">"
+        out.append(t)
+        t = b">a\nAC\n>" + b"h" * (B - 8) + b"\n>b\nGG\n"        # a header line ends a block, the next header opens the next:
+        assert t[B - 1:B + 1] == b"\n>" and t.count(b">") == 3     # the empty contig in between starts at pool offset 2, not 0
+        out.append(t)
+    t = b">a\nAC\n>" + b"h" * 4999 + b"\nACGT\nTT\n"              # a header line of 5 000 bytes spans a block
+    assert t.index(b"\n", 7) - 6 == 5000 and t.index(b"\n", 7) > 4096 > 6
+    out.append(t)
+    t = b">a\nAC\n>b\n"                                           # a header's '\n' is the file's last byte
+    assert t.endswith(b">b\n")
+    out.append(t)
+    t = b">a\nAC\n>" + b"h" * (4095 - 7) + b"\nGG\n"              # a header's '\n' is a block's last byte
+    assert t[4095:4096] == b"\n" and t[6:7] == b">" and b"\n" not in t[7:4095]
+    out.append(t)
+    t = b">a\nAC\n>" + b"h" * (4095 - 7) + b"\n"                  # ... and the file's
+    assert len(t) == 4096 and t[4095:] == b"\n"
+    out.append(t)
+    return out
+
+
+FASTA_CASES += FASTA_LONE_CR_CASES + _fasta_border_cases()
 
 
 def check_fasta_pool(eng, text):
@@ -2581,14 +2661,173 @@ def bgzf_deflate_inputs():
     maf = (b"##maf version=1\n" + b"".join(b"a score=0\ns chr%d %d 700 + 100000 " % (k, 13 * k) + dna[700 * k:700 * k + 700] +
                                           b"\ns qry%d 5 700 - 9000 " % k + dna[700 * k + 350:700 * k + 1050] + b"\n\n" for k in range(120)))
     skew = bytes(rng.choice(256, 70000, p=np.r_[0.97, np.full(255, 0.03 / 255)]).astype(np.uint8))   # one symbol nearly alone: 1-bit code
-    fib = [1, 1]
-    while sum(fib) + fib[-1] + fib[-2] <= 32768:
-        fib.append(fib[-1] + fib[-2])
-    deep = b"".join(bytes([65 + i]) * c for i, c in enumerate(fib))            # Fibonacci counts: a tree deeper than 15 before the halving
     return [("maf", maf), ("dna", dna), ("empty", b""), ("one byte", b"x"), ("two symbols", b"ab" * 5000),
             ("one symbol", b"N" * 40000), ("a member exactly", dna[:32768]), ("two members exactly", dna[:65536]),
             ("one over", dna[:32769]), ("random bytes (stored)", bytes(rng.integers(0, 256, 50000, dtype=np.uint8))),
-            ("all 256 symbols, skewed", skew), ("deep tree", deep + dna[:1000]), ("127 bytes", dna[:127]), ("129 bytes", dna[:129])]
+            ("all 256 symbols, skewed", skew), ("127 bytes", dna[:127]), ("129 bytes", dna[:129])] + \
+           [(name, data) for name, data, _ in bgzf_code_inputs()]
+
+
+# ---- K18's code, not only its stream: the lengths a member's header spells against Huffman's and package-merge's ----
+def huffman_lengths(weights, deepest=False):
+    """optimal code lengths of the (non-zero) weights by the textbook heap construction.  Among equal weights the shallowest
+    subtree goes first, which gives the optimal code of the least depth; `deepest` takes the deepest one first instead.  Both
+    are optimal: the total cost sum(w * len) of an optimal code is unique, its depth is not."""
+    import heapq
+    if len(weights) == 1:
+        return [1]
+    heap = [(w, 0, k, (k,)) for k, w in enumerate(weights)]     # weight, (signed) height, serial number, the leaves below
+    heapq.heapify(heap)
+    lens, serial = [0] * len(weights), len(weights)
+    while len(heap) > 1:
+        a, b = heapq.heappop(heap), heapq.heappop(heap)
+        for k in a[3] + b[3]:
+            lens[k] += 1
+        height = min(a[1], b[1]) - 1 if deepest else max(a[1], b[1]) + 1
+        heapq.heappush(heap, (a[0] + b[0], height, serial, a[3] + b[3]))
+        serial += 1
+    return lens
+
+
+def package_merge_lengths(weights, limit=15):
+    """optimal code lengths of the weights when no length may pass `limit` (Larmore and Hirschberg's package-merge): `limit`
+    rows of the leaves, every row's cheapest items paired into packages that join the next row; a leaf's length is the number
+    of times it occurs among the 2 n - 2 cheapest items of the last row"""
+    n = len(weights)
+    assert 2 <= n <= 1 << limit
+    leaves = sorted((w, (k,)) for k, w in enumerate(weights))
+    row = leaves
+    for _ in range(limit - 1):
+        packages = [(row[i][0] + row[i + 1][0], row[i][1] + row[i + 1][1]) for i in range(0, len(row) - 1, 2)]
+        row = sorted(leaves + packages, key=lambda it: it[0])
+    lens = [0] * n
+    for _, members in row[:2 * n - 2]:
+        for k in members:
+            lens[k] += 1
+    assert sum(2.0 ** -l for l in lens) == 1.0 and max(lens) <= limit
+    return lens
+
+
+def bgzf_members(img):
+    """(deflate payload, ISIZE) of every member of a BGZF stream"""
+    import struct
+    p = 0
+    while p < len(img):
+        bsize = struct.unpack_from("<H", img, p + 16)[0] + 1
+        yield img[p + 18:p + bsize - 8], struct.unpack_from("<I", img, p + bsize - 4)[0]
+        p += bsize
+
+
+def bgzf_header_lengths(payload):
+    """the 257 literal/length code lengths a member of K18 spells in its dynamic-block header (k_bgzf_emit: BFINAL, BTYPE 10,
+    HLIT 0, HDIST 0, HCLEN 15, nineteen 3-bit fields, then from bit 74 one 4-bit field per symbol, most significant bit first:
+    the code-length code is the flat 4-bit one); None for a stored block"""
+    def bit(i):
+        return (payload[i >> 3] >> (i & 7)) & 1
+    if payload[0] & 7 == 1:                                        # BFINAL, BTYPE 00
+        return None
+    assert payload[0] & 7 == 5 and len(payload) * 8 >= 1106        # BFINAL, BTYPE 10
+    assert sum(bit(3 + k) << k for k in range(14)) == 15 << 10     # HLIT 0, HDIST 0, HCLEN 15: 257 lengths, 19 code-length codes
+    assert [sum(bit(17 + 3 * k + j) << j for j in range(3)) for k in range(19)] == [0, 0, 0] + [4] * 16
+    return [sum(bit(74 + 4 * s + j) << (3 - j) for j in range(4)) for s in range(257)]
+
+
+BGZF_DYN_HDR_BITS = 1106                                              # 3 + 5 + 5 + 4 + 19 * 3 + 257 * 4 + 4
+
+
+def _bytes_of_counts(counts, symbols):
+    return b"".join(bytes([s]) * c for s, c in zip(symbols, counts))
+
+
+def bgzf_code_inputs():
+    """(name, one member's bytes, what makes the input decisive) for check_bgzf_deflate_codes, which asserts the claim:
+    ("depth", d): the optimal code of the least depth is d levels deep — beyond 15 the device has to halve the weights and
+    build again (k_bgzf_plan's too_deep loop); ("tie", lo, hi): lo levels when a leaf wins a tie, hi when a node does;
+    ("same size",): the block under its optimal code is exactly as long as the stored block, which then is the one to write"""
+    fib = [1, 1]                                                      # the first 1 is the end-of-block symbol's
+    while sum(fib) + fib[-1] + fib[-2] <= 32768 + 1:
+        fib.append(fib[-1] + fib[-2])
+    geo = [16384 >> i for i in range(15)]
+    # a leaf and an internal node of one weight meet again and again: the leaf first keeps the tree at 15 levels, the node
+    # first makes 16 (found by a search over such sequences; the claim is asserted like the others)
+    tie = [1, 1, 2, 3, 3, 3, 6, 12, 24, 36, 60, 96, 156, 252, 252, 504, 756, 756, 1512, 2268, 4435]
+    n = len(fib) - 1
+    down = [255 - (255 * i) // (n - 1) for i in range(n)]             # the rarest symbol is byte 255, the commonest byte 0
+    assert down[0] == 255 and down[-1] == 0 and len(set(down)) == n
+    return [("deep tree", _bytes_of_counts(fib[1:], range(33, 33 + n)), ("depth", 20)),                   # 28 655 bytes
+            ("deep tree, ranks against symbol order", _bytes_of_counts(fib[1:], down), ("depth", 20)),
+            ("geometric counts, depth 15 exactly", _bytes_of_counts(geo, range(100, 115)), ("depth", 15)),
+            ("depth 16", _bytes_of_counts(fib[1:17], range(33, 49)), ("depth", 16)),
+            ("a leaf wins a tie or the tree is too deep", _bytes_of_counts(tie, range(200, 200 + len(tie))), ("tie", 15, 16)),
+            ("stored and dynamic of one size", (bytes(range(128)) * 9)[:1082], ("same size",))]
+
+
+def check_bgzf_deflate_codes(eng):
+    """every member of every input of bgzf_deflate_inputs(): the code lengths read back out of the member's own header are a
+    complete prefix code (Kraft sum exactly 1) of at most 15 bits over exactly the symbols that occur, and the code is as
+    good as it can be — the payload has the size an OPTIMAL code gives, to the byte, where Huffman's code fits 15 levels (its
+    cost is unique; stored exactly when that is not larger), and is within 1 % of package-merge's optimum where it does
+    not.  1 %: measured, the device's halving costs 0.01 - 0.07 % (profiles/emu_mutants_readers.txt); a flat code
+    costs tens of per cent.  Returns [(name, device bits, package-merge bits)] of the deep members."""
+    from fractions import Fraction
+    claims = {name: claim for name, _, claim in bgzf_code_inputs()}
+    deep = []
+    for name, data in bgzf_deflate_inputs():
+        d_in = eng.upload(np.frombuffer(data + b"\xBB" * 8, dtype=np.uint8))
+        out, used = eng.bgzf_compress(d_in, len(data), eof_marker=False)
+        img = out.numpy()[:used].tobytes()
+        at, depths, same_size = 0, [], []
+        for payload, isize in bgzf_members(img):
+            part = data[at:at + isize]
+            at += isize
+            n = len(part)
+            hist = np.bincount(np.frombuffer(part, dtype=np.uint8), minlength=256).tolist() + [1]   # [256]: end of block
+            used_syms = [s for s in range(257) if hist[s]]
+            weights = [hist[s] for s in used_syms]
+            opt = huffman_lengths(weights)
+            opt_cost = sum(w * l for w, l in zip(weights, opt))
+            assert opt_cost == sum(w * l for w, l in zip(weights, huffman_lengths(weights, deepest=True))), name
+            depths.append(max(opt))
+            lens = bgzf_header_lengths(payload)
+            dev_bits = None
+            if lens is not None:
+                assert sum(Fraction(1, 1 << l) for l in lens if l) == 1, (name, lens)
+                assert max(lens) <= 15, (name, max(lens))
+                assert [s for s in range(257) if lens[s]] == used_syms, name
+                dev_bits = BGZF_DYN_HDR_BITS + sum(hist[s] * lens[s] for s in used_syms)
+                assert len(payload) == (dev_bits + 7) // 8, (name, len(payload), dev_bits)
+            if max(opt) <= 15:
+                dyn, sto = (BGZF_DYN_HDR_BITS + opt_cost + 7) // 8, 5 + n
+                print("K18 %-45s member of %5d bytes: depth %2d, payload %5d, optimum %5d, stored %5d" % (
+                    name, n, max(opt), len(payload), dyn, sto))
+                assert len(payload) == min(dyn, sto), (name, len(payload), dyn, sto)
+                assert (lens is None) == (sto <= dyn), (name, dyn, sto)
+                same_size.append(dyn == sto)
+            else:
+                limited = package_merge_lengths(weights)
+                opt_bits = BGZF_DYN_HDR_BITS + sum(w * l for w, l in zip(weights, limited))
+                print("K18 %-45s member of %5d bytes: depth %2d, device %6d bits, longest code %2d, package-merge %6d bits, "
+                      "excess %d bits = %.4f %%, Huffman without the limit %6d" % (
+                          name, n, max(opt), dev_bits or 0, max(lens or [0]), opt_bits, (dev_bits or 0) - opt_bits,
+                          100.0 * ((dev_bits or 0) - opt_bits) / opt_bits, BGZF_DYN_HDR_BITS + opt_cost))
+                assert lens is not None, name                        # no deep input here is anywhere near incompressible
+                assert opt_bits <= dev_bits, (name, opt_bits, dev_bits)
+                assert 100 * dev_bits <= 101 * opt_bits, (name, opt_bits, dev_bits)
+                deep.append((name, dev_bits, opt_bits))
+        assert at == len(data), name
+        claim = claims.get(name)
+        if claim:                                                    # the input is what its name says
+            assert len(data) <= 32768 and len(depths) == 1, name
+            hist = np.bincount(np.frombuffer(data, dtype=np.uint8), minlength=256).tolist() + [1]
+            weights = [c for c in hist if c]
+            if claim[0] == "depth":
+                assert depths[0] == claim[1], (name, depths, claim)
+            elif claim[0] == "same size":
+                assert same_size == [True], name
+            else:
+                assert (depths[0], max(huffman_lengths(weights, deepest=True))) == claim[1:], (name, depths, claim)
+    assert sorted(n for n, _, _ in deep) == sorted(n for n, _, c in bgzf_code_inputs() if c[0] == "depth" and c[1] > 15)
+    return deep
 
 
 def check_bgzf_deflate(eng, inflate_too=True):
@@ -2874,3 +3113,55 @@ def check_pafcov_look_back_wide(eng):
                 assert (got[:30] == [0] * 20 + [1] * 10).all() and not got[1600:30000].any()
     finally:
         eng.set_param("cov_spin_limit", keep)
+
+
+# ------------------------------------------------------------------------------------------------
+# K3 / K4: the sixteen-bit fields of the MAF walks at their limits
+# ------------------------------------------------------------------------------------------------
+MAF_SHORT_MAX = 61440                # WGA_MAF_SHORT_MAX: the longest block the stream kernel takes
+MAF_FOLD_COLS = 28 * 2048            # WGA_MAF_FOLD_STEPS steps: a piece folds its packed totals (the emulator build: every 3 steps)
+
+
+def _one_class_pairs(cols):
+    """five pairs of `cols` columns whose totals sit in ONE sixteen-bit field each: all X, all I, all D; I and D taking turns
+    (every column starts a run: the run-start fields of I and D hold cols / 2 each); = and X taking turns"""
+    half = cols // 2
+    pairs = [(b"A" * cols, b"C" * cols), (b"-" * cols, b"A" * cols), (b"A" * cols, b"-" * cols),
+             ((b"-A" * (half + 1))[:cols], (b"A-" * (half + 1))[:cols]), (b"A" * cols, (b"AC" * (half + 1))[:cols])]
+    for (t, q), cls, count in zip(pairs, "XIDIX", (cols, cols, cols, cols - half, half)):
+        assert len(t) == len(q) == cols
+        counts, txt = orc.parse_maf_seq_to_cigar(t, q, 0)
+        assert txt.count(cls) == (1 if count == cols else count) and (txt == "%d%s" % (cols, cls)) == (count == cols), txt[:40]
+    return pairs, [0, 1, 0, 1, 1]
+
+
+def check_maf_wide_fields(eng, lengths=(61440, 61441, 65535, 65536), piece=True):
+    """blocks whose per-class totals reach the ends of the sixteen-bit fields the walks pack them in.  With `maf_long_cols`
+    out of the way a block of 61 440 columns of one class is the longest the stream kernel ever takes (its fields hold
+    61 440), and 61 441, 65 535 and 65 536 go to the piece walk by WGA_MAF_SHORT_MAX alone — a stream kernel that took them
+    would wrap a field at 65 536; at the default they are all walked in pieces.  Then ONE piece of 131 072 columns of one class
+    (64 steps): its packed totals pass 65 535 unless they are folded into the 64-bit sums on the way, which the product does
+    every 28 steps (57 344 columns) — a piece that long is otherwise only made beyond 1.9e9 long columns per call.  Counters
+    and run lists of both walks against the oracle (check_maf_pair, check_maf_call_runs)."""
+    assert all(MAF_SHORT_MAX <= c <= 65536 for c in lengths)        # the stream kernel's longest block ... one past a field's end
+    try:
+        for cols in lengths:
+            pairs, strands = _one_class_pairs(cols)
+            for long_cols in (1 << 62, 32768):
+                assert cols < long_cols or cols > 32768            # the stream kernel's own limit decides / every block is long
+                eng.set_param("maf_long_cols", long_cols)
+                check_maf_pair(eng, pairs, strands)
+                check_maf_call_runs(eng, pairs)
+        if piece:
+            piece_cols, cols = 131072, 200000
+            assert piece_cols > 65535 and piece_cols > MAF_FOLD_COLS and piece_cols >= 2 * MAF_FOLD_COLS and cols > piece_cols
+            t, q = b"G" * cols, b"T" * cols
+            counts, txt = orc.parse_maf_seq_to_cigar(t, q, 1)
+            assert txt == "%dX" % cols and min(cols, piece_cols) > 65535     # columns of one class in ONE piece: the field wraps
+            eng.set_param("maf_long_cols", 32768)
+            eng.set_param("maf_piece_cols", piece_cols)
+            check_maf_pair(eng, [(t, q), (t[:70000], t[:70000])], [1, 0])
+            check_maf_call_runs(eng, [(t, q)])
+    finally:
+        eng.set_param("maf_long_cols", 32768)
+        eng.set_param("maf_piece_cols", 16384)

@@ -672,6 +672,8 @@ def test_paf_split(emu):
     # delimiters right at the 16-byte / 4096-byte block edges
     for pad in (4080, 4095, 4096, 4097, 8191):
         pc.check_paf_split(emu, b"#" + b"x" * (pad - 1) + b"\n" + rows[0].encode() + b"\n" + b"\t" * 40 + b"\n")
+    for text in pc.paf_short_tag_texts():                 # tags and spans at their shortest
+        pc.check_paf_split(emu, text)
 
 
 def test_maf_split(emu):
@@ -693,6 +695,8 @@ def test_maf_split(emu):
     pc.check_maf_split(emu, (b"##maf\n" + b"\n".join(odd)).replace(b"\n", b"\r\n"))
     for pad in (4079, 4095, 4096, 4097):                     # delimiters at the block edges
         pc.check_maf_split(emu, b"#" + b"x" * (pad - 1) + b"\n" + block(3, 50) + b" " * 40 + b"\n")
+    for text in pc.maf_one_byte_token_texts():            # one-byte names and rows at a 16-byte group's ends
+        pc.check_maf_split(emu, text)
 
 
 
@@ -745,6 +749,12 @@ def test_maf_long_blocks_piecewise(emu):
     finally:
         emu.set_param("maf_long_cols", 32768)
         emu.set_param("maf_piece_cols", 16384)
+
+
+def test_maf_wide_fields(emu):
+    """the walks' sixteen-bit fields at their limits (pc.check_maf_wide_fields); this build folds a piece's totals every 3 steps,
+    so the piece of 131 072 columns is what a fold that comes too late, or not at all, fails on"""
+    pc.check_maf_wide_fields(emu, lengths=(61440, 65536))
 
 
 def test_reduce_scatter_i32(monkeypatch):
@@ -812,6 +822,7 @@ def test_bgzf_crc32(emu):
 
 def test_bgzf_deflate(emu):
     pc.check_bgzf_deflate(emu)
+    pc.check_bgzf_deflate_codes(emu)
 
 
 def test_bgzf_deflate_random_inputs(emu):

@@ -614,12 +614,17 @@ def test_paf_split(gpu):
     # delimiters right at the 16-byte / 4096-byte block edges
     for pad in (4080, 4095, 4096, 4097, 8191):
         pc.check_paf_split(gpu, b"#" + b"x" * (pad - 1) + b"\n" + rows[0].encode() + b"\n" + b"\t" * 40 + b"\n")
+    for text in pc.paf_short_tag_texts():                 # tags and spans at their shortest
+        pc.check_paf_split(gpu, text)
 
 
 
 def test_maf_pair_long_rows_fold_lane_counters(gpu):
-    """rows beyond 4095 steps of 1024 columns: the 16-bit lane counters are folded into the wave totals on the way
-    (the emulator build of the CPU suite folds every 3 steps instead); counts against the oracle"""
+    """rows of millions of columns: beyond WGA_MAF_SHORT_MAX (61 440 columns) every block is walked in pieces whatever
+    `maf_long_cols` says, one wave per piece, and a piece folds its packed sixteen-bit totals into 64-bit sums every 28 steps
+    of 2 048 columns (the emulator build of the CPU suite: every 3).  Pieces of the default 16 384 columns are 8 steps and end
+    before a fold; pieces of 131 072 columns are 64 steps, fold at steps 28 and 56, and would wrap a field without;
+    counts against the oracle"""
     rng = np.random.default_rng(21)
     L = 4095 * 1024 * 2 + 1500
     t = pc.rand_seq(rng, L, b"ACGTacgt--N")
@@ -634,9 +639,12 @@ def test_maf_pair_long_rows_fold_lane_counters(gpu):
     rows = gpu.upload(np.frombuffer(bytes(buf), dtype=np.uint8))
     n = len(pairs)
     exp = [orc.parse_maf_seq_to_cigar(a, b, strands[i]) for i, (a, b) in enumerate(pairs)]
-    # once as ONE wave per row (the fold of the lane counters), once piece by piece (the default beyond 32 768 columns)
-    for long_cols in (1 << 62, 32768):
+    ta, qa = (np.frombuffer(r[:131072], dtype=np.uint8) for r in (t, q))
+    assert int(((ta != qa) & (ta != 45) & (qa != 45)).sum()) > 65535    # the X field of one piece of 131 072 columns wraps unfolded
+    # piece by piece both times: the default pieces, and pieces long enough for the fold of the packed totals
+    for long_cols, piece_cols in ((32768, 16384), (32768, 131072)):
         gpu.set_param("maf_long_cols", long_cols)
+        gpu.set_param("maf_piece_cols", piece_cols)
         try:
             counts, run_cnt = gpu.maf_pair_stat(n, rows, gpu.upload(np.array(t_off, dtype=np.uint64)),
                                                 gpu.upload(np.array(q_off, dtype=np.uint64)),
@@ -644,11 +652,23 @@ def test_maf_pair_long_rows_fold_lane_counters(gpu):
                                                 gpu.upload(np.array(strands, dtype=np.uint8)))
         finally:
             gpu.set_param("maf_long_cols", 32768)
+            gpu.set_param("maf_piece_cols", 16384)
         c, rc = counts.numpy(), run_cnt.numpy()
         for i in range(n):
             exp_counts, exp_txt = exp[i]
-            assert tuple(int(x) for x in c[i]) == exp_counts, (long_cols, i, exp_counts, c[i])
+            assert tuple(int(x) for x in c[i]) == exp_counts, (piece_cols, i, exp_counts, c[i])
             assert int(rc[i]) == sum(1 for ch in exp_txt if not ch.isdigit())
+
+
+@pytest.mark.parametrize("cols", [61440, 61441, 65535, 65536, "one piece of 131072"])
+def test_maf_wide_fields(gpu, cols):
+    """the walks' sixteen-bit fields at their limits (pc.check_maf_wide_fields): blocks of one class of 61 440 columns (the
+    longest the stream kernel takes) to 65 536 (one more than a field holds), and one piece of 131 072 columns, which reaches
+    the product's fold of the packed totals at steps 28 and 56"""
+    if isinstance(cols, int):
+        pc.check_maf_wide_fields(gpu, lengths=(cols,), piece=False)
+    else:
+        pc.check_maf_wide_fields(gpu, lengths=(), piece=True)
 
 
 def test_maf_long_blocks_piecewise(gpu):
@@ -755,6 +775,8 @@ def test_maf_split(gpu):
     pc.check_maf_split(gpu, (b"##maf\n" + b"\n".join(odd)).replace(b"\n", b"\r\n"))
     for pad in (4079, 4095, 4096, 4097):                     # delimiters at the block edges
         pc.check_maf_split(gpu, b"#" + b"x" * (pad - 1) + b"\n" + block(3, 50) + b" " * 40 + b"\n")
+    for text in pc.maf_one_byte_token_texts():            # one-byte names and rows at a 16-byte group's ends
+        pc.check_maf_split(gpu, text)
 
 
 
@@ -1382,6 +1404,7 @@ def test_bgzf_crc32(gpu):
 
 def test_bgzf_deflate(gpu):
     pc.check_bgzf_deflate(gpu)
+    pc.check_bgzf_deflate_codes(gpu)
 
 
 def test_bgzf_deflate_at_size_round_trip(gpu):
