@@ -960,6 +960,42 @@ int wga_maf2paf(wga_ctx*, uint32_t n, const uint8_t* d_names, uint64_t n_name_by
                 const wga_cigar_counts* d_counts, const uint64_t* d_runs, const uint64_t* d_run_off, const uint64_t* d_cols,
                 void* d_work, uint64_t* total_bytes, uint8_t* d_out);
 
+/* ---- K30: `paf2chain`, `maf2chain` — the chain heads (replaces the record loop of the host's paf2chain_range and maf2chain_text,
+ *      wgatools_amd/host/cmd_chain.inc: the trims, text sizes and diagnostics of every record downloaded, the head printed by one
+ *      CPU thread, the heads and two offset arrays uploaded and scattered around the data lines; in the reference ChainHeader's
+ *      Display chain.rs:185-203 behind the TryFrom arithmetic of chain.rs:103-183) ------------------------------------------------
+ * d_trim[n], d_nbytes[n] and d_diag[n] are the results of wga_cigar_chain's count call for n records, or arrays of the same
+ * meaning.  d_heads[n] reuses wga_maf2paf_head: q[0 .. 2] / t[0 .. 2] = size, start and end BEFORE trimming, the spans of the two
+ * names inside d_names[0 .. n_name_bytes), strand_neg = the query's strand.  n_good = the smallest r with
+ * d_diag[r].bad_op_idx != WGA_NONE, or n.  For every record r < n_good, in input order:
+ *   chain\t255\t<tname>\t<t[0]>\t+\t<ts>\t<te>\t<qname>\t<q[0]>\t<+|->\t<qs>\t<qe>\t<chain_id0 + r>
+ *   then  d_nbytes[r] bytes that this call does NOT write: wga_cigar_chain's text of the record, at d_data_off[r]
+ *   then  \n\n
+ * with, all mod 2^64 and in canonical decimal,
+ *   ts = t[1] + head_del, te = t[2] - tail_del
+ *   `+`: qs = q[1] + head_ins,          qe = q[2] - tail_ins
+ *   `-`: qs = q[0] - (q[2] - head_ins), qe = q[0] - (qs + tail_ins) with the qs just computed (chain.rs:136-137,177-178).
+ * A name is written as it is (`write!`, no quoting); a name whose span does not lie inside d_names is written as empty.
+ *   d_out == NULL: the byte count of every head and the place of every record (d_work), d_data_off[n] (device memory:
+ *                  d_data_off[r] = the place of record r's data lines behind its head; from n_good on the text's length);
+ *                  *total_bytes and *n_good (host values; the call synchronises).
+ *   otherwise    : the heads and the "\n\n" of records [0, n_good) with the places of the first call, and not one byte else:
+ *                  the d_nbytes[r] bytes at d_data_off[r] are wga_cigar_chain's (its fill call with d_data_off and n = n_good,
+ *                  on the same stream in either order).  d_out may have any alignment, the caller leaves 16 bytes of slack behind
+ *                  the text; no byte in front of d_out and none from d_out + *total_bytes + 16 on is touched (this
+ *                  implementation writes none outside the heads and record ends).  *total_bytes and *n_good are read as the
+ *                  first call left them, so the two calls take the same arguments.
+ * n == 0, or a fill with a total of 0: nothing is written.  WGA_E_INVALID_ARG: a null d_work, total_bytes or n_good, a null array
+ * with n > 0 (d_names only when n_name_bytes > 0).
+ * d_work: wga_chain_heads_work_bytes(n) bytes of device memory, 8-byte aligned, shared by the two calls
+ * = 8 * (2 n + 2 + n / 1024 + 4): 8 bytes per record for the plan (its head's byte count), 8 per record and one more for the
+ * scan (its place; the total last), one word for n_good (the min-reduction over d_diag), plus the scan's partial sums. */
+uint64_t wga_chain_heads_work_bytes(uint64_t n);
+int wga_chain_heads(wga_ctx*, uint32_t n, const uint8_t* d_names, uint64_t n_name_bytes, const wga_maf2paf_head* d_heads,
+                    const wga_chain_trim_t* d_trim, const uint64_t* d_nbytes, const wga_rec_diag* d_diag,
+                    uint64_t chain_id0, void* d_work, uint64_t* d_data_off, uint64_t* total_bytes, uint32_t* n_good,
+                    uint8_t* d_out);
+
 #ifdef __cplusplus
 }
 #endif

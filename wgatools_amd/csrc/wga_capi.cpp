@@ -52,6 +52,7 @@
 #include "wga_k27_chain2paf.h" /* K27: the PAF record writer of chain2paf */
 #include "wga_k28_maf2paf.h" /* K28: the PAF record writer of maf2paf */
 #include "wga_k29_paf_fix.h" /* K29: the end-fixing line writer of validate --fix */
+#include "wga_k30_chain_heads.h" /* K30: the chain heads of paf2chain and maf2chain */
 
 /* A grow-only device buffer of a context.  reserve() leaves it with room for `need` bytes: one that is too small is freed
  * behind the work of the context's stream and allocated anew with `grow` (>= need) bytes — every site has its own growth rule —,
@@ -595,6 +596,7 @@ int wga_ctx_get_param(wga_ctx* c, const char* name, int64_t* value) {
 #include "capi_chain_write.inc"
 #include "capi_chain2paf.inc"
 #include "capi_maf2paf.inc"
+#include "capi_chain_heads.inc"
 #include "capi_dotplot_csv.inc"
 #include "capi_pafcov.inc"
 #include "capi_pafpseudo.inc"

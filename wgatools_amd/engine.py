@@ -533,12 +533,13 @@ class Engine:
         self._check(self.lib.wga_chain_line_off_rebase(self.ctx, int(n), _p(line_off), _p(out)))
         return out
 
-    def _count_then_fill(self, name, what, args, n_outs, out_shift):
-        """both calls of the text writer `name`: args, then n_outs u64 results by reference (*total_bytes first), then d_out.
+    def _count_then_fill(self, name, what, args, n_outs, out_shift, types=None):
+        """both calls of the text writer `name`: args, then n_outs results by reference (*total_bytes first; u64, or the ctypes
+        `types`), then d_out.
         The fill goes into a buffer of 0xA5 and must leave the results (`what` names them) and the bytes around the text alone.
         Returns (text, the results)."""
         fn = getattr(self.lib, name)
-        outs = [C.c_uint64(0) for _ in range(n_outs)]
+        outs = [t(0) for t in (types or [C.c_uint64] * n_outs)]
         refs = [C.byref(o) for o in outs]
         self._check(fn(*args, *refs, None))
         first = tuple(int(o.value) for o in outs)
@@ -620,6 +621,59 @@ class Engine:
             work = self.empty(max(int(self.lib.wga_maf2paf_work_bytes(n, int(n_runs))), 16), np.uint8)
         args = (self.ctx, n, _p(names), int(n_name_bytes), _p(heads), _p(counts), _p(runs), _p(run_off), _p(cols), _p(work))
         return self._count_then_fill("wga_maf2paf", "total", args, 1, out_shift)[0]
+
+    def chain_heads_count(self, n, names, n_name_bytes, heads, trim, nbytes, diag, chain_id0, work, data_off):
+        """K30: the count call of wga_chain_heads alone, (total_bytes, n_good); it leaves its plan and the records' places in
+        `work` and the places of K10's data lines in `data_off`"""
+        total, good = C.c_uint64(0), C.c_uint32(0)
+        self._check(self.lib.wga_chain_heads(self.ctx, int(n), _p(names), int(n_name_bytes), _p(heads), _p(trim), _p(nbytes), _p(diag),
+                                             int(chain_id0), _p(work), _p(data_off), C.byref(total), C.byref(good), None))
+        return int(total.value), int(good.value)
+
+    def chain_heads(self, n, names, n_name_bytes, heads, trim, nbytes, diag, chain_id0=0, work=None, data_off=None, out_shift=0):
+        """K30 (chain.rs:103-203): the heads and the "\n\n" of n chain records around the places of K10's data lines, both calls
+        of wga_chain_heads on wga_cigar_chain's count results and the caller's heads (MAF2PAF_HEAD_DTYPE).  Returns (text, n_good,
+        data_off): the fill goes into a buffer of 0xA5, so the data lines' gaps hold that byte; the 64 bytes in front of and behind
+        the text are checked.
+        work, data_off: device buffers to use; out_shift: d_out starts that many bytes behind a 64-byte aligned address"""
+        n = int(n)
+        if work is None:
+            work = self.empty(max(int(self.lib.wga_chain_heads_work_bytes(n)), 16), np.uint8)
+        if data_off is None:
+            data_off = self.empty(max(n, 1), np.uint64)
+        args = (self.ctx, n, _p(names), int(n_name_bytes), _p(heads), _p(trim), _p(nbytes), _p(diag), int(chain_id0), _p(work),
+                _p(data_off))
+        text, (_, good) = self._count_then_fill("wga_chain_heads", "counts", args, 2, out_shift, types=(C.c_uint64, C.c_uint32))
+        return text, good, data_off
+
+    def chain_records(self, batch, names, heads, chain_id0=0, out_shift=0):
+        """paf2chain's / maf2chain's records of a batch: K10 count -> K30 count -> K10 fill at K30's places, over the n_good records in
+        front of the first bad one -> K30 fill.  names: the bytes the heads' spans point into, heads: MAF2PAF_HEAD_DTYPE (host
+        arrays or device arrays).  Returns (text, n_good); the 64 bytes in front of and behind the text are checked."""
+        n = batch.n
+        if not isinstance(names, DeviceArray):
+            names = self.upload(np.frombuffer(bytes(names), dtype=np.uint8)) if len(names) else None
+        n_name_bytes = names.size if names is not None else 0
+        if not isinstance(heads, DeviceArray):
+            heads = self.upload(np.ascontiguousarray(heads, dtype=MAF2PAF_HEAD_DTYPE)) if n else None
+        trim, nbytes, diag = self.cigar_chain(batch)
+        work = self.empty(max(int(self.lib.wga_chain_heads_work_bytes(n)), 16), np.uint8)
+        data_off = self.empty(max(n, 1), np.uint64)
+        hargs = (n, names, n_name_bytes, heads, trim, nbytes, diag, chain_id0, work, data_off)
+        total, good = self.chain_heads_count(*hargs)
+        guard = 64
+        out = self.upload(np.full(total + 2 * guard + 96, 0xA5, dtype=np.uint8))
+        lead = guard + (-out.ptr) % 64 + int(out_shift)
+        if good:
+            self.cigar_chain(Batch(batch.ops, batch.op_off, batch.strand_neg, good, batch.n_ops), out=out.ptr + lead, out_off=data_off)
+        tb, gd = C.c_uint64(total), C.c_uint32(good)
+        self._check(self.lib.wga_chain_heads(self.ctx, n, _p(names), n_name_bytes, _p(heads), _p(trim), _p(nbytes), _p(diag),
+                                             int(chain_id0), _p(work), _p(data_off), C.byref(tb), C.byref(gd), out.ptr + lead))
+        self.sync()
+        got = out.numpy()
+        if not ((got[:lead] == 0xA5).all() and (got[lead + total:] == 0xA5).all()):
+            raise _lib.WgaError("chain_records wrote outside d_out[0 .. total_bytes)")
+        return got[lead:lead + total].tobytes(), good
 
     def dotplot_csv_count(self, n, segs, seg_off, tails, tail_off, work):
         """K26: the count call of wga_dotplot_csv alone, total_bytes; it leaves the scan of the row sizes in `work`"""

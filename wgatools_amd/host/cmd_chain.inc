@@ -1,8 +1,45 @@
 /* cmd_chain.inc — part of wgatools_main.cpp (included there, inside its namespace: the commands share the device helpers, readers and
  * writers defined in front of the include). */
 /* ---- paf2chain (converter.rs:148-173; SURVEY.md 8f rank 2) ------------------------------------------------
- * GPU: tokeniser, data lines and head / tail trims (wga_cigar_chain).  Host: chain headers
- * (chain.rs:142-203, incl. the '-' strand arithmetic that reuses the updated start) and the layout. */
+ * GPU: tokeniser, data lines and head / tail trims (wga_cigar_chain, K10), the chain headers (chain.rs:142-203, incl. the '-'
+ * strand arithmetic that reuses the updated start), the "\n\n" behind a record and the layout (wga_chain_heads, K30).  Host: one
+ * wga_maf2paf_head per record (the numbers of the PAF line, the spans of the two names) and the names gathered for the upload;
+ * the length of the text, the number of records in front of the first bad one and that record's diagnostics come back.
+ * WGA_CHAIN_HEAD_WRITER=host: the headers are printed by one host thread from the downloaded trims and scattered around the data
+ * lines, as before K30 (measurements, and the cross-check of the device writer: same bytes); maf2chain below reads it too. */
+static bool chain_head_host_writer() {
+  const char* w = getenv("WGA_CHAIN_HEAD_WRITER");
+  return w && strcmp(w, "host") == 0;
+}
+/* a name's span in the buffer a batch's names are gathered in */
+static void chain_name_span(std::string& names, const std::string& name, uint64_t& off, uint32_t& len) {
+  off = names.size();
+  len = (uint32_t)name.size();
+  names += name;
+}
+/* the chain text of a batch whose K10 count call has run (d_trim, d_nb, d_diag on device d): K30's count call lays the records
+ * out, K10's fill call writes the data lines of the records in front of the first bad one, K30's fill call the heads and record
+ * ends around them.  Returns the text (on the device) and sets *bytes and *n_good. */
+static const uint8_t* chain_text_device(Dev& d, const wga_cigar_batch& cb, const uint8_t* d_names, uint64_t n_name_bytes,
+                                        const std::vector<wga_maf2paf_head>& heads, const wga_chain_trim_t* d_trim,
+                                        const uint64_t* d_nb, const wga_rec_diag* d_diag, uint64_t chain_id0, uint64_t* bytes,
+                                        uint32_t* n_good) {
+  const uint32_t n = cb.n;
+  auto* d_heads = d.upload(heads);
+  void* d_work = d.alloc((size_t)wga_chain_heads_work_bytes(n));
+  auto* d_data_off = (uint64_t*)d.alloc((size_t)n * 8);
+  d.check(wga_chain_heads(d.ctx, n, d_names, n_name_bytes, d_heads, d_trim, d_nb, d_diag, chain_id0, d_work, d_data_off, bytes,
+                          n_good, nullptr));
+  auto* d_out = (uint8_t*)d.alloc((size_t)*bytes + 64);
+  if (*n_good) {
+    wga_cigar_batch cb2 = cb;
+    cb2.n = *n_good;
+    d.check(wga_cigar_chain(d.ctx, &cb2, nullptr, nullptr, nullptr, d_out, d_data_off));
+    d.check(wga_chain_heads(d.ctx, n, d_names, n_name_bytes, d_heads, d_trim, d_nb, d_diag, chain_id0, d_work, d_data_off, bytes,
+                            n_good, d_out));
+  }
+  return d_out;
+}
 /* the chains of records [lo, hi) of a piece on device d, in resident batches; a batch's text goes to `sink` while it is still on
  * the device.  Returns the reference's message for the first failing record ("" if none): the records in front of it are written. */
 static std::string paf2chain_range(Dev& d, const PafInput& pin, size_t lo, size_t hi, uint64_t chain_base,
@@ -10,6 +47,7 @@ static std::string paf2chain_range(Dev& d, const PafInput& pin, size_t lo, size_
                                    const std::function<void(Dev&, const uint8_t*, size_t)>& sink) {
   const std::vector<PafRecord>& recs = pin.recs;
   const uint64_t kMaxText = 160ull << 20;
+  const bool host_writer = chain_head_host_writer();
   std::string pending_error;
   const size_t keep = d.owned.size(); /* this piece's text */
   size_t i0 = lo;
@@ -30,6 +68,34 @@ static std::string paf2chain_range(Dev& d, const PafInput& pin, size_t lo, size_
       auto* d_nb = (uint64_t*)d.alloc((size_t)n * 8);
       auto* d_diag = (wga_rec_diag*)d.alloc((size_t)n * sizeof(wga_rec_diag));
       d.check(wga_cigar_chain(d.ctx, &cb, d_trim, d_nb, d_diag, nullptr, nullptr));
+      if (!host_writer) {
+        std::vector<wga_maf2paf_head> heads(n);
+        std::string names;
+        for (uint32_t k = 0; k < n; k++) {
+          const PafRecord& r = recs[i0 + k];
+          wga_maf2paf_head& h = heads[k];
+          memset(&h, 0, sizeof h);
+          h.q[0] = r.query_length, h.q[1] = r.query_start, h.q[2] = r.query_end;
+          h.t[0] = r.target_length, h.t[1] = r.target_start, h.t[2] = r.target_end;
+          h.strand_neg = r.neg ? 1 : 0;
+          chain_name_span(names, r.query_name, h.qname_off, h.qname_len);
+          chain_name_span(names, r.target_name, h.tname_off, h.tname_len);
+        }
+        const uint8_t* d_names = d.upload((const uint8_t*)names.data(), names.size());
+        uint64_t bytes = 0;
+        uint32_t good = 0;
+        const uint8_t* d_out = chain_text_device(d, cb, d_names, names.size(), heads, d_trim, d_nb, d_diag,
+                                                 chain_base + (uint64_t)i0, &bytes, &good);
+        if (good < n) { /* parse_cigar_to_trim fails before anything of the record is written */
+          wga_rec_diag g;
+          d.download(&g, d_diag + good, 1);
+          pending_error = "CIGAR OP `" + cigar_op_token_at(cigars[good], g.bad_op_idx) + "` invalid";
+        }
+        if (good) sink(d, d_out, (size_t)bytes);
+        d.release_to(keep);
+        i0 = i;
+        continue;
+      }
       std::vector<wga_chain_trim_t> trim(n);
       std::vector<uint64_t> nb(n);
       std::vector<wga_rec_diag> diag(n);
@@ -103,6 +169,7 @@ int cmd_paf2chain(const std::string* input, Output& out) {
   std::string pending_error;
   PafInput pin;
   uint64_t chain_base = 0; /* chain id = index of the record in the whole input */
+  const char* const records_phase = chain_head_host_writer() ? "paf2chain records (host)" : "paf2chain records (device)";
   std::vector<std::unique_ptr<Dev>> devs; /* --gpus N: devices 1 .. N - 1 next to `d` */
   for (;;) {
     bool more = false;
@@ -114,8 +181,12 @@ int cmd_paf2chain(const std::string* input, Output& out) {
     if (!more) break;
     const size_t n = pin.recs.size();
     if (g_gpus == 1) {
-      pending_error = paf2chain_range(d, pin, 0, n, chain_base, nullptr,
-                                      [&](Dev& dg, const uint8_t* d_out, size_t bytes) { stream_out(dg, out, d_out, bytes); });
+      pending_error = paf2chain_range(d, pin, 0, n, chain_base, nullptr, [&](Dev& dg, const uint8_t* d_out, size_t bytes) {
+        dg.check(wga_sync(dg.ctx));
+        g_timer.mark(records_phase);
+        stream_out(dg, out, d_out, bytes);
+      });
+      g_timer.mark(records_phase); /* a piece without a record to write */
     } else { /* a piece's records in contiguous ranges over the devices; the chains meet in input order, up to the first error */
       d.init();
       if (devs.empty()) {
@@ -143,6 +214,7 @@ int cmd_paf2chain(const std::string* input, Output& out) {
         });
         dg.release_to(keep);
       });
+      g_timer.mark(records_phase);
       for (int g = 0; g < ng && pending_error.empty(); g++) {
         out.write(part[g]);
         pending_error = err[g];
@@ -640,7 +712,10 @@ int cmd_chain2paf(const std::string* input, Output& out) {
 
 /* ---- maf2chain (converter.rs:57-91) ---------------------------------------------------------------------
  * GPU: K3 column-pair runs -> packed ops (wga_maf_runs_ops) -> data lines and trims (wga_cigar_chain; '=' and X
- * runs add up into one block like cigar_cat's M).  Host: chain headers (chain.rs:103-140,185-203). */
+ * runs add up into one block like cigar_cat's M) -> chain headers (chain.rs:103-140,185-203), record ends and the layout
+ * (wga_chain_heads, K30).  Host: one wga_maf2paf_head per block, as maf2paf fills it; the names are read where the rows were
+ * uploaded (p.names_in_rows) or gathered.  Only the text's length comes back (K3's runs hold no op K10 rejects: every block is
+ * good).  WGA_CHAIN_HEAD_WRITER=host: the headers printed by one host thread from the downloaded trims, as before K30. */
 /* the chains of blocks recs[0 .. n), whose rows stand on device d (p); chain ids from chain_id0.  The text stays on the device:
  * *d_text, *bytes. */
 static void maf2chain_text(Dev& d, const MafRows& p, const MafRecord* const* recs, uint32_t n, uint64_t chain_id0,
@@ -675,6 +750,31 @@ static void maf2chain_text(Dev& d, const MafRows& p, const MafRecord* const* rec
   auto* d_nb = (uint64_t*)d.alloc((size_t)n * 8);
   auto* d_diag = (wga_rec_diag*)d.alloc((size_t)n * sizeof(wga_rec_diag));
   d.check(wga_cigar_chain(d.ctx, &cb, d_trim, d_nb, d_diag, nullptr, nullptr));
+  if (!chain_head_host_writer()) {
+    std::vector<wga_maf2paf_head> heads(n);
+    std::string names;
+    auto span = [&](const MafSLine& l, uint64_t& off, uint32_t& len) {
+      if (p.names_in_rows)
+        off = l.name_off, len = (uint32_t)l.name.size();
+      else
+        chain_name_span(names, l.name, off, len);
+    };
+    for (uint32_t k = 0; k < n; k++) {
+      const MafRecord& r = *recs[k];
+      wga_maf2paf_head& h = heads[k];
+      memset(&h, 0, sizeof h);
+      h.q[0] = r.q().size, h.q[1] = r.query_start(), h.q[2] = r.query_end();
+      h.t[0] = r.t().size, h.t[1] = r.t().start, h.t[2] = r.t().start + r.t().align_size;
+      h.strand_neg = r.q().neg ? 1 : 0;
+      span(r.q(), h.qname_off, h.qname_len);
+      span(r.t(), h.tname_off, h.tname_len);
+    }
+    const uint8_t* d_names = p.names_in_rows ? d_rows : d.upload((const uint8_t*)names.data(), names.size());
+    const uint64_t n_name_bytes = p.names_in_rows ? p.n_row_bytes : names.size();
+    uint32_t good = 0;
+    *d_text = chain_text_device(d, cb, d_names, n_name_bytes, heads, d_trim, d_nb, d_diag, chain_id0, bytes, &good);
+    return;
+  }
   std::vector<wga_chain_trim_t> trim(n);
   std::vector<uint64_t> nb(n);
   d.download(trim.data(), d_trim, n);
@@ -734,6 +834,7 @@ int cmd_maf2chain(const std::string* input, const std::string* query_name, Outpu
   MafChunks chunks(input);
   MafInput min;
   uint64_t chain_base = 0; /* chain id = index of the block in the whole input */
+  const char* const records_phase = chain_head_host_writer() ? "maf2chain records (host)" : "maf2chain records (device)";
   std::string pending_error;
   while (pending_error.empty() && chunks.next(d, min)) {
   std::vector<MafRecord>& recs = min.recs;
@@ -766,6 +867,8 @@ int cmd_maf2chain(const std::string* input, const std::string* query_name, Outpu
         const uint8_t* d_text = nullptr;
         uint64_t bytes = 0;
         maf2chain_text(dg, p, all.data() + lo, cnt, chain_base + lo, &d_text, &bytes);
+        dg.check(wga_sync(dg.ctx));
+        g_timer.mark(records_phase);
         stream_out(dg, out, d_text, (size_t)bytes);
       });
     } else { /* --gpus N: a piece's blocks in contiguous ranges over the devices, the chains meet in block order */
@@ -777,6 +880,7 @@ int cmd_maf2chain(const std::string* input, const std::string* query_name, Outpu
         part[g].resize((size_t)bytes);
         if (bytes) dg.download((uint8_t*)&part[g][0], d_text, bytes);
       });
+      g_timer.mark(records_phase);
       for (const std::string& t : part) out.write(t);
     }
   }
