@@ -996,6 +996,42 @@ int wga_chain_heads(wga_ctx*, uint32_t n, const uint8_t* d_names, uint64_t n_nam
                     uint64_t chain_id0, void* d_work, uint64_t* d_data_off, uint64_t* total_bytes, uint32_t* n_good,
                     uint8_t* d_out);
 
+/* ---- K31: `pafpseudo` — the row frame writer (replaces the row strings of the host's cmd_pafpseudo, wgatools_amd/host/
+ *      cmd_pafpseudo.inc: `text.append(gap, '-')`, one append per segment, `append(tail, '-')`, the target row as `append(size, 'N')`
+ *      or a slice of the pool, the `s` line heads and line ends; in the reference pseudomaf.rs:98-209) ---------------------------
+ * A file's text, or a run of whole lines of it, is described by n_items spans, and this call writes every byte of it that is not a
+ * segment: wga_pafpseudo_fill (K6) writes those, with d_dst_off pointing at their places in the same buffer.
+ * Item layout.  The items tile d_out[0, out_bytes) in order without gaps: item[0].dst == 0, item[k + 1].dst == item[k].dst +
+ *   item[k].len, and the last item ends at out_bytes.  Items without bytes are allowed, and runs of them.  d_out must be 16-byte
+ *   aligned (wga_malloc gives 256), else WGA_E_INVALID_ARG.  All offsets and lengths are 64-bit.
+ * Bad items.  *d_first_bad (device memory) receives WGA_NONE, or the index of the first item that breaks the tiling (its dst is
+ *   not the end of the item in front, it does not lie inside [0, out_bytes), it is the last and does not end at out_bytes), has a
+ *   kind above WGA_SPAN_HOLE, or names a copy range that does not lie inside its source.  A bad item writes nothing, and neither
+ *   do the items behind the first bad one (where they belong is not defined); the items in front of it are written.  No byte
+ *   outside d_out[0, out_bytes) is written, whatever the items say.
+ * Bytes written.  Every byte of a FILL or COPY item is written exactly once.  Every byte of a HOLE and every byte outside
+ *   [0, out_bytes) is left as it was — the ragged ends of 16-byte groups included: a group that a hole or the end of the text
+ *   shares with other items is written in narrower stores.  K6's fill and this call may therefore run in either order on the
+ *   stream, and each output byte is written once.
+ * Source reads stay inside d_pool[0, pool_bytes) and d_text[0, text_bytes): a source's ends are read without reaching over them
+ *   (the CLI's pool has 32 bytes of padding at both ends; this call does not ask for it).  Either source may be null when its
+ *   size is 0.
+ * n_items == 0 is valid with out_bytes == 0 only (nothing is written, *d_first_bad = WGA_NONE).  WGA_E_INVALID_ARG: a null
+ * d_first_bad, null d_items or d_out with n_items > 0, a null source of a size above 0, a misaligned d_out, n_items == 0 with
+ * out_bytes > 0, out_bytes of 2^47 or more.
+ * The work is dealt out in tiles of WGA_PSEUDO_FRAME_TILE output bytes, whatever the items' lengths. */
+#define WGA_SPAN_FILL      0u  /* len copies of the byte in the low 8 bits of src                 */
+#define WGA_SPAN_COPY_POOL 1u  /* d_pool[src .. src+len)                                          */
+#define WGA_SPAN_COPY_TEXT 2u  /* d_text[src .. src+len)  (heads, "a score=0\n", newlines)        */
+#define WGA_SPAN_HOLE      3u  /* bytes another kernel writes (K6's segments): left untouched     */
+typedef struct { uint64_t dst, len, src; uint32_t kind, pad; } wga_span_item;   /* 32 bytes */
+#define WGA_PSEUDO_FRAME_TILE 65536u /* output bytes per block */
+
+int wga_pafpseudo_frame(wga_ctx*, uint64_t n_items, const wga_span_item* d_items,
+                        const uint8_t* d_pool, uint64_t pool_bytes,
+                        const uint8_t* d_text, uint64_t text_bytes,
+                        uint8_t* d_out, uint64_t out_bytes, uint64_t* d_first_bad);
+
 #ifdef __cplusplus
 }
 #endif

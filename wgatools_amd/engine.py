@@ -45,6 +45,10 @@ CHAIN_FILTER_PARAMS_DTYPE = np.dtype([("min_block_size", "<u8"), ("min_query_siz
 MAF2PAF_HEAD_DTYPE = np.dtype([("q", np.uint64, 3), ("t", np.uint64, 3), ("qname_off", np.uint64), ("tname_off", np.uint64),
                                ("qname_len", np.uint32), ("tname_len", np.uint32), ("strand_neg", np.uint8),
                                ("pad", np.uint8, 7)])
+# K31 (include/wga_hip.h wga_span_item, WGA_SPAN_*, WGA_PSEUDO_FRAME_TILE)
+SPAN_ITEM_DTYPE = np.dtype([("dst", "<u8"), ("len", "<u8"), ("src", "<u8"), ("kind", "<u4"), ("pad", "<u4")])
+SPAN_FILL, SPAN_COPY_POOL, SPAN_COPY_TEXT, SPAN_HOLE = 0, 1, 2, 3
+PSEUDO_FRAME_TILE = 65536
 
 OP_CODES = {"M": 0, "I": 1, "D": 2, "N": 3, "S": 4, "H": 5, "P": 6, "=": 7, "X": 8}
 OP_I_CONT, OP_D_CONT, OP_OTHER = 9, 10, 11
@@ -674,6 +678,18 @@ class Engine:
         if not ((got[:lead] == 0xA5).all() and (got[lead + total:] == 0xA5).all()):
             raise _lib.WgaError("chain_records wrote outside d_out[0 .. total_bytes)")
         return got[lead:lead + total].tobytes(), good
+
+    def pafpseudo_frame(self, items, pool, pool_bytes, text, text_bytes, out, out_bytes, first_bad=None):
+        """K31 (the rows of pseudomaf.rs:98-209 around the segments): writes every FILL / COPY span of `items` (SPAN_ITEM_DTYPE, a
+        host array or a device array) into out[0, out_bytes) and leaves the holes alone; wga_pafpseudo_frame.  pool / text / out:
+        device arrays or pointers (out 16-byte aligned).  Returns the index of the first bad item, or None"""
+        if not isinstance(items, DeviceArray):
+            items = self.upload(np.ascontiguousarray(items, dtype=SPAN_ITEM_DTYPE))
+        first_bad = first_bad if first_bad is not None else self.empty(1, np.uint64)
+        self._check(self.lib.wga_pafpseudo_frame(self.ctx, items.size, _p(items), _p(pool), int(pool_bytes), _p(text), int(text_bytes),
+                                                 _p(out), int(out_bytes), _p(first_bad)))
+        bad = int(first_bad.numpy()[0])
+        return None if bad == 0xFFFFFFFFFFFFFFFF else bad
 
     def dotplot_csv_count(self, n, segs, seg_off, tails, tail_off, work):
         """K26: the count call of wga_dotplot_csv alone, total_bytes; it leaves the scan of the row sizes in `work`"""

@@ -2,8 +2,24 @@
  * writers defined in front of the include). */
 /* ---- pafpseudo (pseudomaf.rs:18-237) ----------------------------------------------------------------
  * Host: grouping by target / query, insertion sort by target_start, gap / overlap / contained
- * logic (:86-95,:147-175,:198-202).  GPU: every kept record's segment in target coordinates
- * (gen_pesudo_maf_by_cigar + the head trim), all targets in one batch. */
+ * logic (:86-95,:147-175,:198-202), and every check that needs no row byte, before anything is written.  GPU: the files' text,
+ * built in windows of whole lines of at most WGA_PSEUDO_OUT_BYTES bytes (256 MiB; a longer line is a window of its own): every
+ * kept record's segment in target coordinates (gen_pesudo_maf_by_cigar + the head trim, wga_pafpseudo_fill, K6) at its place in
+ * the window, and everything around the segments — line heads, the target row, the `-` runs, line ends — by the row frame writer
+ * (wga_pafpseudo_frame, K31); the window is streamed into the file and the next one takes its buffer.  An error a window's fill
+ * finds (an invalid base, a drain beyond the query) ends the run: the files written so far are complete, the one in progress ends
+ * at the last window written.
+ * WGA_PSEUDO_WRITER=host: all segments of all targets in one batch, downloaded, and every row put together as a string by one
+ * host thread, as before K31 (measurements, and the cross-check of the device writer: same bytes). */
+static bool pseudo_host_writer() {
+  const char* w = getenv("WGA_PSEUDO_WRITER");
+  return w && strcmp(w, "host") == 0;
+}
+static uint64_t pseudo_window_bytes() {
+  uint64_t b = (uint64_t)256 << 20;
+  if (const char* e = getenv("WGA_PSEUDO_OUT_BYTES")) b = strtoull(e, nullptr, 10);
+  return b ? b : 1;
+}
 struct PseudoSeg {
   size_t rec;        /* index into recs */
   uint64_t gap;      /* '-' columns written before the segment */
@@ -102,6 +118,8 @@ int cmd_pafpseudo(const std::string* input, const std::string& outdir, bool rewr
   std::vector<std::vector<wga_tok_err>> terrs(ngpu);
   std::string text16;
   if (pin.on_device && ngpu > 1) text16 = pin.text + std::string(16, '\0');
+  std::vector<const uint8_t*> d_texts(ngpu, nullptr); /* the PAF text on device g (a file the device splitter took) */
+  std::vector<size_t> keep_front(ngpu, 0);            /* device g's allocations in front of the up-front tokeniser's */
   on_devices(ngpu, [&](int g) {
     Dev& dg = *devs[g];
     cbs[g].n = 0;
@@ -113,6 +131,8 @@ int cmd_pafpseudo(const std::string* input, const std::string& outdir, bool rewr
     dg.init();
     const uint8_t* d_text = nullptr;
     if (pin.on_device) d_text = g == 0 ? pin.d_text : dg.upload((const uint8_t*)text16.data(), text16.size());
+    d_texts[g] = d_text;
+    keep_front[g] = dg.owned.size();
     (void)device_tokenise(dg, pin, 0, (uint32_t)mine[g].size(), cigars[g], &cbs[g], &terrs[g], ngpu > 1 ? mine[g].data() : nullptr,
                           d_text);
   });
@@ -131,6 +151,8 @@ int cmd_pafpseudo(const std::string* input, const std::string& outdir, bool rewr
     targets[it->second].recs.push_back(i);
   }
   std::vector<uint64_t> q_off(n_all, 0), q_len(n_all, 0), skip(n_all, UINT64_MAX); /* skip = all: a record the walk drops */
+  std::vector<uint64_t> walk_pos(n_all, 0); /* a kept record's place in the order the reference processes the records in */
+  uint64_t n_kept = 0;
   for (auto& t : targets) {
     std::unordered_map<std::string, size_t> qindex;
     for (size_t i : t.recs) {
@@ -175,6 +197,7 @@ int cmd_pafpseudo(const std::string* input, const std::string& outdir, bool rewr
         q_off[i] = qo;
         q_len[i] = ql;
         skip[i] = overlap;
+        walk_pos[i] = n_kept++;
         q.segs.push_back(PseudoSeg{i, gap, overlap});
         first_query = false;
       }
@@ -209,6 +232,159 @@ int cmd_pafpseudo(const std::string* input, const std::string& outdir, bool rewr
           if (skip[k] > len) fail("panic: String::drain range out of bounds (pseudomaf.rs:191)");
           seg_len[k] = len - skip[k];
         }
+  }
+  if (!pseudo_host_writer()) {
+    /* the target rows' slices (base mode), the last of the checks that need no row byte */
+    std::vector<uint64_t> t_off(targets.size(), 0), t_len(targets.size(), 0);
+    if (base)
+      for (size_t ti = 0; ti < targets.size(); ti++)
+        if (!targets[ti].queries.empty()) fa.fetch(targets[ti].name, 0, targets[ti].target_size_first - 1, &t_off[ti], &t_len[ti]);
+    /* the ops of the whole input have served (tokeniser errors, class sums): a window tokenises its own records again, in the
+     * order of its rows, into a batch of its own (DESIGN.md, K31) */
+    for (int g = 0; g < ngpu; g++)
+      if (devs[g]->ctx && !mine[g].empty()) devs[g]->release_to(keep_front[g]);
+    const uint64_t bound = pseudo_window_bytes();
+    struct RowsError {
+      uint64_t at = UINT64_MAX; /* walk_pos of the record */
+      std::string msg;
+    };
+    std::vector<RowsError> rows_err(ngpu);
+    on_devices(ngpu, [&](int g) {
+      Dev& dg = *devs[g];
+      for (size_t ti = 0; ti < targets.size(); ti++) {
+        const PseudoTarget& t = targets[ti];
+        if ((ngpu > 1 ? (int)(fnv1a64(t.name) % (uint64_t)ngpu) : 0) != g) continue;
+        dg.init();
+        /* the file's lines: "a score=0\n", the target row, the query rows, "\n"; a line = its head, its row, '\n' */
+        struct Line {
+          int kind; /* 0 score, 1 target row, 2 query row, 3 the closing newline */
+          size_t q;
+          std::string head;
+          uint64_t bytes;
+        };
+        std::vector<Line> lines;
+        lines.push_back(Line{0, 0, std::string(), 10});
+        auto s_head = [](const std::string& name, uint64_t size) {
+          std::string h = "s\t" + name + "\t0\t";
+          append_u64(h, size);
+          h += "\t+\t";
+          append_u64(h, size);
+          h.push_back('\t');
+          return h;
+        };
+        if (!t.queries.empty()) {
+          Line l{1, 0, s_head(t.name, t.target_size_first), 0};
+          l.bytes = l.head.size() + (base ? t_len[ti] : t.target_size_first) + 1;
+          lines.push_back(std::move(l));
+        }
+        for (size_t qi = 0; qi < t.queries.size(); qi++) {
+          const PseudoQuery& q = t.queries[qi];
+          Line l{2, qi, s_head(q.name, q.size), 0};
+          l.bytes = l.head.size() + q.tail + 1;
+          for (const auto& sg : q.segs) l.bytes += sg.gap + seg_len[sg.rec];
+          lines.push_back(std::move(l));
+        }
+        lines.push_back(Line{3, 0, std::string(), 1});
+        Output out;
+        out.open(outdir + "/" + t.name + ".maf", true);
+        for (size_t l0 = 0; l0 < lines.size();) {
+          size_t l1 = l0 + 1; /* lines [l0, l1): as many whole lines as the bound takes, one at least */
+          uint64_t out_bytes = lines[l0].bytes;
+          while (l1 < lines.size() && out_bytes + lines[l1].bytes <= bound) out_bytes += lines[l1++].bytes;
+          /* the window's items: everything but the segments, which are holes K6 fills */
+          std::string blob = "a score=0\n";
+          std::vector<wga_span_item> items;
+          std::vector<size_t> wrecs; /* the window's kept records, in the order of its rows */
+          std::vector<uint64_t> wdst;
+          uint64_t at = 0;
+          auto put = [&](uint64_t len, uint64_t src, uint32_t kind) {
+            if (len) items.push_back(wga_span_item{at, len, src, kind, 0});
+            at += len;
+          };
+          auto put_text = [&](const std::string& text) {
+            put(text.size(), blob.size(), WGA_SPAN_COPY_TEXT);
+            blob += text;
+          };
+          for (size_t l = l0; l < l1; l++) {
+            const Line& ln = lines[l];
+            if (ln.kind == 0) {
+              put(10, 0, WGA_SPAN_COPY_TEXT);
+              continue;
+            }
+            if (ln.kind == 1) {
+              put_text(ln.head);
+              if (base)
+                put(t_len[ti], t_off[ti], WGA_SPAN_COPY_POOL);
+              else
+                put(t.target_size_first, (uint64_t)'N', WGA_SPAN_FILL);
+            } else if (ln.kind == 2) {
+              const PseudoQuery& q = t.queries[ln.q];
+              put_text(ln.head);
+              for (const auto& sg : q.segs) {
+                put(sg.gap, (uint64_t)'-', WGA_SPAN_FILL);
+                wrecs.push_back(sg.rec);
+                wdst.push_back(at);
+                put(seg_len[sg.rec], 0, WGA_SPAN_HOLE);
+              }
+              put(q.tail, (uint64_t)'-', WGA_SPAN_FILL);
+            }
+            put(1, 9, WGA_SPAN_COPY_TEXT); /* the '\n' of "a score=0\n" */
+          }
+          if (at != out_bytes) fail("internal error: pafpseudo window layout");
+          const size_t keep = dg.owned.size();
+          dg.out_arena_for((size_t)out_bytes + 64);
+          auto* d_win = (uint8_t*)dg.out_arena;
+          const uint32_t n = (uint32_t)wrecs.size();
+          wga_rec_diag* d_diag = nullptr;
+          if (n) {
+            CigarTexts wcig;
+            wga_cigar_batch wb;
+            std::vector<wga_tok_err> werrs;
+            (void)device_tokenise(dg, pin, 0, n, wcig, &wb, &werrs, wrecs.data(), d_texts[g]);
+            std::vector<uint64_t> qo(n), ql(n), sk(n);
+            for (uint32_t k = 0; k < n; k++) qo[k] = q_off[wrecs[k]], ql[k] = q_len[wrecs[k]], sk[k] = skip[wrecs[k]];
+            d_diag = (wga_rec_diag*)dg.alloc((size_t)n * sizeof(wga_rec_diag));
+            dg.check(wga_pafpseudo_fill(dg.ctx, &wb, base ? 1 : 0, base ? fas[g].d_pool : nullptr, fas[g].bytes,
+                                        base ? dg.upload(qo) : nullptr, base ? dg.upload(ql) : nullptr, dg.upload(sk), d_win,
+                                        dg.upload(wdst), d_diag));
+          }
+          auto* d_bad = (uint64_t*)dg.alloc(8);
+          blob.append(16, '\0');
+          dg.check(wga_pafpseudo_frame(dg.ctx, items.size(), dg.upload(items), base ? fas[g].d_pool : nullptr, base ? fas[g].bytes : 0,
+                                       dg.upload((const uint8_t*)blob.data(), blob.size()), blob.size() - 16, d_win, out_bytes, d_bad));
+          uint64_t bad = 0;
+          dg.download(&bad, d_bad, 1);
+          if (bad != WGA_NONE) fail("internal error: pafpseudo window item " + std::to_string(bad));
+          if (n) { /* in the order the reference processes the records: the window's own */
+            std::vector<wga_rec_diag> diag(n);
+            dg.download(diag.data(), d_diag, n);
+            for (uint32_t k = 0; k < n && rows_err[g].msg.empty(); k++) {
+              const size_t i = wrecs[k];
+              if (diag[k].bad_base_pos != WGA_NONE)
+                rows_err[g].msg = std::string("Invalid Base: `") + fas[g].at(dg, q_off[i] + q_len[i] - 1 - diag[k].bad_base_pos) + "`";
+              else if (diag[k].panic_op_idx != WGA_NONE)
+                rows_err[g].msg = "panic: String::drain / insert_str beyond the end of the query sequence (cigar.rs:772,779)";
+              if (!rows_err[g].msg.empty()) rows_err[g].at = walk_pos[i];
+            }
+          }
+          if (!rows_err[g].msg.empty()) break; /* the file ends at the last window written */
+          stream_out(dg, out, d_win, (size_t)out_bytes, false);
+          dg.release_to(keep);
+          l0 = l1;
+        }
+        out.close();
+        if (!rows_err[g].msg.empty()) return;
+      }
+    });
+    g_timer.mark("pafpseudo rows (device)");
+    int first = -1; /* the device whose error the reference would have met first */
+    for (int g = 0; g < ngpu; g++)
+      if (!rows_err[g].msg.empty() && (first < 0 || rows_err[g].at < rows_err[first].at)) first = g;
+    if (first >= 0) fail(rows_err[first].msg);
+    return leave(0);
+  }
+  /* WGA_PSEUDO_WRITER=host: one fill of every kept segment of every target, the rows put together on the host */
+  if (n_all) {
     std::vector<std::vector<wga_rec_diag>> diag(ngpu);
     on_devices(ngpu, [&](int g) {
       const uint32_t n = cbs[g].n;
@@ -283,5 +459,6 @@ int cmd_pafpseudo(const std::string* input, const std::string& outdir, bool rewr
     out.write(text);
     out.close();
   }
+  g_timer.mark("pafpseudo rows (host)");
   return leave(0);
 }
