@@ -88,10 +88,8 @@ void call_paf_run(Dev& d, DevFasta& tf, DevFasta& qf, const PafInput& pin, const
     if (n) {
       auto* d_cnt = (uint64_t*)d.alloc((size_t)n * 8);
       d.check(wga_paf_call_events(d.ctx, &cb, svlen, snp, d_cnt, nullptr, nullptr));
-      auto* d_eoff = (uint64_t*)d.alloc(((size_t)n + 1) * 8);
-      d.check(wga_exclusive_scan_u64(d.ctx, n, d_cnt, d_eoff));
       uint64_t n_ev = 0;
-      d.download(&n_ev, (const uint64_t*)d_eoff + n, 1);
+      uint64_t* d_eoff = d.scan(n, d_cnt, &n_ev);
       auto* d_ev = (uint64_t*)d.alloc((3 * n_ev + 3) * 8);
       d.check(wga_paf_call_events(d.ctx, &cb, svlen, snp, d_cnt, d_ev, d_eoff));
       /* the rows are formatted where the events lie (wga_paf_call_vcf): names, coordinates and the places of the fetched
@@ -416,10 +414,8 @@ int cmd_call_maf(const std::string* input, bool snp, bool inv, uint64_t svlen, c
     md.run(min, recs, true /* total_size = target row length (:115) */, [&](int g, Dev& dg, const MafRows& p, uint32_t lo, uint32_t cnt) {
       auto* d_cnt = (uint64_t*)dg.alloc((size_t)cnt * 8);
       dg.check(wga_maf_call_runs(dg.ctx, cnt, p.d_rows, p.d_t, p.d_q, p.d_c, d_cnt, nullptr, nullptr));
-      auto* d_roff = (uint64_t*)dg.alloc(((size_t)cnt + 1) * 8);
-      dg.check(wga_exclusive_scan_u64(dg.ctx, cnt, d_cnt, d_roff));
       uint64_t n_runs = 0;
-      dg.download(&n_runs, (const uint64_t*)d_roff + cnt, 1);
+      uint64_t* d_roff = dg.scan(cnt, d_cnt, &n_runs);
       auto* d_runs = (uint64_t*)dg.alloc((3 * n_runs + 3) * 8);
       dg.check(wga_maf_call_runs(dg.ctx, cnt, p.d_rows, p.d_t, p.d_q, p.d_c, d_cnt, d_runs, d_roff));
       /* names (each once) and the s lines' fields go up */

@@ -7,37 +7,49 @@
  * the length of the text, the number of records in front of the first bad one and that record's diagnostics come back.
  * WGA_CHAIN_HEAD_WRITER=host: the headers are printed by one host thread from the downloaded trims and scattered around the data
  * lines, as before K30 (measurements, and the cross-check of the device writer: same bytes); maf2chain below reads it too. */
-static bool chain_head_host_writer() {
-  const char* w = getenv("WGA_CHAIN_HEAD_WRITER");
-  return w && strcmp(w, "host") == 0;
+static bool chain_head_host_writer() { return env_is("WGA_CHAIN_HEAD_WRITER", "host"); }
+/* K10's count call over a batch: the trims, the data lines' bytes and the diagnostics of every record, on the device */
+struct ChainTrims {
+  wga_chain_trim_t* d_trim;
+  uint64_t* d_nb;
+  wga_rec_diag* d_diag;
+};
+static ChainTrims chain_trims(Dev& d, const wga_cigar_batch& cb) {
+  ChainTrims t;
+  t.d_trim = (wga_chain_trim_t*)d.alloc((size_t)cb.n * sizeof(wga_chain_trim_t));
+  t.d_nb = (uint64_t*)d.alloc((size_t)cb.n * 8);
+  t.d_diag = (wga_rec_diag*)d.alloc((size_t)cb.n * sizeof(wga_rec_diag));
+  d.check(wga_cigar_chain(d.ctx, &cb, t.d_trim, t.d_nb, t.d_diag, nullptr, nullptr));
+  return t;
 }
-/* a name's span in the buffer a batch's names are gathered in */
-static void chain_name_span(std::string& names, const std::string& name, uint64_t& off, uint32_t& len) {
-  off = names.size();
-  len = (uint32_t)name.size();
-  names += name;
-}
-/* the chain text of a batch whose K10 count call has run (d_trim, d_nb, d_diag on device d): K30's count call lays the records
- * out, K10's fill call writes the data lines of the records in front of the first bad one, K30's fill call the heads and record
- * ends around them.  Returns the text (on the device) and sets *bytes and *n_good. */
-static const uint8_t* chain_text_device(Dev& d, const wga_cigar_batch& cb, const uint8_t* d_names, uint64_t n_name_bytes,
-                                        const std::vector<wga_maf2paf_head>& heads, const wga_chain_trim_t* d_trim,
-                                        const uint64_t* d_nb, const wga_rec_diag* d_diag, uint64_t chain_id0, uint64_t* bytes,
-                                        uint32_t* n_good) {
+/* the chain text of a batch whose K10 count call has run (t, on device d) and whose heads are uploaded (hd): K30's count call
+ * lays the records out, K10's fill call writes the data lines of the records in front of the first bad one, K30's fill call the
+ * heads and record ends around them.  Returns the text (on the device) and sets *bytes and *n_good. */
+static const uint8_t* chain_text_device(Dev& d, const wga_cigar_batch& cb, const RecordHeads& hd, const ChainTrims& t,
+                                        uint64_t chain_id0, uint64_t* bytes, uint32_t* n_good) {
   const uint32_t n = cb.n;
-  auto* d_heads = d.upload(heads);
   void* d_work = d.alloc((size_t)wga_chain_heads_work_bytes(n));
   auto* d_data_off = (uint64_t*)d.alloc((size_t)n * 8);
-  d.check(wga_chain_heads(d.ctx, n, d_names, n_name_bytes, d_heads, d_trim, d_nb, d_diag, chain_id0, d_work, d_data_off, bytes,
-                          n_good, nullptr));
+  d.check(wga_chain_heads(d.ctx, n, hd.d_names, hd.n_name_bytes, hd.d_heads, t.d_trim, t.d_nb, t.d_diag, chain_id0, d_work,
+                          d_data_off, bytes, n_good, nullptr));
   auto* d_out = (uint8_t*)d.alloc((size_t)*bytes + 64);
   if (*n_good) {
     wga_cigar_batch cb2 = cb;
     cb2.n = *n_good;
     d.check(wga_cigar_chain(d.ctx, &cb2, nullptr, nullptr, nullptr, d_out, d_data_off));
-    d.check(wga_chain_heads(d.ctx, n, d_names, n_name_bytes, d_heads, d_trim, d_nb, d_diag, chain_id0, d_work, d_data_off, bytes,
-                            n_good, d_out));
+    d.check(wga_chain_heads(d.ctx, n, hd.d_names, hd.n_name_bytes, hd.d_heads, t.d_trim, t.d_nb, t.d_diag, chain_id0, d_work,
+                            d_data_off, bytes, n_good, d_out));
   }
+  return d_out;
+}
+/* ... and with the heads printed by the host: the data lines of records [0, f.mid_off.size()) between the heads and record ends
+ * that were added to f */
+static const uint8_t* chain_text_host(Dev& d, const wga_cigar_batch& cb, HostFraming& f) {
+  auto* d_out = (uint8_t*)d.alloc(f.pos + 64);
+  wga_cigar_batch cb2 = cb;
+  cb2.n = (uint32_t)f.mid_off.size();
+  d.check(wga_cigar_chain(d.ctx, &cb2, nullptr, nullptr, nullptr, d_out, d.upload(f.mid_off)));
+  f.scatter(d, d_out);
   return d_out;
 }
 /* the chains of records [lo, hi) of a piece on device d, in resident batches; a batch's text goes to `sink` while it is still on
@@ -62,99 +74,42 @@ static std::string paf2chain_range(Dev& d, const PafInput& pin, size_t lo, size_
     CigarTexts cigars;
     wga_cigar_batch cb;
     pending_error = device_tokenise(d, pin, i0, (uint32_t)(i - i0), cigars, &cb, nullptr, nullptr, d_text_here);
-    uint32_t n = cb.n;
+    const uint32_t n = cb.n;
     if (n) {
-      auto* d_trim = (wga_chain_trim_t*)d.alloc((size_t)n * sizeof(wga_chain_trim_t));
-      auto* d_nb = (uint64_t*)d.alloc((size_t)n * 8);
-      auto* d_diag = (wga_rec_diag*)d.alloc((size_t)n * sizeof(wga_rec_diag));
-      d.check(wga_cigar_chain(d.ctx, &cb, d_trim, d_nb, d_diag, nullptr, nullptr));
+      const ChainTrims t = chain_trims(d, cb);
       if (!host_writer) {
-        std::vector<wga_maf2paf_head> heads(n);
-        std::string names;
-        for (uint32_t k = 0; k < n; k++) {
-          const PafRecord& r = recs[i0 + k];
-          wga_maf2paf_head& h = heads[k];
-          memset(&h, 0, sizeof h);
-          h.q[0] = r.query_length, h.q[1] = r.query_start, h.q[2] = r.query_end;
-          h.t[0] = r.target_length, h.t[1] = r.target_start, h.t[2] = r.target_end;
-          h.strand_neg = r.neg ? 1 : 0;
-          chain_name_span(names, r.query_name, h.qname_off, h.qname_len);
-          chain_name_span(names, r.target_name, h.tname_off, h.tname_len);
-        }
-        const uint8_t* d_names = d.upload((const uint8_t*)names.data(), names.size());
+        RecordHeads hd(n);
+        for (uint32_t k = 0; k < n; k++) hd.add(recs[i0 + k]);
+        hd.upload(d);
         uint64_t bytes = 0;
         uint32_t good = 0;
-        const uint8_t* d_out = chain_text_device(d, cb, d_names, names.size(), heads, d_trim, d_nb, d_diag,
-                                                 chain_base + (uint64_t)i0, &bytes, &good);
+        const uint8_t* d_out = chain_text_device(d, cb, hd, t, chain_base + (uint64_t)i0, &bytes, &good);
         if (good < n) { /* parse_cigar_to_trim fails before anything of the record is written */
           wga_rec_diag g;
-          d.download(&g, d_diag + good, 1);
-          pending_error = "CIGAR OP `" + cigar_op_token_at(cigars[good], g.bad_op_idx) + "` invalid";
+          d.download(&g, t.d_diag + good, 1);
+          pending_error = bad_op_message(cigars, good, g);
         }
         if (good) sink(d, d_out, (size_t)bytes);
-        d.release_to(keep);
-        i0 = i;
-        continue;
-      }
-      std::vector<wga_chain_trim_t> trim(n);
-      std::vector<uint64_t> nb(n);
-      std::vector<wga_rec_diag> diag(n);
-      d.download(trim.data(), d_trim, n);
-      d.download(nb.data(), d_nb, n);
-      d.download(diag.data(), d_diag, n);
-      for (uint32_t k = 0; k < n; k++)
-        if (diag[k].bad_op_idx != WGA_NONE) { /* parse_cigar_to_trim fails before anything of the record is written */
-          pending_error = "CIGAR OP `" + cigar_op_token_at(cigars[k], diag[k].bad_op_idx) + "` invalid";
-          n = k;
-          break;
-        }
-      if (n) {
-        std::string blob;
-        std::vector<uint64_t> blob_off{0}, dst, data_off(n);
-        uint64_t pos = 0;
+      } else {
+        std::vector<wga_chain_trim_t> trim(n);
+        std::vector<uint64_t> nb(n);
+        std::vector<wga_rec_diag> diag(n);
+        d.download(trim.data(), t.d_trim, n);
+        d.download(nb.data(), t.d_nb, n);
+        d.download(diag.data(), t.d_diag, n);
+        HostFraming f;
         for (uint32_t k = 0; k < n; k++) {
-          const PafRecord& r = recs[i0 + k];
-          const wga_chain_trim_t& t = trim[k];
-          uint64_t qs = r.query_start, qe = r.query_end, ts = r.target_start + t.head_del, te = r.target_end - t.tail_del;
-          if (!r.neg) {
-            qs += t.head_ins;
-            qe -= t.tail_ins;
-          } else {
-            qs = r.query_length - (qe - t.head_ins);
-            qe = r.query_length - (qs + t.tail_ins);
+          if (diag[k].bad_op_idx != WGA_NONE) { /* parse_cigar_to_trim fails before anything of the record is written */
+            pending_error = bad_op_message(cigars, k, diag[k]);
+            break;
           }
-          std::string h = "chain\t255\t" + r.target_name + "\t";
-          append_u64(h, r.target_length);
-          h += "\t+\t";
-          append_u64(h, ts);
-          h.push_back('\t');
-          append_u64(h, te);
-          h += "\t" + r.query_name + "\t";
-          append_u64(h, r.query_length);
-          h += r.neg ? "\t-\t" : "\t+\t";
-          append_u64(h, qs);
-          h.push_back('\t');
-          append_u64(h, qe);
-          h.push_back('\t');
-          append_u64(h, chain_base + (uint64_t)(i0 + k));
-          dst.push_back(pos);
-          blob += h;
-          blob_off.push_back(blob.size());
-          pos += h.size();
-          data_off[k] = pos;
-          pos += nb[k];
-          dst.push_back(pos);
-          blob += "\n\n";
-          blob_off.push_back(blob.size());
-          pos += 2;
+          const PafRecord& r = recs[i0 + k];
+          std::string h;
+          append_chain_head(h, r.target_name, r.target_length, r.target_start, r.target_end, r.query_name, r.query_length, r.neg,
+                            r.query_start, r.query_end, trim[k], chain_base + (uint64_t)(i0 + k));
+          f.add(h, nb[k], "\n\n");
         }
-        auto* d_out = (uint8_t*)d.alloc(pos + 64);
-        wga_cigar_batch cb2 = cb;
-        cb2.n = n;
-        d.check(wga_cigar_chain(d.ctx, &cb2, nullptr, nullptr, nullptr, d_out, d.upload(data_off)));
-        d.check(wga_scatter_bytes(d.ctx, 2 * n, d.upload((const uint8_t*)blob.data(), blob.size()), d.upload(blob_off),
-                                  d_out, d.upload(dst)));
-        sink(d, d_out, (size_t)pos);
+        if (f.pos) sink(d, chain_text_host(d, cb, f), (size_t)f.pos);
       }
     }
     d.release_to(keep);
@@ -170,7 +125,7 @@ int cmd_paf2chain(const std::string* input, Output& out) {
   PafInput pin;
   uint64_t chain_base = 0; /* chain id = index of the record in the whole input */
   const char* const records_phase = chain_head_host_writer() ? "paf2chain records (host)" : "paf2chain records (device)";
-  std::vector<std::unique_ptr<Dev>> devs; /* --gpus N: devices 1 .. N - 1 next to `d` */
+  WorkerDevices wd(d); /* --gpus N */
   for (;;) {
     bool more = false;
     try {
@@ -188,31 +143,14 @@ int cmd_paf2chain(const std::string* input, Output& out) {
       });
       g_timer.mark(records_phase); /* a piece without a record to write */
     } else { /* a piece's records in contiguous ranges over the devices; the chains meet in input order, up to the first error */
-      d.init();
-      if (devs.empty()) {
-        devs.emplace_back(new Dev(0));
-        devs[0]->ctx = d.ctx; /* device 0's context is the reader's */
-        devs[0]->own_ctx = false;
-        for (int g = 1; g < g_gpus; g++) devs.emplace_back(new Dev(g));
-      }
       const int ng = g_gpus;
       std::vector<std::string> part(ng), err(ng);
-      std::string text16;
-      if (pin.on_device) text16 = pin.text + std::string(16, '\0');
-      on_devices(ng, [&](int g) {
-        const size_t lo = n * (size_t)g / ng, hi = n * (size_t)(g + 1) / ng;
-        if (lo == hi) return;
-        Dev& dg = *devs[g];
-        dg.init();
-        const size_t keep = dg.owned.size();
-        const uint8_t* d_text = nullptr;
-        if (pin.on_device) d_text = g == 0 ? pin.d_text : dg.upload((const uint8_t*)text16.data(), text16.size());
+      wd.run(pin, [&](int g, Dev& dg, size_t lo, size_t hi, const uint8_t* d_text) {
         err[g] = paf2chain_range(dg, pin, lo, hi, chain_base, d_text, [&](Dev& dd, const uint8_t* d_out, size_t bytes) {
           const size_t at = part[g].size();
           part[g].resize(at + bytes);
           if (bytes) dd.download((uint8_t*)&part[g][at], d_out, bytes);
         });
-        dg.release_to(keep);
       });
       g_timer.mark(records_phase);
       for (int g = 0; g < ng && pending_error.empty(); g++) {
@@ -281,8 +219,8 @@ static void chain_records_of_heads(const std::vector<wga_chain_head>& heads, con
 ChainInput load_chain(Dev& d, const std::string* input, bool keep_on_device = false) {
   ChainInput in;
   std::string text = read_all(input);
-  const char* force = getenv("WGA_CHAIN_READER"); /* "host": always the nom-semantics reader (measurements) */
-  if (!text.empty() && text.size() < 0xFFFFFFF0ull && !(force && strcmp(force, "host") == 0)) {
+  /* WGA_CHAIN_READER=host: always the nom-semantics reader (measurements) */
+  if (!text.empty() && text.size() < 0xFFFFFFF0ull && !env_is("WGA_CHAIN_READER", "host")) {
     g_timer.mark("file read");
     d.init();
     const size_t n_bytes = text.size();
@@ -367,10 +305,8 @@ ChainBatch chain_device_batch(Dev& d, const ChainInput& in, size_t first, uint32
   }
   auto* d_cnt = (uint64_t*)d.alloc((size_t)n * 8);
   d.check(wga_chain_lines_ops(d.ctx, n, b.n_lines, b.d_lines, b.d_line_off, d_cnt, nullptr, nullptr));
-  auto* d_ooff = (uint64_t*)d.alloc(((size_t)n + 1) * 8);
-  d.check(wga_exclusive_scan_u64(d.ctx, n, d_cnt, d_ooff));
   uint64_t total = 0;
-  d.download(&total, d_ooff + n, 1);
+  uint64_t* d_ooff = d.scan(n, d_cnt, &total);
   auto* d_ops = (uint32_t*)d.alloc((total + 4) * 4);
   d.check(wga_chain_lines_ops(d.ctx, n, b.n_lines, b.d_lines, b.d_line_off, nullptr, d_ops, d_ooff));
   b.cb.d_ops = d_ops;
@@ -450,13 +386,10 @@ static size_t c2m_run(Dev& d, DevFasta& tf, DevFasta& qf, const ChainInput& in, 
 static int cmd_chain2maf_multi(Dev& d, ChainInput& in, const std::string& t_fa, const std::string& q_fa, Output& out, int ngpu) {
   const std::vector<ChainRecord>& recs = in.recs;
   std::string pending_error = in.error;
-  std::vector<std::unique_ptr<Dev>> devs;
-  for (int g = 0; g < ngpu; g++) devs.emplace_back(new Dev(g));
-  if (in.on_device) { /* device 0 split the file: its worker borrows the reader's context, the others get their ranges' lines */
-    devs[0]->ctx = d.ctx;
-    devs[0]->own_ctx = false;
-    in.fetch_lines(d);
-  }
+  WorkerDevices wd(d);
+  /* device 0 split the file: its worker borrows the reader's context, the others get their ranges' lines */
+  std::vector<std::unique_ptr<Dev>>& devs = wd.list(in.on_device);
+  if (in.on_device) in.fetch_lines(d);
   std::vector<DevFasta> tf(ngpu), qf(ngpu);
   on_devices(ngpu, [&](int g) {
     devs[g]->init();
@@ -560,45 +493,21 @@ static void chain2paf_range(Dev& d, const ChainInput& in, bool in_place, size_t 
     std::vector<uint64_t> tb(n);
     d.download(tb.data(), d_tb, n);
     /* record text = host fields up to "cg:Z:" | device CIGAR | "\n" */
-    std::string blob;
-    std::vector<uint64_t> blob_off{0}, dst, text_off(n);
-    uint64_t pos = 0;
+    HostFraming f;
     for (uint32_t k = 0; k < n; k++) {
       const ChainRecord& r = recs[i0 + k];
       const wga_cigar_counts& c = counts[k];
       std::string h;
-      append_csv_field(h, r.query_name, '\t');
-      const uint64_t a[] = {r.query_size, r.query_start, r.query_end};
-      for (uint64_t v : a) {
-        h.push_back('\t');
-        append_u64(h, v);
-      }
-      h += r.query_neg ? "\t-\t" : "\t+\t";
-      append_csv_field(h, r.target_name, '\t');
       /* block_length = match + mismatch + del + inv_del (chain.rs:433-435) */
-      const uint64_t b2[] = {r.target_size, r.target_start, r.target_end, c.match,
-                             c.match + c.mismatch + c.del_bp + c.inv_del_bp, 255};
-      for (uint64_t v : b2) {
-        h.push_back('\t');
-        append_u64(h, v);
-      }
+      append_paf_columns(h, r.query_name, r.query_size, r.query_start, r.query_end, r.query_neg, r.target_name, r.target_size,
+                         r.target_start, r.target_end, c.match, c.match + c.mismatch + c.del_bp + c.inv_del_bp);
       h += "\tcg:Z:";
-      dst.push_back(pos);
-      blob += h;
-      blob_off.push_back(blob.size());
-      pos += h.size();
-      text_off[k] = pos;
-      pos += tb[k];
-      dst.push_back(pos);
-      blob += "\n";
-      blob_off.push_back(blob.size());
-      pos += 1;
+      f.add(h, tb[k], "\n");
     }
-    auto* d_out = (uint8_t*)d.alloc(pos + 64);
-    d.check(wga_chain_lines_cigar_text(d.ctx, n, b.n_lines, b.d_lines, b.d_line_off, nullptr, d_out, d.upload(text_off)));
-    d.check(wga_scatter_bytes(d.ctx, 2 * n, d.upload((const uint8_t*)blob.data(), blob.size()), d.upload(blob_off), d_out,
-                              d.upload(dst)));
-    sink(d, d_out, (size_t)pos);
+    auto* d_out = (uint8_t*)d.alloc(f.pos + 64);
+    d.check(wga_chain_lines_cigar_text(d.ctx, n, b.n_lines, b.d_lines, b.d_line_off, nullptr, d_out, d.upload(f.mid_off)));
+    f.scatter(d, d_out);
+    sink(d, d_out, (size_t)f.pos);
     d.release_to(keep);
     i0 = i;
   }
@@ -611,8 +520,7 @@ static void chain2paf_range(Dev& d, const ChainInput& in, bool in_place, size_t 
  * --gpus N > 1, more than 0xFFFFFFF0 chains and data lines, data lines of more than three packed ops each (below),
  * WGA_CHAIN2PAF_WRITER=host (measurements). */
 static bool chain2paf_device_wanted() {
-  const char* w = getenv("WGA_CHAIN2PAF_WRITER");
-  return g_gpus == 1 && !(w && strcmp(w, "host") == 0);
+  return g_gpus == 1 && !env_is("WGA_CHAIN2PAF_WRITER", "host");
 }
 /* ... and a file whose data lines need more packed ops than three per line (a value of 2^28 or more is walked in pieces, 2^64 - 1
  * in 2^36 of them): chain2paf_range counts and allocates those ops, and the command keeps what that path does with such a file,
@@ -624,9 +532,8 @@ static bool chain2paf_device_takes(Dev& d, const ChainInput& in) {
   auto* d_cnt = (uint64_t*)d.alloc((size_t)n * 8);
   auto* d_ooff = (uint64_t*)d.alloc(((size_t)n + 1) * 8);
   d.check(wga_chain_lines_ops(d.ctx, n, in.n_data_lines, in.d_lines, in.d_line_off, d_cnt, nullptr, nullptr));
-  d.check(wga_exclusive_scan_u64(d.ctx, n, d_cnt, d_ooff));
   uint64_t n_ops = 0;
-  d.download(&n_ops, d_ooff + n, 1);
+  d.scan(n, d_cnt, &n_ops, d_ooff);
   d.release(d_ooff);
   d.release(d_cnt);
   return n_ops <= 3 * in.n_data_lines;
@@ -686,13 +593,10 @@ int cmd_chain2paf(const std::string* input, Output& out) {
   } else { /* --gpus N: the chains in contiguous ranges over the devices, the rows meet in input order */
     const int ng = g_gpus;
     const size_t n = recs.size();
-    std::vector<std::unique_ptr<Dev>> devs;
-    for (int g = 0; g < ng; g++) devs.emplace_back(new Dev(g));
-    if (in.on_device) { /* device 0 split the file: its worker borrows the reader's context, the others get their ranges' lines */
-      devs[0]->ctx = d.ctx;
-      devs[0]->own_ctx = false;
-      in.fetch_lines(d);
-    }
+    WorkerDevices wd(d);
+    /* device 0 split the file: its worker borrows the reader's context, the others get their ranges' lines */
+    std::vector<std::unique_ptr<Dev>>& devs = wd.list(in.on_device);
+    if (in.on_device) in.fetch_lines(d);
     std::vector<std::string> part(ng);
     on_devices(ng, [&](int g) {
       const size_t lo = n * (size_t)g / ng, hi = n * (size_t)(g + 1) / ng;
@@ -720,112 +624,30 @@ int cmd_chain2paf(const std::string* input, Output& out) {
  * *d_text, *bytes. */
 static void maf2chain_text(Dev& d, const MafRows& p, const MafRecord* const* recs, uint32_t n, uint64_t chain_id0,
                            const uint8_t** d_text, uint64_t* bytes) {
-  const uint8_t* d_rows = p.d_rows;
-  auto *d_t = p.d_t, *d_q = p.d_q, *d_c = p.d_c;
-  auto* d_s = p.d_s;
-  auto* d_counts = (wga_cigar_counts*)d.alloc((size_t)n * sizeof(wga_cigar_counts));
-  auto* d_cnt = (uint64_t*)d.alloc((size_t)n * 8);
-  d.check(wga_maf_pair_stat(d.ctx, n, d_rows, d_t, d_q, d_c, d_s, d_counts, d_cnt, nullptr, nullptr));
-  auto* d_roff = (uint64_t*)d.alloc(((size_t)n + 1) * 8);
-  d.check(wga_exclusive_scan_u64(d.ctx, n, d_cnt, d_roff));
-  uint64_t n_runs = 0;
-  d.download(&n_runs, d_roff + n, 1);
-  auto* d_runs = (uint64_t*)d.alloc((n_runs + 1) * 8);
-  d.check(wga_maf_pair_stat(d.ctx, n, d_rows, d_t, d_q, d_c, d_s, d_counts, d_cnt, d_runs, d_roff));
-  auto* d_ocnt = (uint64_t*)d.alloc((size_t)n * 8);
-  d.check(wga_maf_runs_ops(d.ctx, n, n_runs, d_runs, d_roff, d_c, d_ocnt, nullptr, nullptr));
-  auto* d_ooff = (uint64_t*)d.alloc(((size_t)n + 1) * 8);
-  d.check(wga_exclusive_scan_u64(d.ctx, n, d_ocnt, d_ooff));
-  uint64_t n_ops = 0;
-  d.download(&n_ops, d_ooff + n, 1);
-  auto* d_ops = (uint32_t*)d.alloc((n_ops + 4) * 4);
-  d.check(wga_maf_runs_ops(d.ctx, n, n_runs, d_runs, d_roff, d_c, nullptr, d_ops, d_ooff));
-  wga_cigar_batch cb;
-  cb.d_ops = d_ops;
-  cb.d_op_off = d_ooff;
-  cb.d_strand_neg = d_s;
-  cb.n_ops = n_ops;
-  cb.n = n;
-  auto* d_trim = (wga_chain_trim_t*)d.alloc((size_t)n * sizeof(wga_chain_trim_t));
-  auto* d_nb = (uint64_t*)d.alloc((size_t)n * 8);
-  auto* d_diag = (wga_rec_diag*)d.alloc((size_t)n * sizeof(wga_rec_diag));
-  d.check(wga_cigar_chain(d.ctx, &cb, d_trim, d_nb, d_diag, nullptr, nullptr));
+  const wga_cigar_batch cb = maf_runs_batch(d, p, n, maf_runs(d, p, n));
+  const ChainTrims t = chain_trims(d, cb);
   if (!chain_head_host_writer()) {
-    std::vector<wga_maf2paf_head> heads(n);
-    std::string names;
-    auto span = [&](const MafSLine& l, uint64_t& off, uint32_t& len) {
-      if (p.names_in_rows)
-        off = l.name_off, len = (uint32_t)l.name.size();
-      else
-        chain_name_span(names, l.name, off, len);
-    };
-    for (uint32_t k = 0; k < n; k++) {
-      const MafRecord& r = *recs[k];
-      wga_maf2paf_head& h = heads[k];
-      memset(&h, 0, sizeof h);
-      h.q[0] = r.q().size, h.q[1] = r.query_start(), h.q[2] = r.query_end();
-      h.t[0] = r.t().size, h.t[1] = r.t().start, h.t[2] = r.t().start + r.t().align_size;
-      h.strand_neg = r.q().neg ? 1 : 0;
-      span(r.q(), h.qname_off, h.qname_len);
-      span(r.t(), h.tname_off, h.tname_len);
-    }
-    const uint8_t* d_names = p.names_in_rows ? d_rows : d.upload((const uint8_t*)names.data(), names.size());
-    const uint64_t n_name_bytes = p.names_in_rows ? p.n_row_bytes : names.size();
+    RecordHeads hd(n, &p);
+    for (uint32_t k = 0; k < n; k++) hd.add(*recs[k]);
+    hd.upload(d);
     uint32_t good = 0;
-    *d_text = chain_text_device(d, cb, d_names, n_name_bytes, heads, d_trim, d_nb, d_diag, chain_id0, bytes, &good);
+    *d_text = chain_text_device(d, cb, hd, t, chain_id0, bytes, &good);
     return;
   }
   std::vector<wga_chain_trim_t> trim(n);
   std::vector<uint64_t> nb(n);
-  d.download(trim.data(), d_trim, n);
-  d.download(nb.data(), d_nb, n);
-  std::string blob;
-  std::vector<uint64_t> blob_off{0}, dst, data_off(n);
-  uint64_t pos = 0;
+  d.download(trim.data(), t.d_trim, n);
+  d.download(nb.data(), t.d_nb, n);
+  HostFraming f;
   for (uint32_t k = 0; k < n; k++) {
     const MafRecord& r = *recs[k];
-    const wga_chain_trim_t& t = trim[k];
-    const bool neg = r.q().neg;
-    uint64_t qs = r.query_start(), qe = r.query_end();
-    const uint64_t ts = r.t().start + t.head_del, te = r.t().start + r.t().align_size - t.tail_del;
-    if (!neg) {
-      qs += t.head_ins;
-      qe -= t.tail_ins;
-    } else { /* chain.rs:131-136: the new end is computed from the already updated start */
-      qs = r.q().size - (qe - t.head_ins);
-      qe = r.q().size - (qs + t.tail_ins);
-    }
-    std::string h = "chain\t255\t" + r.t().name + "\t";
-    append_u64(h, r.t().size);
-    h += "\t+\t";
-    append_u64(h, ts);
-    h.push_back('\t');
-    append_u64(h, te);
-    h += "\t" + r.q().name + "\t";
-    append_u64(h, r.q().size);
-    h += neg ? "\t-\t" : "\t+\t";
-    append_u64(h, qs);
-    h.push_back('\t');
-    append_u64(h, qe);
-    h.push_back('\t');
-    append_u64(h, chain_id0 + (uint64_t)k);
-    dst.push_back(pos);
-    blob += h;
-    blob_off.push_back(blob.size());
-    pos += h.size();
-    data_off[k] = pos;
-    pos += nb[k];
-    dst.push_back(pos);
-    blob += "\n\n";
-    blob_off.push_back(blob.size());
-    pos += 2;
+    std::string h;
+    append_chain_head(h, r.t().name, r.t().size, r.t().start, r.t().start + r.t().align_size, r.q().name, r.q().size, r.q().neg,
+                      r.query_start(), r.query_end(), trim[k], chain_id0 + (uint64_t)k);
+    f.add(h, nb[k], "\n\n");
   }
-  auto* d_out = (uint8_t*)d.alloc(pos + 64);
-  d.check(wga_cigar_chain(d.ctx, &cb, nullptr, nullptr, nullptr, d_out, d.upload(data_off)));
-  d.check(wga_scatter_bytes(d.ctx, 2 * n, d.upload((const uint8_t*)blob.data(), blob.size()), d.upload(blob_off), d_out,
-                            d.upload(dst)));
-  *d_text = d_out;
-  *bytes = pos;
+  *d_text = chain_text_host(d, cb, f);
+  *bytes = f.pos;
 }
 
 int cmd_maf2chain(const std::string* input, const std::string* query_name, Output& out) {

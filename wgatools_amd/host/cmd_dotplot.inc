@@ -23,10 +23,7 @@ struct DotRecs {
   }
 };
 /* WGA_DOTPLOT_WRITER=host: the base-level rows are printed on the host from the downloaded segments (measurements) */
-static bool dotplot_host_writer() {
-  const char* e = getenv("WGA_DOTPLOT_WRITER");
-  return e && std::string(e) == "host";
-}
+static bool dotplot_host_writer() { return env_is("WGA_DOTPLOT_WRITER", "host"); }
 /* csv rows (no header line) of the records R: base-level segments from wga_cigar_dotplot over the device batch cb, written as
  * text on the device (K26, wga_dotplot_csv), or one overview row per record from the counts */
 static std::string dotplot_rows(Dev& d, bool base, bool no_identity, uint64_t cutoff, const DotRecs& R, const wga_cigar_batch& cb,
@@ -38,10 +35,8 @@ static std::string dotplot_rows(Dev& d, bool base, bool no_identity, uint64_t cu
       auto* d_cnt = (uint64_t*)d.alloc((size_t)n * 8);
       auto *d_ts = d.upload(R.ts), *d_qs = d.upload(R.qs);
       d.check(wga_cigar_dotplot(d.ctx, &cb, cutoff, d_ts, d_qs, d_cnt, nullptr, nullptr));
-      auto* d_off = (uint64_t*)d.alloc(((size_t)n + 1) * 8);
-      d.check(wga_exclusive_scan_u64(d.ctx, n, d_cnt, d_off));
       uint64_t n_rows = 0;
-      d.download(&n_rows, d_off + n, 1);
+      uint64_t* d_off = d.scan(n, d_cnt, &n_rows);
       auto* d_segs = (uint64_t*)d.alloc((n_rows + 1) * 5 * 8);
       d.check(wga_cigar_dotplot(d.ctx, &cb, cutoff, d_ts, d_qs, nullptr, d_segs, d_off));
       /* every row ends in its record's tail: the names quoted once per record, the newline */
@@ -130,7 +125,7 @@ static std::string dotplot_paf_part(Dev& d, const PafInput& pin, size_t lo, size
       d.download(diag.data(), d_diag, cb.n);
       for (uint32_t k = 0; k < cb.n; k++)
         if (diag[k].bad_op_idx != WGA_NONE) {
-          err = "CIGAR OP `" + cigar_op_token_at(cigars[k], diag[k].bad_op_idx) + "` invalid";
+          err = bad_op_message(cigars, k, diag[k]);
           break;
         }
     }
@@ -151,35 +146,12 @@ static std::string dotplot_maf_part(Dev& d, const MafRows& p, const MafRecord* c
   cb.n = 0;
   std::vector<wga_cigar_counts> counts;
   if (n && (base || !no_identity)) {
-    const uint8_t* d_rows = p.d_rows;
-    auto *d_t = p.d_t, *d_q = p.d_q, *d_c = p.d_c;
-    auto* d_s = p.d_s;
-    auto* d_counts = (wga_cigar_counts*)d.alloc((size_t)n * sizeof(wga_cigar_counts));
-    auto* d_cnt = (uint64_t*)d.alloc((size_t)n * 8);
-    d.check(wga_maf_pair_stat(d.ctx, n, d_rows, d_t, d_q, d_c, d_s, d_counts, d_cnt, nullptr, nullptr));
+    const MafRuns r = maf_runs(d, p, n, !base); /* the overview wants the counts only */
     if (!base) {
       counts.resize(n);
-      d.download(counts.data(), d_counts, n);
+      d.download(counts.data(), r.d_counts, n);
     } else {
-      auto* d_roff = (uint64_t*)d.alloc(((size_t)n + 1) * 8);
-      d.check(wga_exclusive_scan_u64(d.ctx, n, d_cnt, d_roff));
-      uint64_t n_runs = 0;
-      d.download(&n_runs, d_roff + n, 1);
-      auto* d_runs = (uint64_t*)d.alloc((n_runs + 1) * 8);
-      d.check(wga_maf_pair_stat(d.ctx, n, d_rows, d_t, d_q, d_c, d_s, d_counts, d_cnt, d_runs, d_roff));
-      auto* d_ocnt = (uint64_t*)d.alloc((size_t)n * 8);
-      d.check(wga_maf_runs_ops(d.ctx, n, n_runs, d_runs, d_roff, d_c, d_ocnt, nullptr, nullptr));
-      auto* d_ooff = (uint64_t*)d.alloc(((size_t)n + 1) * 8);
-      d.check(wga_exclusive_scan_u64(d.ctx, n, d_ocnt, d_ooff));
-      uint64_t n_ops = 0;
-      d.download(&n_ops, d_ooff + n, 1);
-      auto* d_ops = (uint32_t*)d.alloc((n_ops + 4) * 4);
-      d.check(wga_maf_runs_ops(d.ctx, n, n_runs, d_runs, d_roff, d_c, nullptr, d_ops, d_ooff));
-      cb.d_ops = d_ops;
-      cb.d_op_off = d_ooff;
-      cb.d_strand_neg = d_s;
-      cb.n_ops = n_ops;
-      cb.n = n;
+      cb = maf_runs_batch(d, p, n, r);
     }
   }
   return dotplot_rows(d, base, no_identity, cutoff, R, cb, counts);
@@ -204,7 +176,7 @@ int cmd_dotplot(const std::string* input, const std::string& format, const std::
   if (format == "paf") {
     PafChunks chunks(input, false);
     PafInput pin;
-    std::vector<std::unique_ptr<Dev>> devs;
+    WorkerDevices wd(d);
     while (chunks.next(d, pin)) {
       const size_t n = pin.recs.size();
       n_records += n;
@@ -213,25 +185,8 @@ int cmd_dotplot(const std::string* input, const std::string& format, const std::
       if (ng == 1) {
         part[0] = dotplot_paf_part(d, pin, 0, n, nullptr, base, no_identity, cutoff, err[0]);
       } else {
-        d.init();
-        if (devs.empty()) {
-          devs.emplace_back(new Dev(0));
-          devs[0]->ctx = d.ctx; /* device 0's context is the reader's */
-          devs[0]->own_ctx = false;
-          for (int g = 1; g < ng; g++) devs.emplace_back(new Dev(g));
-        }
-        std::string text16;
-        if (pin.on_device) text16 = pin.text + std::string(16, '\0');
-        on_devices(ng, [&](int g) {
-          const size_t lo = n * (size_t)g / ng, hi = n * (size_t)(g + 1) / ng;
-          if (lo == hi) return;
-          Dev& dg = *devs[g];
-          dg.init();
-          const size_t keep = dg.owned.size();
-          const uint8_t* d_text = nullptr;
-          if (pin.on_device) d_text = g == 0 ? pin.d_text : dg.upload((const uint8_t*)text16.data(), text16.size());
+        wd.run(pin, [&](int g, Dev& dg, size_t lo, size_t hi, const uint8_t* d_text) {
           part[g] = dotplot_paf_part(dg, pin, lo, hi, d_text, base, no_identity, cutoff, err[g]);
-          dg.release_to(keep);
         });
       }
       for (int g = 0; g < ng; g++) {

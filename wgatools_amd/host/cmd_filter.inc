@@ -156,10 +156,7 @@ struct PafOnDev {
   uint64_t n_bytes = 0, n_lines = 0, n_ok = 0; /* n_ok: the piece's records */
   uint64_t bytes = 0, kept = 0;                /* of the last count call */
 };
-static bool paf_filter_host_forced() {
-  const char* force = getenv("WGA_PAF_READER");
-  return force && strcmp(force, "host") == 0;
-}
+static bool paf_filter_host_forced() { return env_is("WGA_PAF_READER", "host"); }
 /* the piece on the device, split, and through the count call at thresholds 0 (every record kept: n_ok).  False, with nothing left
  * on the device: the piece is the host path's. */
 static bool paf_filter_upload(Dev& d, std::string& text, PafOnDev& p) {

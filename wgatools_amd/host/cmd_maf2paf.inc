@@ -3,10 +3,7 @@
 /* ---- maf2paf (converter.rs:29-54, maf.rs:484-520) ------------------------------------------------ */
 /* WGA_MAF2PAF_WRITER=host: the records' fields are printed by host threads around the device's cg:Z: text, as before K28
  * (measurements, and the cross-check of the device writer: same bytes) */
-static bool maf2paf_host_writer() {
-  const char* w = getenv("WGA_MAF2PAF_WRITER");
-  return w && strcmp(w, "host") == 0;
-}
+static bool maf2paf_host_writer() { return env_is("WGA_MAF2PAF_WRITER", "host"); }
 
 /* the PAF rows of blocks recs[0 .. n), whose rows stand on device d (p).  The records are written on the device (wga_maf2paf,
  * K28): the host fills the numbers of every head and says where the two names stand — in the uploaded file where the device
@@ -14,57 +11,32 @@ static bool maf2paf_host_writer() {
  * number of runs and the text's length come back before the text. */
 static std::string maf2paf_rows(Dev& d, const MafRows& p, const MafRecord* const* recs, uint32_t n, bool host_writer) {
   std::string text;
-  const uint8_t* d_rows = p.d_rows;
-  auto *d_t = p.d_t, *d_q = p.d_q, *d_c = p.d_c;
-  auto* d_s = p.d_s;
-  auto* d_counts = (wga_cigar_counts*)d.alloc((size_t)n * sizeof(wga_cigar_counts));
-  auto* d_cnt = (uint64_t*)d.alloc((size_t)n * 8);
-  d.check(wga_maf_pair_stat(d.ctx, n, d_rows, d_t, d_q, d_c, d_s, d_counts, d_cnt, nullptr, nullptr));
-  auto* d_roff = (uint64_t*)d.alloc(((size_t)n + 1) * 8);
-  d.check(wga_exclusive_scan_u64(d.ctx, n, d_cnt, d_roff));
-  uint64_t n_runs = 0;
-  d.download(&n_runs, d_roff + n, 1);
-  auto* d_runs = (uint64_t*)d.alloc((n_runs + 1) * 8);
-  d.check(wga_maf_pair_stat(d.ctx, n, d_rows, d_t, d_q, d_c, d_s, d_counts, d_cnt, d_runs, d_roff));
-  if (!host_writer && (uint64_t)n + n_runs <= 0xFFFFFFF0ull) { /* beyond wga_maf2paf's limit: the host's fields */
-    std::vector<wga_maf2paf_head> heads(n);
-    std::string names;
-    auto span = [&](const MafSLine& l, uint64_t& off, uint32_t& len) {
-      off = p.names_in_rows ? l.name_off : names.size();
-      len = (uint32_t)l.name.size();
-      if (!p.names_in_rows) names += l.name;
-    };
-    for (uint32_t k = 0; k < n; k++) {
-      const MafRecord& r = *recs[k];
-      wga_maf2paf_head& h = heads[k];
-      memset(&h, 0, sizeof h);
-      h.q[0] = r.q().size, h.q[1] = r.query_start(), h.q[2] = r.query_end();
-      h.t[0] = r.t().size, h.t[1] = r.t().start, h.t[2] = r.t().start + r.t().align_size;
-      h.strand_neg = r.q().neg ? 1 : 0;
-      span(r.q(), h.qname_off, h.qname_len);
-      span(r.t(), h.tname_off, h.tname_len);
-    }
-    const uint8_t* d_names = p.names_in_rows ? d_rows : d.upload((const uint8_t*)names.data(), names.size());
-    const uint64_t n_name_bytes = p.names_in_rows ? p.n_row_bytes : names.size();
-    auto* d_heads = d.upload(heads);
-    void* d_work = d.alloc((size_t)wga_maf2paf_work_bytes(n, n_runs));
+  const MafRuns R = maf_runs(d, p, n);
+  if (!host_writer && (uint64_t)n + R.n_runs <= 0xFFFFFFF0ull) { /* beyond wga_maf2paf's limit: the host's fields */
+    RecordHeads hd(n, &p);
+    for (uint32_t k = 0; k < n; k++) hd.add(*recs[k]);
+    hd.upload(d);
+    void* d_work = d.alloc((size_t)wga_maf2paf_work_bytes(n, R.n_runs));
     uint64_t total = 0;
-    d.check(wga_maf2paf(d.ctx, n, d_names, n_name_bytes, d_heads, d_counts, d_runs, d_roff, d_c, d_work, &total, nullptr));
+    d.check(wga_maf2paf(d.ctx, n, hd.d_names, hd.n_name_bytes, hd.d_heads, R.d_counts, R.d_runs, R.d_roff, p.d_c, d_work, &total,
+                        nullptr));
     auto* d_out = (uint8_t*)d.alloc(total + 64);
-    if (total) d.check(wga_maf2paf(d.ctx, n, d_names, n_name_bytes, d_heads, d_counts, d_runs, d_roff, d_c, d_work, &total, d_out));
+    if (total)
+      d.check(wga_maf2paf(d.ctx, n, hd.d_names, hd.n_name_bytes, hd.d_heads, R.d_counts, R.d_runs, R.d_roff, p.d_c, d_work, &total,
+                          d_out));
     text.resize((size_t)total);
     if (total) d.download((uint8_t*)&text[0], d_out, total);
     return text;
   }
   std::vector<uint64_t> roff(n + 1);
-  d.download(roff.data(), d_roff, n + 1);
+  d.download(roff.data(), R.d_roff, n + 1);
   /* the cg:Z: text is formatted on the device (wga_maf_runs_cigar_text) between the host's fields */
   auto* d_tb = (uint64_t*)d.alloc((size_t)n * 8);
-  d.check(wga_maf_runs_cigar_text(d.ctx, n, roff[n], d_runs, d_roff, d_c, d_tb, nullptr, nullptr));
+  d.check(wga_maf_runs_cigar_text(d.ctx, n, roff[n], R.d_runs, R.d_roff, p.d_c, d_tb, nullptr, nullptr));
   std::vector<uint64_t> tb(n);
   d.download(tb.data(), d_tb, n);
   std::vector<wga_cigar_counts> counts(n);
-  d.download(counts.data(), d_counts, n);
+  d.download(counts.data(), R.d_counts, n);
   /* the fields around the cg:Z: text: a record's "<12 columns>\tNM:i:<n>\tcg:Z:" and its "\n", formatted by host threads over
    * contiguous ranges of blocks (2 000 000 blocks: 0.5 s on one thread), dropped into the output by wga_scatter_bytes */
   unsigned nthr = std::thread::hardware_concurrency();
@@ -80,19 +52,8 @@ static std::string maf2paf_rows(Dev& d, const MafRows& p, const MafRecord* const
       const wga_cigar_counts& c = counts[k];
       const uint64_t block = c.match + c.mismatch + c.ins_bp + c.inv_ins_bp + c.del_bp + c.inv_del_bp;
       const size_t at = bl.size();
-      append_csv_field(bl, r.q().name, '\t');
-      const uint64_t a[] = {r.q().size, r.query_start(), r.query_end()};
-      for (uint64_t v : a) {
-        bl.push_back('\t');
-        append_u64(bl, v);
-      }
-      bl += r.q().neg ? "\t-\t" : "\t+\t";
-      append_csv_field(bl, r.t().name, '\t');
-      const uint64_t bb[] = {r.t().size, r.t().start, r.t().start + r.t().align_size, c.match, block, 255};
-      for (uint64_t v : bb) {
-        bl.push_back('\t');
-        append_u64(bl, v);
-      }
+      append_paf_columns(bl, r.q().name, r.q().size, r.query_start(), r.query_end(), r.q().neg, r.t().name, r.t().size, r.t().start,
+                         r.t().start + r.t().align_size, c.match, block);
       bl += "\tNM:i:";
       append_u64(bl, block - c.match);
       bl += "\tcg:Z:";
@@ -106,34 +67,19 @@ static std::string maf2paf_rows(Dev& d, const MafRows& p, const MafRecord* const
     fmt(0);
     for (auto& x : th) x.join();
   }
-  std::string blob;
+  HostFraming f; /* the threads' blobs joined are its blob: a head, then the "\n" behind the cg:Z: text, per record */
   {
     size_t total = 0;
     for (const std::string& bl : blobs) total += bl.size();
-    blob.reserve(total);
-    for (const std::string& bl : blobs) blob += bl;
+    f.blob.reserve(total);
+    for (const std::string& bl : blobs) f.blob += bl;
   }
-  std::vector<uint64_t> blob_off(2 * (size_t)n + 1), dst(2 * (size_t)n), text_off(n);
-  uint64_t pos = 0, bpos = 0;
-  for (uint32_t k = 0; k < n; k++) {
-    blob_off[2 * (size_t)k] = bpos;
-    dst[2 * (size_t)k] = pos;
-    bpos += hsize[k];
-    pos += hsize[k];
-    text_off[k] = pos;
-    pos += tb[k];
-    blob_off[2 * (size_t)k + 1] = bpos;
-    dst[2 * (size_t)k + 1] = pos;
-    bpos += 1;
-    pos += 1;
-  }
-  blob_off[2 * (size_t)n] = bpos;
-  auto* d_out = (uint8_t*)d.alloc(pos + 64);
-  d.check(wga_maf_runs_cigar_text(d.ctx, n, roff[n], d_runs, d_roff, d_c, nullptr, d_out, d.upload(text_off)));
-  d.check(wga_scatter_bytes(d.ctx, 2 * n, d.upload((const uint8_t*)blob.data(), blob.size()), d.upload(blob_off), d_out,
-                            d.upload(dst)));
-  text.resize((size_t)pos);
-  if (pos) d.download((uint8_t*)&text[0], d_out, pos);
+  for (uint32_t k = 0; k < n; k++) f.place(hsize[k], tb[k], 1);
+  auto* d_out = (uint8_t*)d.alloc(f.pos + 64);
+  d.check(wga_maf_runs_cigar_text(d.ctx, n, roff[n], R.d_runs, R.d_roff, p.d_c, nullptr, d_out, d.upload(f.mid_off)));
+  f.scatter(d, d_out);
+  text.resize((size_t)f.pos);
+  if (f.pos) d.download((uint8_t*)&text[0], d_out, f.pos);
   return text;
 }
 

@@ -1,25 +1,6 @@
 /* cmd_paf2maf.inc — part of wgatools_main.cpp (included there, inside its namespace: the commands share the device helpers, readers and
  * writers defined in front of the include). */
 /* ---- paf2maf (converter.rs:176-265) ------------------------------------------------------------- */
-/* one thread per device over fn(g); the first worker error (by device number) is rethrown on the caller's thread */
-static void on_devices(int ngpu, const std::function<void(int)>& fn) {
-  std::vector<std::string> werr(ngpu);
-  std::vector<std::thread> th;
-  for (int g = 0; g < ngpu; g++)
-    th.emplace_back([&, g] {
-      try {
-        fn(g);
-      } catch (Error& e) {
-        werr[g] = e.msg.empty() ? std::string("error") : e.msg;
-      } catch (std::exception& e) {
-        werr[g] = std::string("internal error: ") + e.what();
-      }
-    });
-  for (auto& t : th) t.join();
-  for (int g = 0; g < ngpu; g++)
-    if (!werr[g].empty()) fail(werr[g]);
-}
-
 /* fnv1a64(name): the sharding rule of the multi-device paths (the same hash as wgatools_amd/shard.py) */
 static uint64_t fnv1a64(const std::string& s) {
   uint64_t h = 0xCBF29CE484222325ull;

@@ -11,10 +11,7 @@
  * at the last window written.
  * WGA_PSEUDO_WRITER=host: all segments of all targets in one batch, downloaded, and every row put together as a string by one
  * host thread, as before K31 (measurements, and the cross-check of the device writer: same bytes). */
-static bool pseudo_host_writer() {
-  const char* w = getenv("WGA_PSEUDO_WRITER");
-  return w && strcmp(w, "host") == 0;
-}
+static bool pseudo_host_writer() { return env_is("WGA_PSEUDO_WRITER", "host"); }
 static uint64_t pseudo_window_bytes() {
   uint64_t b = (uint64_t)256 << 20;
   if (const char* e = getenv("WGA_PSEUDO_OUT_BYTES")) b = strtoull(e, nullptr, 10);

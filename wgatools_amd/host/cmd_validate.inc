@@ -13,9 +13,7 @@ struct ValidateAcc {
   std::string q_list, t_list, rows;
 };
 static bool validate_fix_host_forced() {
-  const char* w = getenv("WGA_VALIDATE_WRITER");
-  const char* r = getenv("WGA_PAF_READER");
-  return (w && strcmp(w, "host") == 0) || (r && strcmp(r, "host") == 0);
+  return env_is("WGA_VALIDATE_WRITER", "host") || env_is("WGA_PAF_READER", "host");
 }
 /* n bytes of device memory behind `dst`: two pinned buffers, the copy of one slab runs while the one before it is appended */
 static void download_append(Dev& d, std::string& dst, const uint8_t* d_src, size_t n) {
@@ -66,10 +64,8 @@ static bool validate_fix_device(Dev& d, std::string& text, ValidateAcc& acc) {
   auto* d_cnt = (uint64_t*)d.alloc((size_t)n * 8);
   auto* d_err = (wga_tok_err*)d.alloc((size_t)n * sizeof(wga_tok_err));
   d.check(wga_cigar_tokenise_spans(d.ctx, n, d_text, d_beg, d_end, d_cnt, d_err, nullptr, nullptr));
-  auto* d_ooff = (uint64_t*)d.alloc(((size_t)n + 1) * 8);
-  d.check(wga_exclusive_scan_u64(d.ctx, n, d_cnt, d_ooff));
   uint64_t n_ops = 0;
-  d.download(&n_ops, d_ooff + n, 1);
+  uint64_t* d_ooff = d.scan(n, d_cnt, &n_ops);
   auto* d_ops = (uint32_t*)d.alloc((size_t)(n_ops + 4) * 4);
   d.check(wga_cigar_tokenise_spans(d.ctx, n, d_text, d_beg, d_end, d_cnt, d_err, d_ops, d_ooff));
   std::vector<wga_tok_err> errs(n);
@@ -132,7 +128,7 @@ int cmd_validate(const std::string* input, const std::string* fix, Output& out) 
   ValidateAcc acc;
   uint64_t &n_total = acc.n_total, &q_bad = acc.q_bad, &t_bad = acc.t_bad;
   std::string &q_list = acc.q_list, &t_list = acc.t_list, &rows = acc.rows;
-  std::vector<std::unique_ptr<Dev>> devs; /* --gpus N: devices 1 .. N - 1 next to `d` */
+  WorkerDevices wd(d); /* --gpus N */
   auto host_piece = [&](PafInput& pin) { /* one piece of the file at a time */
     std::vector<PafRecord>& recs = pin.recs;
     const uint32_t n = (uint32_t)recs.size();
@@ -140,35 +136,15 @@ int cmd_validate(const std::string* input, const std::string* fix, Output& out) 
     d.init();
     std::string e;
     if (g_gpus > 1) { /* --gpus N: the records by target hash, as `stat` (the counts meet on the host) */
-      if (devs.empty()) {
-        devs.emplace_back(new Dev(0));
-        devs[0]->ctx = d.ctx; /* device 0's context is the reader's */
-        devs[0]->own_ctx = false;
-        for (int g = 1; g < g_gpus; g++) devs.emplace_back(new Dev(g));
-      }
       try {
-        stat_piece_multi(devs, pin, counts);
+        stat_piece_multi(wd.list(), pin, counts);
       } catch (Error& er) {
         e = er.msg;
       }
-    } else {
-      CigarTexts cigars;
-      wga_cigar_batch cb;
-      e = device_tokenise(d, pin, 0, n, cigars, &cb);
-      const uint32_t m = cb.n;
-      if (m) {
-        auto* d_counts = (wga_cigar_counts*)d.alloc((size_t)m * sizeof(wga_cigar_counts));
-        auto* d_diag = (wga_rec_diag*)d.alloc((size_t)m * sizeof(wga_rec_diag));
-        d.check(wga_cigar_stat(d.ctx, &cb, d_counts, d_diag, nullptr));
-        std::vector<wga_rec_diag> diag(m);
-        d.download(diag.data(), d_diag, m);
-        d.download(counts.data(), d_counts, m);
-        for (uint32_t k = 0; k < m && e.empty(); k++)
-          if (diag[k].bad_op_idx != WGA_NONE) {
-            e = "CIGAR OP `" + cigar_op_token_at(cigars[k], diag[k].bad_op_idx) + "` invalid";
-            break;
-          }
-      }
+    } else { /* the tag or tokeniser error speaks before an op K1 rejects */
+      std::string op_err;
+      e = paf_counts(d, pin, n, counts, op_err);
+      if (e.empty()) e = op_err;
     }
     /* rec.get_stat().unwrap() (:79) */
     if (!e.empty()) fail("panic: called `Result::unwrap()` on an `Err` value: " + e);
@@ -199,19 +175,8 @@ int cmd_validate(const std::string* input, const std::string* fix, Output& out) 
     }
     if (fix) /* csv writer: tab, flexible, no header; PafRecord field order (paf.rs:50-65) */
       for (const PafRecord& r : recs) {
-        append_csv_field(rows, r.query_name, '\t');
-        const uint64_t a[] = {r.query_length, r.query_start, r.query_end};
-        for (uint64_t v : a) {
-          rows.push_back('\t');
-          append_u64(rows, v);
-        }
-        rows += r.neg ? "\t-\t" : "\t+\t";
-        append_csv_field(rows, r.target_name, '\t');
-        const uint64_t b2[] = {r.target_length, r.target_start, r.target_end, r.matches, r.block_length, r.mapq};
-        for (uint64_t v : b2) {
-          rows.push_back('\t');
-          append_u64(rows, v);
-        }
+        append_paf_columns(rows, r.query_name, r.query_length, r.query_start, r.query_end, r.neg, r.target_name, r.target_length,
+                           r.target_start, r.target_end, r.matches, r.block_length, r.mapq);
         for (const std::string& tg : r.tags) {
           rows.push_back('\t');
           append_csv_field(rows, tg, '\t');

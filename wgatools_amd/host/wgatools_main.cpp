@@ -124,8 +124,8 @@ static GpuWarm g_warm;
  * the page cache moves 2-4 GB/s, the copy engine > 40 GB/s), anything else (stdout, .gz) keeps the one ordered
  * writer.  Replaces "download everything into one std::string, then fwrite" (r01: paf2maf 1.8 s for 3 GB of MAF). */
 struct DevStreamer {
-  static const size_t kPiece = (size_t)16 << 20;
-  static const int kBufs = 40; /* at most; a run takes what its writers need (below) */
+  static constexpr size_t kPiece = (size_t)16 << 20;
+  static constexpr int kBufs = 40; /* at most; a run takes what its writers need (below) */
   wga_ctx* ctx;
   void* buf[kBufs];
   explicit DevStreamer(wga_ctx* c) : ctx(c) {
@@ -271,6 +271,11 @@ struct DevStreamer {
  * pafcov shard their records over N devices by fnv1a64(target_name) % N — one worker thread and one context per device */
 static int g_gpus = 1;
 static bool g_spread = false; /* `--spread` (with --gpus N, pafcov): deal the records out round robin and sum the coverage over the devices */
+/* the knobs of the form WGA_*_READER=host, WGA_*_WRITER=host */
+static bool env_is(const char* name, const char* value) {
+  const char* e = getenv(name);
+  return e && strcmp(e, value) == 0;
+}
 
 struct Dev;
 static Dev* g_gz_dev = nullptr; /* the device host text for a `.gz` file is deflated on (Output::big_text) */
@@ -333,6 +338,13 @@ struct Dev {
   T* upload(const std::vector<T>& v) { return upload(v.data(), v.size()); }
   template <typename T>
   void download(T* h, const T* d, size_t n) { check(wga_memcpy_d2h(ctx, h, d, n * sizeof(T))); }
+  /* count, scan, total: the n + 1 exclusive offsets of d_cnt[0 .. n) (allocated here unless the caller brings them) and their sum */
+  uint64_t* scan(uint32_t n, const uint64_t* d_cnt, uint64_t* total, uint64_t* d_off = nullptr) {
+    if (!d_off) d_off = (uint64_t*)alloc(((size_t)n + 1) * 8);
+    check(wga_exclusive_scan_u64(ctx, n, d_cnt, d_off));
+    download(total, (const uint64_t*)d_off + n, 1);
+    return d_off;
+  }
   /* The rows of paf2maf go into ONE device buffer for the whole run (it grows when a piece needs more): a buffer per piece
    * would pay the allocation and the first touch of gigabytes every time. */
   void* out_arena = nullptr;
@@ -542,8 +554,7 @@ struct DevFasta {
   uint64_t bytes = 0;
   bool have_host = false;
   void load(Dev& d, const std::string& path) {
-    const char* mode = getenv("WGA_FASTA_READER");
-    if (mode && strcmp(mode, "host") == 0) {
+    if (env_is("WGA_FASTA_READER", "host")) {
       idx.load(path);
       idx.pool.insert(0, (size_t)kPad, 'N');
       idx.pool.append((size_t)kPad, 'N');
@@ -683,8 +694,8 @@ PafInput paf_from_text(Dev& d, std::string&& text, bool want_tags, uint64_t rec0
                        uint64_t byte0 = 0) {
   PafInput in;
   in.text = std::move(text);
-  const char* force = getenv("WGA_PAF_READER"); /* "host": always the csv-semantics reader (measurements) */
-  if (!want_tags && !in.text.empty() && in.text.size() < 0xFFFFFFF0ull && !(force && strcmp(force, "host") == 0)) {
+  /* WGA_PAF_READER=host: always the csv-semantics reader (measurements) */
+  if (!want_tags && !in.text.empty() && in.text.size() < 0xFFFFFFF0ull && !env_is("WGA_PAF_READER", "host")) {
     g_timer.mark("file read");
     d.init();
     in.text.append(16, '\0'); /* slack behind the text for whole-vector loads */
@@ -882,10 +893,8 @@ std::string device_tokenise(Dev& d, const PafInput& in, size_t first, uint32_t n
   auto* d_cnt = (uint64_t*)d.alloc((size_t)n_ok * 8);
   auto* d_err = (wga_tok_err*)d.alloc((size_t)n_ok * sizeof(wga_tok_err));
   d.check(wga_cigar_tokenise_spans(d.ctx, n_ok, d_text, d_beg, d_end, d_cnt, d_err, nullptr, nullptr));
-  auto* d_ooff = (uint64_t*)d.alloc(((size_t)n_ok + 1) * 8);
-  d.check(wga_exclusive_scan_u64(d.ctx, n_ok, d_cnt, d_ooff));
   uint64_t total = 0;
-  d.download(&total, d_ooff + n_ok, 1);
+  uint64_t* d_ooff = d.scan(n_ok, d_cnt, &total);
   auto* d_ops = (uint32_t*)d.alloc((total + 4) * 4);
   d.check(wga_cigar_tokenise_spans(d.ctx, n_ok, d_text, d_beg, d_end, d_cnt, d_err, d_ops, d_ooff));
   std::vector<wga_tok_err> errs(n_ok);
@@ -1073,6 +1082,8 @@ uint32_t expand_batch(Dev& d, const wga_cigar_batch& cb, const ExpandJob& j, con
   }
   return good;
 }
+
+#include "cmd_common.inc"
 
 #include "cmd_paf2maf.inc"
 
