@@ -1032,6 +1032,56 @@ int wga_pafpseudo_frame(wga_ctx*, uint64_t n_items, const wga_span_item* d_items
                         const uint8_t* d_text, uint64_t text_bytes,
                         uint8_t* d_out, uint64_t out_bytes, uint64_t* d_first_bad);
 
+/* ---- K32: `paf2maf`, `chain2maf` — the MAF record frames (replaces ExpandJob::add and the frame part of expand_batch,
+ *      wgatools_amd/host/wgatools_main.cpp: three strings per record built by one CPU thread, the counts and three offset arrays
+ *      downloaded, 3 n destinations computed, the blob, its offsets and the destinations uploaded and scattered, every diagnostic
+ *      downloaded; in the reference MAFWriter::write_record maf.rs:566-581 behind converter.rs:196-263 and :288-355) ---------------
+ * d_counts[n] are wga_cigar_stat's counters and d_t_src_len[n] / d_q_src_len[n] the lengths of the fetched slices, as for
+ * wga_paf2maf_layout; d_heads[n] the numbers AS PRINTED and the spans of the two names inside d_names[0 .. n_name_bytes).  Record
+ * r, in input order, is
+ *   a score=<score>\n
+ *   s\t<tname>\t<t[0]>\t<t[1]>\t<+|->\t<t[2]>\t          the target head
+ *   then  d_t_src_len[r] + ins_bp + inv_ins_bp bytes that this call does NOT write: the target row, at d_t_row_off[r]
+ *   \ns\t<qname>\t<q[0]>\t<q[1]>\t<+|->\t<q[2]>\t        the query head
+ *   then  d_q_src_len[r] + del_bp + inv_del_bp bytes that this call does NOT write: the query row, at d_q_row_off[r]
+ *   \n\n
+ * with every number in canonical decimal of its 64-bit value.  A name is written as it is (`format!`, no quoting); a name whose
+ * span does not lie inside d_names is written as empty.
+ *   d_out == NULL: the byte counts of every record's two heads (d_work); d_t_row_off[n], d_q_row_off[n] and d_rec_off[n + 1]
+ *                  (device memory; d_rec_off[n] = the text's length): exactly what wga_paf2maf_layout gives for pre_t / pre_q =
+ *                  those head lengths and post = 2, so wga_paf2maf_expand takes them unchanged; *total_bytes (a host value; the
+ *                  call synchronises).  d_diag is not read; *n_good = n and *good_bytes = *total_bytes.
+ *   otherwise    : every frame byte of all n records at the places of the first call, and not one byte else: the rows' bytes are
+ *                  left as they were, the ragged ends of 16-byte groups that a frame shares with a row included (narrower stores
+ *                  there), so wga_paf2maf_expand may run before or after this call on the stream.  *n_good = the smallest r
+ *                  whose d_diag[r] has bad_op_idx, panic_op_idx or bad_base_pos set, n when there is none or d_diag is NULL;
+ *                  *good_bytes = d_rec_off[*n_good] (host values; the call synchronises).  The frames behind n_good are written
+ *                  as well: the caller cuts the text at *good_bytes.  d_out may have any alignment, the caller leaves 16 bytes
+ *                  of slack behind the text; no byte in front of d_out and none from d_out + *total_bytes on is written.
+ *                  *total_bytes is read as the first call left it, so the two calls take the same arguments.
+ * All places are 64-bit: a text beyond 4 GiB is the normal case of a resident batch.
+ * n == 0: *total_bytes = 0, *n_good = 0, nothing is written.  WGA_E_INVALID_ARG: a null d_work, total_bytes, n_good or good_bytes,
+ * whatever n; a null array with n > 0 (d_names only when n_name_bytes > 0; d_diag may always be null).
+ * d_work: wga_paf2maf_frame_work_bytes(n) bytes of device memory, 8-byte aligned, shared by the two calls
+ * = 8 * (2 n + 2 + n / 1024 + 4): 8 bytes per record for each of the two heads' byte counts, one word for n_good (the
+ * min-reduction over d_diag) and one for good_bytes, plus the scan's partial sums. */
+typedef struct {
+  uint64_t score;                 /* as printed */
+  uint64_t t[3], q[3];            /* start, aligned size, source size — as printed (the caller has already
+                                     turned a '-' query's start into q_size - q_end, mod 2^64) */
+  uint64_t tname_off, qname_off;  /* spans of d_names */
+  uint32_t tname_len, qname_len;
+  uint8_t  t_neg, q_neg, pad[6];
+} wga_maf_frame_head;             /* 88 bytes */
+
+uint64_t wga_paf2maf_frame_work_bytes(uint64_t n);
+int wga_paf2maf_frame(wga_ctx*, uint32_t n, const uint8_t* d_names, uint64_t n_name_bytes,
+                      const wga_maf_frame_head* d_heads, const wga_cigar_counts* d_counts,
+                      const uint64_t* d_t_src_len, const uint64_t* d_q_src_len,
+                      const wga_rec_diag* d_diag, void* d_work,
+                      uint64_t* d_t_row_off, uint64_t* d_q_row_off, uint64_t* d_rec_off,
+                      uint64_t* total_bytes, uint32_t* n_good, uint64_t* good_bytes, uint8_t* d_out);
+
 #ifdef __cplusplus
 }
 #endif

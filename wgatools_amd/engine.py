@@ -49,6 +49,10 @@ MAF2PAF_HEAD_DTYPE = np.dtype([("q", np.uint64, 3), ("t", np.uint64, 3), ("qname
 SPAN_ITEM_DTYPE = np.dtype([("dst", "<u8"), ("len", "<u8"), ("src", "<u8"), ("kind", "<u4"), ("pad", "<u4")])
 SPAN_FILL, SPAN_COPY_POOL, SPAN_COPY_TEXT, SPAN_HOLE = 0, 1, 2, 3
 PSEUDO_FRAME_TILE = 65536
+# K32 (include/wga_hip.h wga_maf_frame_head)
+MAF_FRAME_HEAD_DTYPE = np.dtype([("score", "<u8"), ("t", np.uint64, 3), ("q", np.uint64, 3), ("tname_off", "<u8"),
+                                 ("qname_off", "<u8"), ("tname_len", "<u4"), ("qname_len", "<u4"), ("t_neg", np.uint8),
+                                 ("q_neg", np.uint8), ("pad", np.uint8, 6)])
 
 OP_CODES = {"M": 0, "I": 1, "D": 2, "N": 3, "S": 4, "H": 5, "P": 6, "=": 7, "X": 8}
 OP_I_CONT, OP_D_CONT, OP_OTHER = 9, 10, 11
@@ -193,6 +197,13 @@ class Engine:
         arr = np.ascontiguousarray(arr)
         self._check(self.lib.wga_memcpy_h2d(self.ctx, dst.ptr, arr.ctypes.data, arr.nbytes))
         self.sync()
+
+    def download_slice(self, src, byte_off, nbytes):
+        """bytes [byte_off, byte_off + nbytes) of a device array (or of a device pointer) as a numpy array of u8"""
+        out = np.empty(int(nbytes), dtype=np.uint8)
+        if nbytes:
+            self._check(self.lib.wga_memcpy_d2h(self.ctx, out.ctypes.data, _p(src) + int(byte_off), int(nbytes)))
+        return out
 
     def sync(self):
         self._check(self.lib.wga_sync(self.ctx))
@@ -678,6 +689,78 @@ class Engine:
         if not ((got[:lead] == 0xA5).all() and (got[lead + total:] == 0xA5).all()):
             raise _lib.WgaError("chain_records wrote outside d_out[0 .. total_bytes)")
         return got[lead:lead + total].tobytes(), good
+
+    def maf_frame_count(self, n, names, n_name_bytes, heads, counts, t_src_len, q_src_len, work, t_row_off, q_row_off, rec_off,
+                        diag=None):
+        """K32: the count call of wga_paf2maf_frame alone, total_bytes; it leaves the heads' byte counts in `work` and the
+        layout in t_row_off[n], q_row_off[n] and rec_off[n + 1]"""
+        total, good, gb = C.c_uint64(0), C.c_uint32(0), C.c_uint64(0)
+        self._check(self.lib.wga_paf2maf_frame(self.ctx, int(n), _p(names), int(n_name_bytes), _p(heads), _p(counts), _p(t_src_len),
+                                               _p(q_src_len), _p(diag), _p(work), _p(t_row_off), _p(q_row_off), _p(rec_off),
+                                               C.byref(total), C.byref(good), C.byref(gb), None))
+        return int(total.value)
+
+    def maf_frame(self, n, names, n_name_bytes, heads, counts, t_src_len, q_src_len, diag=None, work=None, out_shift=0):
+        """K32 (maf.rs:566-581): the frames of n MAF records around the places of their rows, both calls of wga_paf2maf_frame
+        on wga_cigar_stat's counters (or arrays of the same meaning) and the caller's heads (MAF_FRAME_HEAD_DTYPE).  Returns
+        (text, n_good, good_bytes, (t_row_off, q_row_off, rec_off)): the fill goes into a buffer of 0xA5, so the rows' places hold
+        that byte; the 64 bytes in front of and behind the text are checked.
+        work: a device buffer to use; out_shift: d_out starts that many bytes behind a 64-byte aligned address"""
+        n = int(n)
+        if work is None:
+            work = self.empty(max(int(self.lib.wga_paf2maf_frame_work_bytes(n)), 16), np.uint8)
+        lay = (self.empty(max(n, 1), np.uint64), self.empty(max(n, 1), np.uint64), self.empty(n + 1, np.uint64))
+        args = (self.ctx, n, _p(names), int(n_name_bytes), _p(heads), _p(counts), _p(t_src_len), _p(q_src_len), _p(diag), _p(work),
+                _p(lay[0]), _p(lay[1]), _p(lay[2]))
+        total, good, gb = C.c_uint64(0), C.c_uint32(0), C.c_uint64(0)
+        refs = (C.byref(total), C.byref(good), C.byref(gb))
+        self._check(self.lib.wga_paf2maf_frame(*args, *refs, None))
+        first = int(total.value)
+        guard = 64  # bytes around the text that the fill call must leave alone
+        out = self.upload(np.full(first + 2 * guard + 96, 0xA5, dtype=np.uint8))
+        lead = guard + (-out.ptr) % 64 + int(out_shift)
+        self._check(self.lib.wga_paf2maf_frame(*args, *refs, out.ptr + lead))
+        self.sync()
+        if int(total.value) != first:
+            raise _lib.WgaError("wga_paf2maf_frame changed its total in the second call")
+        got = out.numpy()
+        if not ((got[:lead] == 0xA5).all() and (got[lead + first:] == 0xA5).all()):
+            raise _lib.WgaError("wga_paf2maf_frame wrote outside d_out[0 .. total_bytes)")
+        return got[lead:lead + first].tobytes(), int(good.value), int(gb.value), lay
+
+    def maf_records(self, batch, names, heads, t_fa, t_fa_bytes, t_src_off, t_src_len, q_fa, q_fa_bytes, q_src_off, q_src_len,
+                    out_shift=0):
+        """paf2maf's / chain2maf's records of a batch: K1 -> K32 count -> the row kernel at K32's places -> K32 fill.  names: the bytes the heads' spans point into, heads: MAF_FRAME_HEAD_DTYPE (host
+        arrays or device arrays); the pools and slices as for paf2maf_expand.  Returns (the text of the records in front of the
+        first bad one, n_good, the whole text); the 64 bytes in front of and behind the text are checked."""
+        n = batch.n
+        if not isinstance(names, DeviceArray):
+            names = self.upload(np.frombuffer(bytes(names), dtype=np.uint8)) if len(names) else None
+        n_name_bytes = names.size if names is not None else 0
+        if not isinstance(heads, DeviceArray):
+            heads = self.upload(np.ascontiguousarray(heads, dtype=MAF_FRAME_HEAD_DTYPE)) if n else None
+        counts, diag, tile_ws = self.cigar_stat(batch)
+        work = self.empty(max(int(self.lib.wga_paf2maf_frame_work_bytes(n)), 16), np.uint8)
+        lay = (self.empty(max(n, 1), np.uint64), self.empty(max(n, 1), np.uint64), self.empty(n + 1, np.uint64))
+        args = (self.ctx, n, _p(names), n_name_bytes, _p(heads), _p(counts), _p(t_src_len), _p(q_src_len), _p(diag), _p(work),
+                _p(lay[0]), _p(lay[1]), _p(lay[2]))
+        total, good, gb = C.c_uint64(0), C.c_uint32(0), C.c_uint64(0)
+        refs = (C.byref(total), C.byref(good), C.byref(gb))
+        self._check(self.lib.wga_paf2maf_frame(*args, *refs, None))
+        first = int(total.value)
+        guard = 64
+        out = self.upload(np.full(first + 2 * guard + 96, 0xA5, dtype=np.uint8))
+        lead = guard + (-out.ptr) % 64 + int(out_shift)
+        if n:
+            self.paf2maf_expand(batch, counts, tile_ws, t_fa, t_fa_bytes, t_src_off, t_src_len, q_fa, q_fa_bytes, q_src_off,
+                                q_src_len, out.ptr + lead, lay[0], lay[1], diag)
+        self._check(self.lib.wga_paf2maf_frame(*args, *refs, out.ptr + lead))
+        self.sync()
+        got = out.numpy()
+        if int(total.value) != first or not ((got[:lead] == 0xA5).all() and (got[lead + first:] == 0xA5).all()):
+            raise _lib.WgaError("maf_records wrote outside d_out[0 .. total_bytes)")
+        text = got[lead:lead + first].tobytes()
+        return text[:int(gb.value)], int(good.value), text
 
     def pafpseudo_frame(self, items, pool, pool_bytes, text, text_bytes, out, out_bytes, first_bad=None):
         """K31 (the rows of pseudomaf.rs:98-209 around the segments): writes every FILL / COPY span of `items` (SPAN_ITEM_DTYPE, a

@@ -357,6 +357,7 @@ static size_t c2m_run(Dev& d, DevFasta& tf, DevFasta& qf, const ChainInput& in, 
       wga_rec_diag g;
       sink.which = nullptr;
       sink.first = i0;
+      sink.records_phase = kChain2mafRecords;
       const uint32_t good = expand_batch(d, b.cb, job, tf.d_pool, tf.bytes, qf.d_pool, qf.bytes, sink, &g);
       d.check(wga_sync(d.ctx));
       if (good < n) {
@@ -427,6 +428,7 @@ static int cmd_chain2maf_multi(Dev& d, ChainInput& in, const std::string& t_fa, 
   offsets[0] = pos0;
   for (size_t i = 0; i < n; i++) offsets[i + 1] = offsets[i] + (i < first_bad ? sizes[i] : 0);
   pass(BatchSink::ROWS, first_bad);
+  g_timer.mark(kChain2mafRecords[maf_frame_host_writer() ? 1 : 0]); /* the devices' workers do not mark */
   for (int g = 0; g < ngpu; g++) first_bad = std::min(first_bad, bad_at[g]);
   if (first_bad < n)
     for (int g = 0; g < ngpu; g++)
@@ -456,6 +458,7 @@ int cmd_chain2maf(const std::string* input, const std::string& t_fa, const std::
   sink.out = &out;
   std::string err;
   if (c2m_run(d, tf, qf, in, true, 0, recs.size(), sink, err) < recs.size()) pending_error = err;
+  g_timer.mark(kChain2mafRecords[maf_frame_host_writer() ? 1 : 0]); /* a file without a record to write */
   out.close();
   if (!pending_error.empty()) fail(pending_error);
   return leave(0);

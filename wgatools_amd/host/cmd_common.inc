@@ -434,19 +434,28 @@ static wga_maf2paf_head record_head(const MafRecord& r) {
 static wga_maf2paf_head record_head(const PafRecord& r) {
   return record_head(r.query_length, r.query_start, r.query_end, r.neg, r.target_length, r.target_start, r.target_end);
 }
-struct RecordHeads {
-  std::vector<wga_maf2paf_head> heads;
+/* The names a batch's heads point into: in the uploaded file where the device splitter took the piece and this device holds it
+ * (rows), otherwise gathered here once per batch and uploaded (RecordHeads below, MafFrameHeads of paf2maf and chain2maf). */
+struct NameSpans {
   std::string names;
   const MafRows* rows; /* the uploaded rows the names are read in, or nullptr: gathered */
-  const wga_maf2paf_head* d_heads = nullptr;
   const uint8_t* d_names = nullptr;
   uint64_t n_name_bytes = 0;
-  explicit RecordHeads(uint32_t n, const MafRows* p = nullptr) : rows(p && p->names_in_rows ? p : nullptr) { heads.reserve(n); }
+  explicit NameSpans(const MafRows* p = nullptr) : rows(p && p->names_in_rows ? p : nullptr) {}
   void span(const std::string& name, uint64_t at_in_rows, uint64_t& off, uint32_t& len) {
     off = rows ? at_in_rows : names.size();
     len = (uint32_t)name.size();
     if (!rows) names += name;
   }
+  void upload_names(Dev& d) {
+    d_names = rows ? rows->d_rows : d.upload((const uint8_t*)names.data(), names.size());
+    n_name_bytes = rows ? rows->n_row_bytes : names.size();
+  }
+};
+struct RecordHeads : NameSpans {
+  std::vector<wga_maf2paf_head> heads;
+  const wga_maf2paf_head* d_heads = nullptr;
+  explicit RecordHeads(uint32_t n, const MafRows* p = nullptr) : NameSpans(p) { heads.reserve(n); }
   void add(const MafRecord& r) {
     wga_maf2paf_head h = record_head(r);
     span(r.q().name, r.q().name_off, h.qname_off, h.qname_len);
@@ -460,8 +469,7 @@ struct RecordHeads {
     heads.push_back(h);
   }
   void upload(Dev& d) {
-    d_names = rows ? rows->d_rows : d.upload((const uint8_t*)names.data(), names.size());
-    n_name_bytes = rows ? rows->n_row_bytes : names.size();
+    upload_names(d);
     d_heads = d.upload(heads);
   }
 };

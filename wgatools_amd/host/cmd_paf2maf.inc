@@ -75,6 +75,7 @@ size_t p2m_run(Dev& d, DevFasta& tf, DevFasta& qf, const PafInput& in, const siz
       wga_rec_diag g;
       sink.which = which;
       sink.first = i0;
+      sink.records_phase = kPaf2mafRecords;
       const uint32_t good = expand_batch(d, cb, job, tf.d_pool, tf.bytes, qf.d_pool, qf.bytes, sink, &g);
       if (good < n) {
         const uint32_t k = good;
@@ -170,6 +171,7 @@ int cmd_paf2maf_multi(const std::string* input, const std::string& t_fa, const s
     pass(BatchSink::ROWS, first_bad);
     for (int g = 0; g < ngpu; g++) first_bad = std::min(first_bad, bad_at[g]);
     g_timer.mark("rows + copy out + write");
+    g_timer.mark(kPaf2mafRecords[maf_frame_host_writer() ? 1 : 0]); /* the devices' workers do not mark: this names the writer they ran */
     file_pos = offsets[first_bad];
     for (int g = 0; g < ngpu; g++) devs[g]->release_to(keep_pools[g]); /* the piece's text on every device */
     if (first_bad < n) {
@@ -217,6 +219,7 @@ int cmd_paf2maf(const std::string* input, const std::string& t_fa, const std::st
     BatchSink sink;
     sink.out = &out;
     p2m_run(d, tf, qf, in, nullptr, in.recs.size(), nullptr, sink, pending_error);
+    g_timer.mark(kPaf2mafRecords[maf_frame_host_writer() ? 1 : 0]); /* a piece without a record to write */
     d.release_to(keep_pools);
     if (!pending_error.empty()) break;
   }

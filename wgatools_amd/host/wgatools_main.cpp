@@ -919,12 +919,26 @@ std::string device_tokenise(Dev& d, const PafInput& in, size_t first, uint32_t n
   return first_err;
 }
 
+#include "cmd_common.inc"
+
 /* ---- rows of a batch of records -> MAF text (shared by paf2maf and chain2maf) ------------------------
- * The host supplies the fetched slices and the line text around the rows (MAFWriter, maf.rs:566-581:
- * "a score=..", "s\tname\tstart\tsize\tstrand\tsrcsize\t<row>" twice, blank line); K1, the layout scan,
- * K2 and the snippet scatter run on the device and one copy brings the finished text back. */
+ * The host supplies the fetched slices and one wga_maf_frame_head per record (the numbers as MAFWriter prints them,
+ * maf.rs:566-581, and the spans of the two names, gathered once per batch); K1, the frame count call (K32: the layout), the
+ * row kernel and the frame fill call run on the device, and one copy brings the finished text back.
+ * WGA_MAF_FRAME_WRITER=host: the line text around the rows ("a score=..", "s\tname\tstart\tsize\tstrand\tsrcsize\t<row>"
+ * twice, blank line) is built by one host thread, laid out by wga_paf2maf_layout and scattered around the rows
+ * (wga_scatter_bytes), as before K32 (measurements, and the cross-check of the device writer: same bytes). */
+static bool maf_frame_host_writer() { return env_is("WGA_MAF_FRAME_WRITER", "host"); }
+/* WGA_TIMING: the phase of a batch's device work, named after the writer that ran ({device, host}) */
+static const char* const kPaf2mafRecords[2] = {"paf2maf records (device)", "paf2maf records (host)"};
+static const char* const kChain2mafRecords[2] = {"chain2maf records (device)", "chain2maf records (host)"};
 struct ExpandJob {
   std::vector<uint64_t> t_off, t_len, q_off, q_len;
+  const bool host_frames = maf_frame_host_writer();
+  /* the device writer: the heads and the names they point into */
+  std::vector<wga_maf_frame_head> heads;
+  NameSpans names;
+  /* the host writer: three snippets per record */
   std::vector<uint32_t> pre_t, pre_q, post;
   std::string blob;
   std::vector<uint64_t> blob_off{0};
@@ -935,6 +949,18 @@ struct ExpandJob {
     t_len.push_back(tl);
     q_off.push_back(qo);
     q_len.push_back(ql);
+    if (!host_frames) {
+      wga_maf_frame_head h;
+      memset(&h, 0, sizeof h);
+      h.score = score;
+      h.t[0] = t_start, h.t[1] = t_ali, h.t[2] = t_size;
+      h.q[0] = q_start, h.q[1] = q_ali, h.q[2] = q_size;
+      h.t_neg = t_neg ? 1 : 0, h.q_neg = q_neg ? 1 : 0;
+      names.span(t_name, 0, h.tname_off, h.tname_len);
+      names.span(q_name, 0, h.qname_off, h.qname_len);
+      heads.push_back(h);
+      return;
+    }
     std::string a = "a score=";
     append_u64(a, score);
     a += "\ns\t" + t_name + "\t";
@@ -966,6 +992,10 @@ struct ExpandJob {
     t_len.resize(k);
     q_off.resize(k);
     q_len.resize(k);
+    if (!host_frames) {
+      heads.resize(k); /* the names of the records behind stay in the buffer: no head points at them */
+      return;
+    }
     pre_t.resize(k);
     pre_q.resize(k);
     post.resize(k);
@@ -986,6 +1016,7 @@ struct BatchSink {
   int fd = -1;
   const size_t* which = nullptr; /* record k of the batch is record which[first + k] of the piece */
   size_t first = 0;
+  const char* const* records_phase = nullptr; /* WGA_TIMING: {device, host}, the phase named after the frame writer that ran */
 };
 
 /* n bytes of a device buffer to a file in runs: (offset in the buffer, length, file offset), through one pinned buffer */
@@ -1017,9 +1048,33 @@ void write_runs(Dev& d, int fd, const uint8_t* d_src, const std::vector<std::arr
   if (!err.empty()) fail(err);
 }
 
+/* ROWS: every record where the input order puts it; neighbours in the input leave in one run */
+static void write_rows(Dev& d, const BatchSink& sink, const uint8_t* d_out, const std::vector<uint64_t>& rec_off, uint32_t good) {
+  std::vector<std::array<uint64_t, 3>> runs;
+  for (uint32_t k = 0; k < good; k++) {
+    const uint64_t off = (*sink.offsets)[sink.which ? sink.which[sink.first + k] : sink.first + k], len = rec_off[k + 1] - rec_off[k];
+    if (!runs.empty() && runs.back()[0] + runs.back()[1] == rec_off[k] && runs.back()[2] + runs.back()[1] == off)
+      runs.back()[1] += len;
+    else
+      runs.push_back({rec_off[k], len, off});
+  }
+  d.check(wga_sync(d.ctx));
+  write_runs(d, sink.fd, d_out, runs);
+}
+/* SIZES: a record's byte count is known before a row byte exists */
+static void take_sizes(const BatchSink& sink, const std::vector<uint64_t>& rec_off, uint32_t n) {
+  for (uint32_t k = 0; k < n; k++) (*sink.sizes)[sink.which ? sink.which[sink.first + k] : sink.first + k] = rec_off[k + 1] - rec_off[k];
+}
+/* the batch's work on the device is done: what it took belongs to the phase named after the frame writer */
+static void mark_records(Dev& d, const BatchSink& sink, bool host_frames) {
+  if (!sink.records_phase) return;
+  d.check(wga_sync(d.ctx));
+  g_timer.mark(sink.records_phase[host_frames ? 1 : 0]);
+}
+
 /* Writes (or sizes) the text of the leading records without a diagnostic; returns their number and, when it is
  * below cb.n, the diagnostic of the first failing record in *first_bad. */
-uint32_t expand_batch(Dev& d, const wga_cigar_batch& cb, const ExpandJob& j, const uint8_t* d_tpool, uint64_t t_bytes,
+uint32_t expand_batch(Dev& d, const wga_cigar_batch& cb, ExpandJob& j, const uint8_t* d_tpool, uint64_t t_bytes,
                       const uint8_t* d_qpool, uint64_t q_bytes, BatchSink& sink, wga_rec_diag* first_bad) {
   const uint32_t n = cb.n;
   auto* d_counts = (wga_cigar_counts*)d.alloc((size_t)n * sizeof(wga_cigar_counts));
@@ -1027,15 +1082,49 @@ uint32_t expand_batch(Dev& d, const wga_cigar_batch& cb, const ExpandJob& j, con
   void* d_tiles = d.alloc(wga_tile_ws_bytes(cb.n_ops));
   d.check(wga_cigar_stat(d.ctx, &cb, d_counts, d_diag, d_tiles));
   uint64_t *d_to = d.upload(j.t_off), *d_tl = d.upload(j.t_len), *d_qo = d.upload(j.q_off), *d_ql = d.upload(j.q_len);
-  uint32_t *d_pt = d.upload(j.pre_t), *d_pq = d.upload(j.pre_q), *d_po = d.upload(j.post);
   auto* d_tro = (uint64_t*)d.alloc((size_t)n * 8);
   auto* d_qro = (uint64_t*)d.alloc((size_t)n * 8);
   auto* d_rec = (uint64_t*)d.alloc(((size_t)n + 1) * 8);
+  if (!j.host_frames) {
+    /* K32: the count call lays the records out, the row kernel writes the rows, the fill call the frames around them on the
+     * same stream; the text's length, the records in front of the first bad one and their bytes come back */
+    NameSpans& names = j.names;
+    names.upload_names(d);
+    const wga_maf_frame_head* d_heads = d.upload(j.heads);
+    void* d_work = d.alloc((size_t)wga_paf2maf_frame_work_bytes(n));
+    uint64_t total = 0, good_bytes = 0;
+    uint32_t good = 0;
+    d.check(wga_paf2maf_frame(d.ctx, n, names.d_names, names.n_name_bytes, d_heads, d_counts, d_tl, d_ql, d_diag, d_work, d_tro,
+                              d_qro, d_rec, &total, &good, &good_bytes, nullptr));
+    std::vector<uint64_t> rec_off;
+    if (sink.mode != BatchSink::STREAM) { /* SIZES, and the runs of ROWS */
+      rec_off.resize((size_t)n + 1);
+      d.download(rec_off.data(), d_rec, (size_t)n + 1);
+    }
+    if (sink.mode == BatchSink::SIZES) {
+      take_sizes(sink, rec_off, n);
+      return n;
+    }
+    d.out_arena_for(total + 64);
+    auto* d_out = (uint8_t*)d.out_arena;
+    d.check(wga_paf2maf_expand(d.ctx, &cb, d_counts, d_tiles, d_tpool, t_bytes, d_to, d_tl, d_qpool, q_bytes, d_qo, d_ql, d_out,
+                               d_tro, d_qro, d_diag));
+    d.check(wga_paf2maf_frame(d.ctx, n, names.d_names, names.n_name_bytes, d_heads, d_counts, d_tl, d_ql, d_diag, d_work, d_tro,
+                              d_qro, d_rec, &total, &good, &good_bytes, d_out));
+    if (good < n) d.download(first_bad, d_diag + good, 1);
+    mark_records(d, sink, false);
+    if (sink.mode == BatchSink::STREAM)
+      stream_out(d, *sink.out, d_out, (size_t)good_bytes);
+    else
+      write_rows(d, sink, d_out, rec_off, good);
+    return good;
+  }
+  uint32_t *d_pt = d.upload(j.pre_t), *d_pq = d.upload(j.pre_q), *d_po = d.upload(j.post);
   d.check(wga_paf2maf_layout(d.ctx, n, d_counts, d_tl, d_ql, d_pt, d_pq, d_po, d_tro, d_qro, d_rec));
   std::vector<uint64_t> rec_off(n + 1), tro(n), qro(n);
   d.download(rec_off.data(), d_rec, n + 1);
-  if (sink.mode == BatchSink::SIZES) { /* a record's byte count is known here, before a row byte exists */
-    for (uint32_t k = 0; k < n; k++) (*sink.sizes)[sink.which ? sink.which[sink.first + k] : sink.first + k] = rec_off[k + 1] - rec_off[k];
+  if (sink.mode == BatchSink::SIZES) {
+    take_sizes(sink, rec_off, n);
     return n;
   }
   d.download(tro.data(), d_tro, n);
@@ -1066,24 +1155,13 @@ uint32_t expand_batch(Dev& d, const wga_cigar_batch& cb, const ExpandJob& j, con
     *first_bad = g;
     break;
   }
-  if (sink.mode == BatchSink::STREAM) {
+  mark_records(d, sink, true);
+  if (sink.mode == BatchSink::STREAM)
     stream_out(d, *sink.out, d_out, (size_t)rec_off[good]);
-  } else { /* ROWS: every record where the input order puts it; neighbours in the input leave in one run */
-    std::vector<std::array<uint64_t, 3>> runs;
-    for (uint32_t k = 0; k < good; k++) {
-      const uint64_t off = (*sink.offsets)[sink.which ? sink.which[sink.first + k] : sink.first + k], len = rec_off[k + 1] - rec_off[k];
-      if (!runs.empty() && runs.back()[0] + runs.back()[1] == rec_off[k] && runs.back()[2] + runs.back()[1] == off)
-        runs.back()[1] += len;
-      else
-        runs.push_back({rec_off[k], len, off});
-    }
-    d.check(wga_sync(d.ctx));
-    write_runs(d, sink.fd, d_out, runs);
-  }
+  else
+    write_rows(d, sink, d_out, rec_off, good);
   return good;
 }
-
-#include "cmd_common.inc"
 
 #include "cmd_paf2maf.inc"
 
