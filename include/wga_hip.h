@@ -1082,6 +1082,54 @@ int wga_paf2maf_frame(wga_ctx*, uint32_t n, const uint8_t* d_names, uint64_t n_n
                       uint64_t* d_t_row_off, uint64_t* d_q_row_off, uint64_t* d_rec_off,
                       uint64_t* total_bytes, uint32_t* n_good, uint64_t* good_bytes, uint8_t* d_out);
 
+/* ---- K33: `stat --each` — the TSV rows (replaces, for `-e`, the per-record StatInput / Statistic structs, the stable_sort over
+ *      all of them and the row printing of stat_tsv, wgatools_amd/host/wga_host.cpp: 17 integers, 2 names and 3 floats per row from
+ *      one CPU thread; in the reference split_final stat.rs:129-164 through the csv writer of stat.rs:117-123, over the
+ *      per-record statistics of common.rs:116-140) ---------------------------------------------------------------------------
+ * d_counts[n] are wga_cigar_stat's or wga_maf_pair_stat's counters; d_heads[n] the four numbers AS PRINTED and the spans of the
+ * two names inside d_names[0 .. n_name_bytes).  Row r, in input order, is ONE line of 22 columns, tabs between them:
+ *   <ref_name> <ref_size> <ref_start> <query_name> <query_size> <query_start> <aligned_size> 0 <identity> <similarity>
+ *   <matched> <mismatched> <ins_event> <del_event> <ins_size> <del_size> <inv_event> <inv_size>
+ *   <inv_ins_event> <inv_ins_size> <inv_del_event> <inv_del_size> \n
+ * with c = d_counts[r] and all integer arithmetic mod 2^64:
+ *   aligned_size = match + mismatch + del_bp + inv_del_bp            (unaligned_size is the literal 0 in this mode)
+ *   identity     = (float)match / (float)aligned_size
+ *   similarity   = (float)(match + mismatch) / (float)aligned_size
+ *   inv_size     = inv_ev != 0 ? (float)(aligned_size + match + mismatch + ins_bp + inv_ins_bp) / (float)(inv_ev + 1) : 0.0f
+ * u64 -> f32 rounds to nearest even and the division is the IEEE single precision one.  Integers are printed in canonical
+ * decimal.  A name is written as the csv writer does under QuoteStyle::Necessary with a tab delimiter (as it is, unless it holds
+ * a tab, a quote, CR or LF: then between quotes, every quote inside doubled); a name whose span does not lie inside d_names is
+ * written as empty.  An f32 is written as ryu does (wga_f32_text below).
+ *   d_out == NULL: the byte count of every row (d_work), d_row_off[n + 1] (device memory; d_row_off[n] = the text's length)
+ *                  and *total_bytes (a host value; the call synchronises).
+ *   otherwise    : the text at d_out[0 .. *total_bytes).  d_out may have any alignment, the caller leaves 16 bytes of slack
+ *                  behind the text; no byte in front of d_out and none from d_out + *total_bytes on is written.  *total_bytes,
+ *                  d_work and d_row_off are read as the first call left them, so the two calls take the same arguments.  A row
+ *                  whose span in d_row_off is not its byte count in d_work is not written.
+ * All places are 64-bit.  n == 0: *total_bytes = 0, nothing is written.  WGA_E_INVALID_ARG: a null d_work or total_bytes,
+ * whatever n; a null array with n > 0 (d_names only when n_name_bytes > 0); n > 0xFFFFFFF0.
+ * d_work: wga_stat_rows_work_bytes(n) bytes of device memory, 8-byte aligned, shared by the two calls
+ * = 8 * (n + n / 1024 + 4): 8 bytes per row for its byte count, plus the scan's partial sums (32 bytes for n == 0). */
+typedef struct {
+  uint64_t ref_size, ref_start, query_size, query_start;   /* as printed */
+  uint64_t rname_off, qname_off;                            /* spans of d_names */
+  uint32_t rname_len, qname_len;
+} wga_stat_row_head;                                        /* 56 bytes */
+
+uint64_t wga_stat_rows_work_bytes(uint64_t n);
+int wga_stat_rows(wga_ctx*, uint32_t n, const uint8_t* d_names, uint64_t n_name_bytes,
+                  const wga_stat_row_head* d_heads, const wga_cigar_counts* d_counts,
+                  void* d_work, uint64_t* d_row_off /* n + 1, device */, uint64_t* total_bytes, uint8_t* d_out);
+
+/* the formatter alone, for tests: d_text[16 i ..] receives the text of the f32 with bit pattern d_bits[i], d_len[i] its length
+ * (at most 16; the bytes of d_text behind a text are left as they were).  NaN -> "NaN", +-inf -> "inf" / "-inf", +-0 -> "0.0" /
+ * "-0.0", anything else the shortest digits that read back as the same f32, the closest such to the value, laid out as
+ * ryu::Buffer::format does: with the digits' count len, the decimal exponent k of the last digit and kk = len + k
+ *   0 <= k && kk <= 13 : digits, k zeros, ".0"         0 < kk <= 13 : dddd.ddd
+ *   -6 < kk <= 0       : "0.", -kk zeros, digits       else         : d[.ddd]e<kk - 1>
+ * n == 0 is valid; WGA_E_INVALID_ARG: a null array with n > 0, n > 0xFFFFFFF0. */
+int wga_f32_text(wga_ctx*, uint64_t n, const uint32_t* d_bits, uint8_t* d_text, uint8_t* d_len);
+
 #ifdef __cplusplus
 }
 #endif

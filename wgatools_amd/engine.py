@@ -49,6 +49,10 @@ MAF2PAF_HEAD_DTYPE = np.dtype([("q", np.uint64, 3), ("t", np.uint64, 3), ("qname
 SPAN_ITEM_DTYPE = np.dtype([("dst", "<u8"), ("len", "<u8"), ("src", "<u8"), ("kind", "<u4"), ("pad", "<u4")])
 SPAN_FILL, SPAN_COPY_POOL, SPAN_COPY_TEXT, SPAN_HOLE = 0, 1, 2, 3
 PSEUDO_FRAME_TILE = 65536
+# K33 (include/wga_hip.h wga_stat_row_head)
+STAT_ROW_HEAD_DTYPE = np.dtype([("ref_size", "<u8"), ("ref_start", "<u8"), ("query_size", "<u8"), ("query_start", "<u8"),
+                                ("rname_off", "<u8"), ("qname_off", "<u8"), ("rname_len", "<u4"), ("qname_len", "<u4")])
+assert STAT_ROW_HEAD_DTYPE.itemsize == 56
 # K32 (include/wga_hip.h wga_maf_frame_head)
 MAF_FRAME_HEAD_DTYPE = np.dtype([("score", "<u8"), ("t", np.uint64, 3), ("q", np.uint64, 3), ("tname_off", "<u8"),
                                  ("qname_off", "<u8"), ("tname_len", "<u4"), ("qname_len", "<u4"), ("t_neg", np.uint8),
@@ -761,6 +765,58 @@ class Engine:
             raise _lib.WgaError("maf_records wrote outside d_out[0 .. total_bytes)")
         text = got[lead:lead + first].tobytes()
         return text[:int(gb.value)], int(good.value), text
+
+    def stat_rows_count(self, n, names, n_name_bytes, heads, counts, work, row_off):
+        """K33: the count call of wga_stat_rows alone, total_bytes; it leaves the rows' byte counts in `work` and their places in
+        row_off[n + 1]"""
+        total = C.c_uint64(0)
+        self._check(self.lib.wga_stat_rows(self.ctx, int(n), _p(names), int(n_name_bytes), _p(heads), _p(counts), _p(work),
+                                           _p(row_off), C.byref(total), None))
+        return int(total.value)
+
+    def stat_rows(self, n, names, n_name_bytes, heads, counts, work=None, out_shift=0):
+        """K33 (stat.rs:129-164): the TSV rows of `stat --each` for n records, both calls of wga_stat_rows on wga_cigar_stat's or
+        wga_maf_pair_stat's counters (or arrays of the same meaning) and the caller's heads (STAT_ROW_HEAD_DTYPE).  Returns
+        (text, row_off); the guard bytes in front of and behind the text are checked after the count call and after the fill.
+        work: a device buffer to use; out_shift: d_out starts that many bytes behind a 64-byte aligned address"""
+        n = int(n)
+        if work is None:
+            work = self.empty(max(int(self.lib.wga_stat_rows_work_bytes(n)), 16), np.uint8)
+        row_off = self.empty(n + 1, np.uint64)
+        args = (self.ctx, n, _p(names), int(n_name_bytes), _p(heads), _p(counts), _p(work), _p(row_off))
+        total = C.c_uint64(0)
+        self._check(self.lib.wga_stat_rows(*args, C.byref(total), None))
+        first = int(total.value)
+        guard = 64  # bytes around the text that the calls must leave alone
+        out = self.upload(np.full(first + 2 * guard + 96, 0xA5, dtype=np.uint8))
+        lead = guard + (-out.ptr) % 64 + int(out_shift)
+        self._check(self.lib.wga_stat_rows(*args, C.byref(total), out.ptr + lead))
+        self.sync()
+        if int(total.value) != first:
+            raise _lib.WgaError("wga_stat_rows changed its total in the second call")
+        got = out.numpy()
+        if not ((got[:lead] == 0xA5).all() and (got[lead + first:] == 0xA5).all()):
+            raise _lib.WgaError("wga_stat_rows wrote outside d_out[0 .. total_bytes)")
+        return got[lead:lead + first].tobytes(), (row_off.numpy().copy() if n else np.zeros(1, np.uint64))
+
+    def f32_text(self, bits):
+        """K33's formatter alone (wga_f32_text): the texts of the f32s with the bit patterns `bits` (uint32), a list of bytes.
+        The text buffer is filled with 0xA5 first: a text may not reach beyond its length"""
+        bits = np.ascontiguousarray(bits, dtype=np.uint32)
+        n = int(bits.size)
+        if n == 0:
+            self._check(self.lib.wga_f32_text(self.ctx, 0, None, None, None))
+            return []
+        d_bits = self.upload(bits)
+        d_text = self.upload(np.full(16 * n, 0xA5, dtype=np.uint8))
+        d_len = self.upload(np.full(n, 0xFF, dtype=np.uint8))
+        self._check(self.lib.wga_f32_text(self.ctx, n, _p(d_bits), _p(d_text), _p(d_len)))
+        self.sync()
+        text = d_text.numpy().reshape(n, 16)
+        ln = d_len.numpy()
+        if (ln > 16).any() or not (text[np.arange(16)[None, :] >= ln[:, None]] == 0xA5).all():
+            raise _lib.WgaError("wga_f32_text wrote behind a text's length")
+        return [text[i, :ln[i]].tobytes() for i in range(n)]
 
     def pafpseudo_frame(self, items, pool, pool_bytes, text, text_bytes, out, out_bytes, first_bad=None):
         """K31 (the rows of pseudomaf.rs:98-209 around the segments): writes every FILL / COPY span of `items` (SPAN_ITEM_DTYPE, a

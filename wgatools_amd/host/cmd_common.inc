@@ -1,7 +1,8 @@
 /* cmd_common.inc — part of wgatools_main.cpp (included there, inside its namespace, in front of the commands): what more than one
  * command does the same way.  The worker threads and devices of --gpus N, the single-device tokeniser + K1 step, the MAF input
- * and its rows on the device, K3's run list and the ops made of it, the heads the record writers take, and the host's text
- * around text the device writes (WGA_*_WRITER=host). */
+ * and its rows on the device, K3's run list and the ops made of it, the heads the record writers take, the host's text
+ * around text the device writes (WGA_*_WRITER=host), the download through the pinned buffers, and the rows of `stat --each`
+ * (K33's heads, the pieces' texts and their order). */
 /* one thread per device over fn(g); the first worker error (by device number) is rethrown on the caller's thread */
 static void on_devices(int ngpu, const std::function<void(int)>& fn) {
   std::vector<std::string> werr(ngpu);
@@ -68,19 +69,22 @@ static std::string bad_op_message(const CigarTexts& cigars, size_t k, const wga_
 }
 /* Records [0, n) of a piece on one device: tokeniser, then K1 over the records in front of the first tag / tokeniser error; their
  * counts come back.  Returns that error's message and sets op_err to the message for the first op K1 rejects ("" if none): which
- * of the two speaks, and how, is the command's. */
-static std::string paf_counts(Dev& d, const PafInput& pin, uint32_t n, std::vector<wga_cigar_counts>& counts, std::string& op_err) {
+ * of the two speaks, and how, is the command's.  on_device: the counts are not downloaded, *on_device is where they stand. */
+static std::string paf_counts(Dev& d, const PafInput& pin, uint32_t n, std::vector<wga_cigar_counts>& counts, std::string& op_err,
+                              const wga_cigar_counts** on_device = nullptr) {
   CigarTexts cigars;
   wga_cigar_batch cb;
   const std::string e = device_tokenise(d, pin, 0, n, cigars, &cb);
   const uint32_t m = cb.n;
+  if (on_device) *on_device = nullptr;
   if (m) {
     auto* d_counts = (wga_cigar_counts*)d.alloc((size_t)m * sizeof(wga_cigar_counts));
     auto* d_diag = (wga_rec_diag*)d.alloc((size_t)m * sizeof(wga_rec_diag));
     d.check(wga_cigar_stat(d.ctx, &cb, d_counts, d_diag, nullptr));
     std::vector<wga_rec_diag> diag(m);
     d.download(diag.data(), d_diag, m);
-    d.download(counts.data(), d_counts, m);
+    if (on_device) *on_device = d_counts; /* the counts stay where K1 left them (stat -e: K33 reads them there) */
+    else d.download(counts.data(), d_counts, m);
     for (uint32_t k = 0; k < m && op_err.empty(); k++)
       if (diag[k].bad_op_idx != WGA_NONE) op_err = bad_op_message(cigars, k, diag[k]);
   }
@@ -549,3 +553,123 @@ static void append_paf_columns(std::string& s, const std::string& q_name, uint64
     append_u64(s, v);
   }
 }
+
+/* n bytes of device memory behind `dst`: two pinned buffers, the copy of one slab runs while the one before it is appended */
+static void download_append(Dev& d, std::string& dst, const uint8_t* d_src, size_t n) {
+  if (n == 0) return;
+  if (!d.streamer) d.streamer.reset(new DevStreamer(d.ctx));
+  DevStreamer& st = *d.streamer;
+  for (int k = 0; k < 2; k++)
+    if (!st.buf[k] && wga_host_alloc(d.ctx, DevStreamer::kPiece, &st.buf[k])) fail(std::string("GPU engine: ") + wga_last_error());
+  dst.reserve(dst.size() + n);
+  const size_t kPiece = DevStreamer::kPiece, np = (n + kPiece - 1) / kPiece;
+  d.check(wga_memcpy_d2h_async(d.ctx, st.buf[0], d_src, std::min(kPiece, n)));
+  for (size_t p = 0; p < np; p++) {
+    d.check(wga_sync(d.ctx));
+    if (p + 1 < np) d.check(wga_memcpy_d2h_async(d.ctx, st.buf[(p + 1) & 1], d_src + (p + 1) * kPiece, std::min(kPiece, n - (p + 1) * kPiece)));
+    dst.append((const char*)st.buf[p & 1], std::min(kPiece, n - p * kPiece));
+  }
+}
+
+/* ---- stat --each on the device (K33, wga_stat_rows) ------------------------------------------------------------------------------
+ * WGA_STAT_WRITER=host: stat_tsv builds, sorts and prints a Statistic per record on one host thread, as before K33 (measurements,
+ * and the cross-check of the device writer: same bytes) */
+static bool stat_host_writer() { return env_is("WGA_STAT_WRITER", "host"); }
+
+/* the heads wga_stat_rows takes: a record's four numbers and where its two names stand (NameSpans) */
+struct StatRowHeads : NameSpans {
+  std::vector<wga_stat_row_head> heads;
+  explicit StatRowHeads(uint32_t n, const MafRows* p = nullptr) : NameSpans(p) { heads.reserve(n); }
+  void add(const std::string& ref_name, uint64_t ref_at, uint64_t ref_size, uint64_t ref_start, const std::string& query_name,
+           uint64_t query_at, uint64_t query_size, uint64_t query_start) {
+    wga_stat_row_head h;
+    h.ref_size = ref_size, h.ref_start = ref_start, h.query_size = query_size, h.query_start = query_start;
+    span(ref_name, ref_at, h.rname_off, h.rname_len);
+    span(query_name, query_at, h.qname_off, h.qname_len);
+    heads.push_back(h);
+  }
+};
+
+/* The rows of `stat --each` over all pieces.  A piece's rows are written on the device in input order and come back as one text
+ * with its row offsets; of a record the host keeps only the id of its distinct ref_name.  The rows leave sorted stably by the
+ * natural order of ref_name (stat.rs:104): the DISTINCT names are sorted with natord_compare, names that compare equal (natord
+ * skips white space: "c 1" and "c1") share a rank, and a stable counting sort on the rank orders the records — the order of a
+ * stable_sort over all records, for n log n fewer string comparisons. */
+struct StatRows {
+  std::vector<std::string> text;              /* per piece */
+  std::vector<std::vector<uint64_t>> row_off; /* per piece: n + 1 */
+  std::vector<uint32_t> name_id;              /* per record, over all pieces */
+  std::unordered_map<std::string, uint32_t> ids;
+  std::vector<const std::string*> distinct; /* the keys of `ids` (node addresses are stable) */
+  const std::string* last = nullptr;
+  uint32_t last_id = 0;
+  void note(const std::string& ref_name) {
+    if (!last || *last != ref_name) { /* neighbours mostly share their target */
+      auto it = ids.find(ref_name);
+      if (it == ids.end()) {
+        it = ids.emplace(ref_name, (uint32_t)distinct.size()).first;
+        distinct.push_back(&it->first);
+      }
+      last = &it->first;
+      last_id = it->second;
+    }
+    name_id.push_back(last_id);
+  }
+  /* the rows of the n records noted last, whose counts stand on d (device 0) */
+  void piece(Dev& d, StatRowHeads& hd, const wga_cigar_counts* d_counts) {
+    const uint32_t n = (uint32_t)hd.heads.size();
+    hd.upload_names(d);
+    const wga_stat_row_head* d_heads = d.upload(hd.heads);
+    void* d_work = d.alloc((size_t)wga_stat_rows_work_bytes(n));
+    auto* d_off = (uint64_t*)d.alloc(((size_t)n + 1) * 8);
+    uint64_t total = 0;
+    d.check(wga_stat_rows(d.ctx, n, hd.d_names, hd.n_name_bytes, d_heads, d_counts, d_work, d_off, &total, nullptr));
+    auto* d_out = (uint8_t*)d.alloc((size_t)total + 64);
+    if (total) d.check(wga_stat_rows(d.ctx, n, hd.d_names, hd.n_name_bytes, d_heads, d_counts, d_work, d_off, &total, d_out));
+    text.emplace_back();
+    download_append(d, text.back(), d_out, (size_t)total);
+    std::string offs; /* the offsets through the same pinned buffers */
+    download_append(d, offs, (const uint8_t*)d_off, ((size_t)n + 1) * 8);
+    row_off.emplace_back((size_t)n + 1);
+    memcpy(row_off.back().data(), offs.data(), offs.size());
+    g_timer.mark("stat rows (device)");
+  }
+  /* the header (only in front of a row: the csv writer prints it with the first record) and the rows in their order */
+  void write(Output& out) {
+    const size_t n_rows = name_id.size();
+    if (n_rows == 0) return;
+    const uint32_t nd = (uint32_t)distinct.size();
+    std::vector<uint32_t> order(nd), rank(nd);
+    for (uint32_t k = 0; k < nd; k++) order[k] = k;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return natord_compare(*distinct[a], *distinct[b]) < 0; });
+    uint32_t n_rank = 0;
+    for (uint32_t k = 0; k < nd; k++) {
+      if (k && natord_compare(*distinct[order[k - 1]], *distinct[order[k]]) < 0) n_rank++;
+      rank[order[k]] = n_rank;
+    }
+    n_rank++;
+    std::vector<size_t> at(n_rank + 1, 0); /* counting sort: where a rank's rows begin */
+    for (uint32_t id : name_id) at[rank[id] + 1]++;
+    for (uint32_t k = 0; k < n_rank; k++) at[k + 1] += at[k];
+    std::vector<uint64_t> rows(n_rows); /* piece << 32 | row in the piece */
+    size_t g = 0;
+    for (size_t p = 0; p < text.size(); p++)
+      for (size_t k = 0; k + 1 < row_off[p].size(); k++, g++) rows[at[rank[name_id[g]]]++] = (uint64_t)p << 32 | (uint64_t)k;
+    std::string buf =
+        "ref_name\tref_size\tref_start\tquery_name\tquery_size\tquery_start\taligned_size\t"
+        "unaligned_size\tidentity\tsimilarity\tmatched\tmismatched\tins_event\tdel_event\tins_size\t"
+        "del_size\tinv_event\tinv_size\tinv_ins_event\tinv_ins_size\tinv_del_event\tinv_del_size\n";
+    const size_t kFlush = (size_t)8 << 20;
+    buf.reserve(kFlush + 4096);
+    for (uint64_t r : rows) {
+      const size_t p = (size_t)(r >> 32), k = (size_t)(r & 0xFFFFFFFFu);
+      buf.append(text[p], (size_t)row_off[p][k], (size_t)(row_off[p][k + 1] - row_off[p][k]));
+      if (buf.size() >= kFlush) {
+        out.write(buf);
+        buf.clear();
+      }
+    }
+    out.write(buf);
+    g_timer.mark("stat rows gathered + written");
+  }
+};

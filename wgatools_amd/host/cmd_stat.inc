@@ -55,7 +55,50 @@ static void stat_piece_multi(std::vector<std::unique_ptr<Dev>>& devs, const PafI
       if (bad_at[g] == first_bad) fail(bad_msg[g]);
 }
 
+/* `stat -e` with the device writer (K33): per piece the counters stay on device 0 where K1 left them (--gpus N: they meet on the
+ * host as for the merged table and are uploaded there), the host fills one head per record, and the piece's rows come back as
+ * text (StatRows, cmd_common.inc).  Buffered driver: nothing is written before the last piece's records are counted. */
+static int stat_paf_rows_device(const std::string* input, Output& out) {
+  Dev d;
+  PafChunks chunks(input, false);
+  PafInput pin;
+  WorkerDevices wd(d); /* --gpus N */
+  StatRows rows;
+  while (chunks.next(d, pin)) {
+    const std::vector<PafRecord>& recs = pin.recs;
+    const uint32_t n = (uint32_t)recs.size();
+    d.init();
+    const wga_cigar_counts* d_counts = nullptr;
+    if (g_gpus > 1) {
+      std::vector<wga_cigar_counts> counts(n);
+      stat_piece_multi(wd.list(), pin, counts);
+      d_counts = d.upload(counts);
+    } else {
+      std::vector<wga_cigar_counts> none;
+      std::string op_err;
+      const std::string e = paf_counts(d, pin, n, none, op_err, &d_counts);
+      if (!op_err.empty()) fail(op_err);
+      if (!e.empty()) fail(e);
+    }
+    MafRows in_piece; /* the names are read in the uploaded piece where the device reader took it */
+    in_piece.d_rows = pin.d_text;
+    in_piece.names_in_rows = pin.on_device;
+    in_piece.n_row_bytes = pin.text.size();
+    StatRowHeads hd(n, &in_piece);
+    for (const PafRecord& r : recs) {
+      rows.note(r.target_name);
+      hd.add(r.target_name, r.tname_off, r.target_length, r.target_start, r.query_name, r.qname_off, r.query_length, r.query_start);
+    }
+    rows.piece(d, hd, d_counts);
+    d.release_all();
+  }
+  rows.write(out);
+  out.close();
+  return leave(0);
+}
+
 int cmd_stat_paf(const std::string* input, bool each, Output& out) {
+  if (each && !stat_host_writer()) return stat_paf_rows_device(input, out);
   Dev d;
   PafChunks chunks(input, false);
   std::vector<StatInput> in;
@@ -83,11 +126,56 @@ int cmd_stat_paf(const std::string* input, bool each, Output& out) {
     d.release_all();
   }
   out.write(stat_tsv(in, each));
+  if (each) g_timer.mark("stat rows (host)");
+  out.close();
+  return leave(0);
+}
+
+/* `stat -e` on MAF with the device writer: as stat_paf_rows_device, over K3's counters.  One device: they stay where K3 left them
+ * and the names are read in the uploaded piece; --gpus N: they arrive on the host and are uploaded to device 0 with the names. */
+static int stat_maf_rows_device(const std::string* input, const std::string* query_name, Output& out) {
+  Dev d;
+  MafDevices md(d);
+  MafChunks chunks(input);
+  MafInput min;
+  StatRows rows;
+  while (chunks.next(d, min)) {
+    std::vector<MafRecord>& recs = min.recs;
+    select_query(recs, query_name);
+    const uint32_t n = (uint32_t)recs.size();
+    if (n) {
+      for (const MafRecord& r : recs) rows.note(r.t().name);
+      auto heads = [&](StatRowHeads& hd) {
+        for (const MafRecord& r : recs)
+          hd.add(r.t().name, r.t().name_off, r.t().size, r.t().start, r.q().name, r.q().name_off, r.q().size, r.query_start());
+      };
+      std::vector<wga_cigar_counts> counts(md.count() > 1 ? n : 0);
+      md.run(min, all_records(recs), false, [&](int, Dev& dg, const MafRows& p, uint32_t lo, uint32_t cnt) {
+        const MafRuns R = maf_runs(dg, p, cnt, true);
+        if (md.count() > 1) {
+          dg.download(counts.data() + lo, R.d_counts, cnt);
+          return;
+        }
+        StatRowHeads hd(n, &p);
+        heads(hd);
+        rows.piece(dg, hd, R.d_counts);
+      });
+      if (md.count() > 1) {
+        d.init();
+        StatRowHeads hd(n);
+        heads(hd);
+        rows.piece(d, hd, d.upload(counts));
+      }
+    }
+    md.release_all();
+  }
+  rows.write(out);
   out.close();
   return leave(0);
 }
 
 int cmd_stat_maf(const std::string* input, bool each, const std::string* query_name, Output& out) {
+  if (each && !stat_host_writer()) return stat_maf_rows_device(input, query_name, out);
   Dev d;
   MafDevices md(d);
   MafChunks chunks(input);
@@ -112,6 +200,7 @@ int cmd_stat_maf(const std::string* input, bool each, const std::string* query_n
     md.release_all();
   }
   out.write(stat_tsv(in, each));
+  if (each) g_timer.mark("stat rows (host)");
   out.close();
   return leave(0);
 }

@@ -15,22 +15,6 @@ struct ValidateAcc {
 static bool validate_fix_host_forced() {
   return env_is("WGA_VALIDATE_WRITER", "host") || env_is("WGA_PAF_READER", "host");
 }
-/* n bytes of device memory behind `dst`: two pinned buffers, the copy of one slab runs while the one before it is appended */
-static void download_append(Dev& d, std::string& dst, const uint8_t* d_src, size_t n) {
-  if (n == 0) return;
-  if (!d.streamer) d.streamer.reset(new DevStreamer(d.ctx));
-  DevStreamer& st = *d.streamer;
-  for (int k = 0; k < 2; k++)
-    if (!st.buf[k] && wga_host_alloc(d.ctx, DevStreamer::kPiece, &st.buf[k])) fail(std::string("GPU engine: ") + wga_last_error());
-  dst.reserve(dst.size() + n);
-  const size_t kPiece = DevStreamer::kPiece, np = (n + kPiece - 1) / kPiece;
-  d.check(wga_memcpy_d2h_async(d.ctx, st.buf[0], d_src, std::min(kPiece, n)));
-  for (size_t p = 0; p < np; p++) {
-    d.check(wga_sync(d.ctx));
-    if (p + 1 < np) d.check(wga_memcpy_d2h_async(d.ctx, st.buf[(p + 1) & 1], d_src + (p + 1) * kPiece, std::min(kPiece, n - (p + 1) * kPiece)));
-    dst.append((const char*)st.buf[p & 1], std::min(kPiece, n - p * kPiece));
-  }
-}
 /* one piece on the device.  False, with nothing left on the device and `acc` as it was: the piece is the host path's. */
 static bool validate_fix_device(Dev& d, std::string& text, ValidateAcc& acc) {
   if (validate_fix_host_forced() || text.empty() || text.size() >= 0xFFFFFFF0ull) return false;

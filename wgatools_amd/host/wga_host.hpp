@@ -92,6 +92,7 @@ struct PafRecord { /* paf.rs:50-65 */
   uint64_t target_length = 0, target_start = 0, target_end = 0;
   uint64_t matches = 0, block_length = 0, mapq = 0;
   std::vector<std::string> tags;
+  uint64_t qname_off = 0, tname_off = 0; /* the names' offsets in the piece (device splitter only) */
 };
 /* csv-crate reading: records end at \n, \r\n or \r; empty lines and lines starting with '#' are
  * skipped; fields split on tabs with '"' quoting. */

@@ -725,6 +725,7 @@ PafInput paf_from_text(Dev& d, std::string&& text, bool want_tags, uint64_t rec0
         PafRecord r;
         r.query_name.assign(in.text, (size_t)L.qname_off, L.qname_len);
         r.target_name.assign(in.text, (size_t)L.tname_off, L.tname_len);
+        r.qname_off = L.qname_off, r.tname_off = L.tname_off;
         r.query_length = L.num[0];
         r.query_start = L.num[1];
         r.query_end = L.num[2];
