@@ -1130,6 +1130,50 @@ int wga_stat_rows(wga_ctx*, uint32_t n, const uint8_t* d_names, uint64_t n_name_
  * n == 0 is valid; WGA_E_INVALID_ARG: a null array with n > 0, n > 0xFFFFFFF0. */
 int wga_f32_text(wga_ctx*, uint64_t n, const uint32_t* d_bits, uint8_t* d_text, uint8_t* d_len);
 
+/* ---- K34: `dotplot -m overview` — the csv rows (replaces the per-record loop of dotplot_rows, wgatools_amd/host/cmd_dotplot.inc:
+ *      the counters downloaded, then four integers, one f64 and two quoted names per row from one CPU thread; in the reference
+ *      rec_dot_data tools/dotplot.rs:384-423 through the csv writer of render_output) ------------------------------------------
+ * d_counts[n] are wga_cigar_stat's or wga_maf_pair_stat's counters; d_heads[n] the four numbers AS PRINTED (the caller has
+ * swapped the query pair of a `-` record), the divisor and the spans of the two names inside d_names[0 .. n_name_bytes).
+ * Row r, in input order, is ONE line of 7 columns, commas between them:
+ *   <ref_start>,<ref_end>,<q_first>,<q_second>,<identity>,<ref_chro>,<query_chro>\n
+ *   identity = (double)d_counts[r].match / (double)align_size
+ * u64 -> f64 rounds to nearest even and the division is the IEEE double precision one: 0 / 0 prints "NaN", x / 0 "inf".  With
+ * no_identity != 0 the column is the literal "1.0", d_counts may be NULL and nothing is read from it.  Integers are printed in
+ * canonical decimal.  A name is written as the csv writer does under QuoteStyle::Necessary with a comma delimiter (as it is,
+ * unless it holds a comma, a quote, CR or LF: then between quotes, every quote inside doubled); a name whose span does not lie
+ * inside d_names is written as empty.  An f64 is written as ryu does (wga_f64_text below).
+ *   d_out == NULL: the byte count of every row (d_work), d_row_off[n + 1] (device memory; d_row_off[n] = the text's length)
+ *                  and *total_bytes (a host value; the call synchronises).
+ *   otherwise    : the text at d_out[0 .. *total_bytes).  d_out may have any alignment, the caller leaves 16 bytes of slack
+ *                  behind the text; no byte in front of d_out and none from d_out + *total_bytes on is written.  *total_bytes,
+ *                  d_work and d_row_off are read as the first call left them, so the two calls take the same arguments.  A row
+ *                  whose span in d_row_off is not its byte count in d_work is not written.
+ * All places are 64-bit.  n == 0: *total_bytes = 0, nothing is written.  WGA_E_INVALID_ARG: a null d_work or total_bytes,
+ * whatever n; a null array with n > 0 (d_counts only when !no_identity, d_names only when n_name_bytes > 0); n > 0xFFFFFFF0.
+ * d_work: wga_dotplot_overview_work_bytes(n) bytes of device memory, 8-byte aligned, shared by the two calls
+ * = 8 * (n + n / 1024 + 4): 8 bytes per row for its byte count, plus the scan's partial sums (32 bytes for n == 0). */
+typedef struct {
+  uint64_t ref_start, ref_end, q_first, q_second;          /* as printed */
+  uint64_t align_size;                                      /* the divisor of identity */
+  uint64_t rname_off, qname_off;                            /* spans of d_names */
+  uint32_t rname_len, qname_len;
+} wga_dotplot_ov_head;                                      /* 64 bytes */
+
+uint64_t wga_dotplot_overview_work_bytes(uint64_t n);
+int wga_dotplot_overview(wga_ctx*, uint32_t n, const uint8_t* d_names, uint64_t n_name_bytes,
+                         const wga_dotplot_ov_head* d_heads, const wga_cigar_counts* d_counts, int no_identity,
+                         void* d_work, uint64_t* d_row_off /* n + 1, device */, uint64_t* total_bytes, uint8_t* d_out);
+
+/* the formatter alone, for tests: d_text[32 i ..] receives the text of the f64 with bit pattern d_bits[i], d_len[i] its length
+ * (at most 24; the bytes of d_text behind a text are left as they were).  NaN -> "NaN", +-inf -> "inf" / "-inf", +-0 -> "0.0" /
+ * "-0.0", anything else the shortest digits that read back as the same f64, the closest such to the value, laid out as
+ * ryu::Buffer::format does: with the digits' count len, the decimal exponent k of the last digit and kk = len + k
+ *   0 <= k && kk <= 16 : digits, k zeros, ".0"         0 < kk <= 16 : dddd.ddd
+ *   -5 < kk <= 0       : "0.", -kk zeros, digits       else         : d[.ddd]e<kk - 1>
+ * n == 0 is valid; WGA_E_INVALID_ARG: a null array with n > 0, n > 0xFFFFFFF0. */
+int wga_f64_text(wga_ctx*, uint64_t n, const uint64_t* d_bits, uint8_t* d_text /* 32 n bytes */, uint8_t* d_len);
+
 #ifdef __cplusplus
 }
 #endif

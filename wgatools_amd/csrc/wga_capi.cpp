@@ -56,6 +56,7 @@
 #include "wga_k31_pseudo_frame.h" /* K31: the row frame writer of pafpseudo */
 #include "wga_k32_maf_frame.h" /* K32: the MAF record frames of paf2maf and chain2maf */
 #include "wga_k33_stat_rows.h" /* K33: the TSV rows of stat --each, the f32 text */
+#include "wga_k34_dotplot_overview.h" /* K34: the csv rows of dotplot -m overview, the f64 text */
 
 /* A grow-only device buffer of a context.  reserve() leaves it with room for `need` bytes: one that is too small is freed
  * behind the work of the context's stream and allocated anew with `grow` (>= need) bytes — every site has its own growth rule —,
@@ -603,6 +604,7 @@ int wga_ctx_get_param(wga_ctx* c, const char* name, int64_t* value) {
 #include "capi_pafpseudo_frame.inc"
 #include "capi_maf_frame.inc"
 #include "capi_stat_rows.inc"
+#include "capi_dotplot_overview.inc"
 #include "capi_dotplot_csv.inc"
 #include "capi_pafcov.inc"
 #include "capi_pafpseudo.inc"

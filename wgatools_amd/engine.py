@@ -53,6 +53,11 @@ PSEUDO_FRAME_TILE = 65536
 STAT_ROW_HEAD_DTYPE = np.dtype([("ref_size", "<u8"), ("ref_start", "<u8"), ("query_size", "<u8"), ("query_start", "<u8"),
                                 ("rname_off", "<u8"), ("qname_off", "<u8"), ("rname_len", "<u4"), ("qname_len", "<u4")])
 assert STAT_ROW_HEAD_DTYPE.itemsize == 56
+# K34 (include/wga_hip.h wga_dotplot_ov_head)
+DOTPLOT_OV_HEAD_DTYPE = np.dtype([("ref_start", "<u8"), ("ref_end", "<u8"), ("q_first", "<u8"), ("q_second", "<u8"),
+                                  ("align_size", "<u8"), ("rname_off", "<u8"), ("qname_off", "<u8"), ("rname_len", "<u4"),
+                                  ("qname_len", "<u4")])
+assert DOTPLOT_OV_HEAD_DTYPE.itemsize == 64
 # K32 (include/wga_hip.h wga_maf_frame_head)
 MAF_FRAME_HEAD_DTYPE = np.dtype([("score", "<u8"), ("t", np.uint64, 3), ("q", np.uint64, 3), ("tname_off", "<u8"),
                                  ("qname_off", "<u8"), ("tname_len", "<u4"), ("qname_len", "<u4"), ("t_neg", np.uint8),
@@ -817,6 +822,56 @@ class Engine:
         if (ln > 16).any() or not (text[np.arange(16)[None, :] >= ln[:, None]] == 0xA5).all():
             raise _lib.WgaError("wga_f32_text wrote behind a text's length")
         return [text[i, :ln[i]].tobytes() for i in range(n)]
+
+    def dotplot_overview(self, n, names, n_name_bytes, heads, counts, no_identity=False, work=None, out_shift=0):
+        """K34 (dotplot.rs:384-423): the csv rows of `dotplot -m overview` for n records, both calls of wga_dotplot_overview on
+        wga_cigar_stat's or wga_maf_pair_stat's counters (or an array of the same meaning; None under no_identity) and the
+        caller's heads (DOTPLOT_OV_HEAD_DTYPE).  Returns (text, row_off); the guard bytes in front of and behind the text are
+        checked after the count call and after the fill.
+        work: a device buffer to use; out_shift: d_out starts that many bytes behind a 64-byte aligned address"""
+        n = int(n)
+        if work is None:
+            work = self.empty(max(int(self.lib.wga_dotplot_overview_work_bytes(n)), 16), np.uint8)
+        row_off = self.empty(n + 1, np.uint64)
+        args = (self.ctx, n, _p(names), int(n_name_bytes), _p(heads), _p(counts), 1 if no_identity else 0, _p(work), _p(row_off))
+        total = C.c_uint64(0)
+        guard = 64  # bytes around the text that the calls must leave alone
+        self._check(self.lib.wga_dotplot_overview(*args, C.byref(total), None))
+        first = int(total.value)
+        out = self.upload(np.full(first + 2 * guard + 96, 0xA5, dtype=np.uint8))
+        lead = guard + (-out.ptr) % 64 + int(out_shift)
+        self._check(self.lib.wga_dotplot_overview(*args, C.byref(total), out.ptr + lead))
+        self.sync()
+        if int(total.value) != first:
+            raise _lib.WgaError("wga_dotplot_overview changed its total in the second call")
+        got = out.numpy()
+        if not ((got[:lead] == 0xA5).all() and (got[lead + first:] == 0xA5).all()):
+            raise _lib.WgaError("wga_dotplot_overview wrote outside d_out[0 .. total_bytes)")
+        return got[lead:lead + first].tobytes(), (row_off.numpy().copy() if n else np.zeros(1, np.uint64))
+
+    def f64_text(self, bits):
+        """K34's formatter alone (wga_f64_text): the texts of the f64s with the bit patterns `bits` (uint64), a list of bytes.
+        The text buffer is filled with 0xA5 first: a text may not reach beyond its length"""
+        bits = np.ascontiguousarray(bits, dtype=np.uint64)
+        n = int(bits.size)
+        if n == 0:
+            self._check(self.lib.wga_f64_text(self.ctx, 0, None, None, None))
+            return []
+        d_bits = self.upload(bits)
+        d_text = self.upload(np.full(32 * n, 0xA5, dtype=np.uint8))
+        d_len = self.upload(np.full(n, 0xFF, dtype=np.uint8))
+        self._check(self.lib.wga_f64_text(self.ctx, n, _p(d_bits), _p(d_text), _p(d_len)))
+        self.sync()
+        text = d_text.numpy().reshape(n, 32)
+        ln = d_len.numpy()
+        if (ln > 24).any() or not (text[np.arange(32)[None, :] >= ln[:, None]] == 0xA5).all():
+            raise _lib.WgaError("wga_f64_text wrote behind a text's length")
+        flat, at = text.tobytes(), 0
+        out = []
+        for k in ln.tolist():
+            out.append(flat[at:at + k])
+            at += 32
+        return out
 
     def pafpseudo_frame(self, items, pool, pool_bytes, text, text_bytes, out, out_bytes, first_bad=None):
         """K31 (the rows of pseudomaf.rs:98-209 around the segments): writes every FILL / COPY span of `items` (SPAN_ITEM_DTYPE, a

@@ -3,7 +3,10 @@
 /* ---- dotplot --out-format csv (tools/dotplot.rs; SURVEY.md 8f rank 4) -----------------------------------
  * base-level: segments from wga_cigar_dotplot (PAF: device tokeniser; MAF: K3 runs -> wga_maf_runs_ops), their rows
  * written on the device (K26) unless WGA_DOTPLOT_WRITER=host;
- * overview: one row per record, identity = matched / target_align_size from K1 / K3.  All data is generated
+ * overview: one row per record, identity = matched / target_align_size from K1 / K3, written on the device (K34,
+ * wga_dotplot_overview) where the counters lie unless WGA_DOTPLOT_WRITER=host: only K1's diagnostics and the text come back.
+ * With -d on PAF nothing is tokenised and K34 writes "1.0"; with -d on MAF no device holds anything of the blocks, and the rows
+ * stay the host's loop (an upload of the names would be all the device got).  All data is generated
  * before anything is written (:208-262), so an error leaves the output empty.  The html / json outputs embed
  * the reference's Vega-Lite document and are not provided. */
 /* the records of one device's share of a piece, as the csv rows need them */
@@ -22,7 +25,8 @@ struct DotRecs {
     ali.push_back(a);
   }
 };
-/* WGA_DOTPLOT_WRITER=host: the base-level rows are printed on the host from the downloaded segments (measurements) */
+/* WGA_DOTPLOT_WRITER=host: the rows are printed on the host from the downloaded segments / counters (measurements, and the
+ * cross-check of the device writers: same bytes) */
 static bool dotplot_host_writer() { return env_is("WGA_DOTPLOT_WRITER", "host"); }
 /* csv rows (no header line) of the records R: base-level segments from wga_cigar_dotplot over the device batch cb, written as
  * text on the device (K26, wga_dotplot_csv), or one overview row per record from the counts */
@@ -99,9 +103,98 @@ static std::string dotplot_rows(Dev& d, bool base, bool no_identity, uint64_t cu
   }
   return text;
 }
+/* ---- overview on the device (K34) ---------------------------------------------------------------------------------------------
+ * the heads wga_dotplot_overview takes: a record's four numbers as printed, the divisor and where its two names stand */
+struct DotOvHeads : NameSpans {
+  std::vector<wga_dotplot_ov_head> heads;
+  explicit DotOvHeads(uint32_t n, const MafRows* p = nullptr) : NameSpans(p) { heads.reserve(n); }
+  void add(const std::string& t_name, uint64_t t_at, const std::string& q_name, uint64_t q_at, uint64_t ts, uint64_t te, uint64_t qs,
+           uint64_t qe, bool neg, uint64_t ali) {
+    wga_dotplot_ov_head h;
+    h.ref_start = ts, h.ref_end = te;
+    h.q_first = neg ? qe : qs, h.q_second = neg ? qs : qe; /* dotplot.rs:400-406 */
+    h.align_size = ali;
+    span(t_name, t_at, h.rname_off, h.rname_len);
+    span(q_name, q_at, h.qname_off, h.qname_len);
+    heads.push_back(h);
+  }
+};
+/* a range's rows can be K34's */
+static bool dotplot_overview_on_device(size_t n) { return !dotplot_host_writer() && n <= 0xFFFFFFF0ull; }
+/* the rows of the records of hd, whose counters stand on d (nullptr: no_identity), as text */
+static std::string dotplot_overview_rows(Dev& d, DotOvHeads& hd, const wga_cigar_counts* d_counts) {
+  std::string text;
+  const uint32_t n = (uint32_t)hd.heads.size();
+  if (n == 0) return text;
+  hd.upload_names(d);
+  const wga_dotplot_ov_head* d_heads = d.upload(hd.heads);
+  void* d_work = d.alloc((size_t)wga_dotplot_overview_work_bytes(n));
+  auto* d_off = (uint64_t*)d.alloc(((size_t)n + 1) * 8);
+  const int no_identity = d_counts ? 0 : 1;
+  uint64_t total = 0;
+  d.check(wga_dotplot_overview(d.ctx, n, hd.d_names, hd.n_name_bytes, d_heads, d_counts, no_identity, d_work, d_off, &total, nullptr));
+  if (total == 0) return text;
+  auto* d_out = (uint8_t*)d.alloc((size_t)total + 64);
+  d.check(wga_dotplot_overview(d.ctx, n, hd.d_names, hd.n_name_bytes, d_heads, d_counts, no_identity, d_work, d_off, &total, d_out));
+  download_append(d, text, d_out, (size_t)total);
+  return text;
+}
+/* records [lo, hi) of a PAF piece: the counters stay where K1 left them, only the diagnostics come back; the names are read in
+ * the uploaded piece where the device reader took it */
+static std::string dotplot_paf_overview(Dev& d, const PafInput& pin, size_t lo, size_t hi, const uint8_t* d_text_here, bool no_identity,
+                                        std::string& err) {
+  const uint32_t n = (uint32_t)(hi - lo);
+  if (n == 0) return std::string();
+  d.init();
+  const wga_cigar_counts* d_counts = nullptr;
+  if (!no_identity) {
+    CigarTexts cigars;
+    wga_cigar_batch cb;
+    err = device_tokenise(d, pin, lo, n, cigars, &cb, nullptr, nullptr, d_text_here);
+    if (cb.n) { /* get_stat (paf.rs:205-209): ops outside M = X I D are an error */
+      auto* d_cnt = (wga_cigar_counts*)d.alloc((size_t)cb.n * sizeof(wga_cigar_counts));
+      auto* d_diag = (wga_rec_diag*)d.alloc((size_t)cb.n * sizeof(wga_rec_diag));
+      d.check(wga_cigar_stat(d.ctx, &cb, d_cnt, d_diag, nullptr));
+      std::vector<wga_rec_diag> diag(cb.n);
+      d.download(diag.data(), d_diag, cb.n);
+      for (uint32_t k = 0; k < cb.n; k++)
+        if (diag[k].bad_op_idx != WGA_NONE) {
+          err = bad_op_message(cigars, k, diag[k]);
+          break;
+        }
+      d_counts = d_cnt;
+    }
+    if (!err.empty() || cb.n != n) return std::string();
+  }
+  MafRows in_piece;
+  in_piece.d_rows = d_text_here ? d_text_here : pin.d_text;
+  in_piece.names_in_rows = pin.on_device;
+  in_piece.n_row_bytes = pin.text.size();
+  DotOvHeads hd(n, &in_piece);
+  for (size_t k = lo; k < hi; k++) {
+    const PafRecord& r = pin.recs[k];
+    hd.add(r.target_name, r.tname_off, r.query_name, r.qname_off, r.target_start, r.target_end, r.query_start, r.query_end, r.neg,
+           r.target_end - r.target_start);
+  }
+  return dotplot_overview_rows(d, hd, d_counts);
+}
+/* blocks recs[0 .. n) of a MAF piece, whose rows stand on device d (p): the counters stay where K3 left them */
+static std::string dotplot_maf_overview(Dev& d, const MafRows& p, const MafRecord* const* recs, uint32_t n) {
+  if (n == 0) return std::string();
+  const MafRuns runs = maf_runs(d, p, n, true);
+  DotOvHeads hd(n, &p);
+  for (uint32_t k = 0; k < n; k++) {
+    const MafRecord& r = *recs[k];
+    hd.add(r.t().name, r.t().name_off, r.q().name, r.q().name_off, r.t().start, r.t().start + r.t().align_size, r.query_start(),
+           r.query_end(), r.q().neg, r.t().align_size);
+  }
+  return dotplot_overview_rows(d, hd, runs.d_counts);
+}
+
 /* records [lo, hi) of a PAF piece on device d; `err` = the reference's message for the first failing record of the range */
 static std::string dotplot_paf_part(Dev& d, const PafInput& pin, size_t lo, size_t hi, const uint8_t* d_text_here, bool base,
                                     bool no_identity, uint64_t cutoff, std::string& err) {
+  if (!base && dotplot_overview_on_device(hi - lo)) return dotplot_paf_overview(d, pin, lo, hi, d_text_here, no_identity, err);
   DotRecs R;
   for (size_t k = lo; k < hi; k++) {
     const PafRecord& r = pin.recs[k];
@@ -136,6 +229,7 @@ static std::string dotplot_paf_part(Dev& d, const PafInput& pin, size_t lo, size
 /* blocks recs[0 .. n) of a MAF piece, whose rows stand on device d (p) */
 static std::string dotplot_maf_part(Dev& d, const MafRows& p, const MafRecord* const* recs, uint32_t n, bool base, bool no_identity,
                                     uint64_t cutoff) {
+  if (!base && !no_identity && dotplot_overview_on_device(n)) return dotplot_maf_overview(d, p, recs, n);
   DotRecs R;
   for (uint32_t k = 0; k < n; k++) {
     const MafRecord& r = *recs[k];
@@ -167,8 +261,9 @@ int cmd_dotplot(const std::string* input, const std::string& format, const std::
   }
   if (format != "maf" && format != "paf") fail("Only support MAF and PAF format");
   const bool base = mode == "base-level";
-  /* WGA_TIMING=1 names the writer of the rows; the overview rows are always the host's */
-  const char* const rows_phase = base && !dotplot_host_writer() ? "dotplot rows (device)" : "dotplot rows (host)";
+  /* WGA_TIMING=1 names the writer of the rows; the overview rows of a MAF under -d are always the host's */
+  const bool device_rows = !dotplot_host_writer() && (base || format == "paf" || !no_identity);
+  const char* const rows_phase = device_rows ? "dotplot rows (device)" : "dotplot rows (host)";
   std::string text; /* all data is generated before anything is written (dotplot.rs:208-262) */
   uint64_t n_records = 0;
   Dev d;
