@@ -1,10 +1,14 @@
 #!/usr/bin/env python3
-"""kernel_isa_diff.py REV — is the device code of every kernel the same as at commit REV?
+"""kernel_isa_diff.py REV [--rename OLD=NEW ...] — is the device code of every kernel the same as at commit REV?
 
 Builds the gfx950 device assembly of wgatools_amd/csrc/wga_capi.cpp twice, for the working tree and for REV (taken with
 `git archive` into a temporary directory), with build_hip's flags plus --cuda-device-only -S, cuts both files into kernels
 (entry label to .Lfunc_end, plus the kernel's .amdhsa_kernel ... .end_amdhsa_kernel block: registers, LDS, scratch), strips
 `;` comments and the function number inside local labels, and compares the texts kernel by kernel.
+
+--rename OLD=NEW (repeatable): the kernel called OLD at REV is called NEW in the working tree (each a symbol of the assembly,
+or a part of a name that only one kernel on its side has); it is compared after OLD is replaced by NEW throughout its text.  Of
+a kernel whose text differs, the line counts and the descriptor's registers, LDS and scratch are printed for both sides.
 
 It compares text only, looks for no particular instruction and runs nothing on a GPU.  For a pull request that only moves
 source between files it stands in for a per-kernel timing: the same instructions under the same launch geometry.
@@ -62,10 +66,32 @@ def kernels(asm):
     return {n: "\n".join(t) for n, t in out.items()}
 
 
+def unique(part, names, side):
+    hit = [part] if part in names else [n for n in names if part in n]
+    if len(hit) != 1:
+        sys.exit("--rename: %r names %d kernels %s" % (part, len(hit), side))
+    return hit[0]
+
+
+def resources(text):
+    """the descriptor's registers, LDS and scratch, and the number of lines"""
+    keys = (".amdhsa_next_free_vgpr", ".amdhsa_next_free_sgpr", ".amdhsa_group_segment_fixed_size",
+            ".amdhsa_private_segment_fixed_size")
+    got = dict(l.split()[:2] for l in text.split("\n") if l.split() and l.split()[0] in keys)
+    return "  ".join("%s %s" % (k[len(".amdhsa_"):], got.get(k, "?")) for k in keys) + "  lines %d" % (text.count("\n") + 1)
+
+
 def main():
-    if len(sys.argv) != 2:
+    argv, renames = [], []
+    args = iter(sys.argv[1:])
+    for a in args:
+        if a == "--rename":
+            renames.append(next(args, "").split("=", 1))
+        else:
+            argv.append(a)
+    if len(argv) != 1 or any(len(r) != 2 for r in renames):
         sys.exit(__doc__)
-    rev = subprocess.run(["git", "-C", ROOT, "rev-parse", sys.argv[1]], check=True, stdout=subprocess.PIPE,
+    rev = subprocess.run(["git", "-C", ROOT, "rev-parse", argv[0]], check=True, stdout=subprocess.PIPE,
                          text=True).stdout.strip()
     head = subprocess.run(["git", "-C", ROOT, "rev-parse", "HEAD"], check=True, stdout=subprocess.PIPE,
                           text=True).stdout.strip()
@@ -79,6 +105,10 @@ def main():
         subprocess.run(["tar", "-x", "-C", old_tree], input=tar, check=True)
         old = kernels(device_asm(old_tree, os.path.join(tmp, "rev.s")))
         new = kernels(device_asm(ROOT, os.path.join(tmp, "tree.s")))
+    for a, b in renames:
+        a, b = unique(a, old, "at the reference"), unique(b, new, "in the working tree")
+        old[b] = old.pop(a).replace(a, b)
+        print("renamed       %s -> %s" % (a, b))
     print("reference     %s" % rev)
     print("working tree  %s%s" % (head, " + uncommitted changes" if dirty else ""))
     print("kernels       %d in the reference, %d in the working tree" % (len(old), len(new)))
@@ -89,6 +119,9 @@ def main():
         print("%-24s %d" % (title + ":", len(names)))
         for n in names:
             print("    " + n)
+            if names is differ:
+                print("        reference     " + resources(old[n]))
+                print("        working tree  " + resources(new[n]))
     ok = not (only_old or only_new or differ)
     print("verdict       %s" % ("device code unchanged" if ok else "DEVICE CODE DIFFERS"))
     return 0 if ok else 1

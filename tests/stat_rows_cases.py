@@ -13,6 +13,7 @@ import numpy as np
 import maf2paf_cases as m2p
 import oracle_py as orc
 import stat_rows_ref as ref
+import text_items_cases as ti
 from chain_split_cases import run, write
 from wgatools_amd.engine import COUNTS_DTYPE, STAT_ROW_HEAD_DTYPE
 
@@ -115,9 +116,9 @@ class Raw:
         self.row_off = eng.upload(np.full(a.n + 1 + 8, 0xA5A5A5A5A5A5A5A5, dtype=np.uint64))
         self.total = None
 
-    def call(self, out_ptr):
+    def call(self, out_ptr, total=None):
         n, names, nb, heads, cnt = self.a.args()
-        tot = C.c_uint64(self.total if self.total is not None else 7)
+        tot = C.c_uint64(total if total is not None else self.total if self.total is not None else 7)
         rc = self.eng.lib.wga_stat_rows(self.eng.ctx, n, names.ptr, nb, heads.ptr, cnt.ptr, self.work.ptr, self.row_off.ptr,
                                         C.byref(tot), out_ptr)
         self.eng.sync()
@@ -323,6 +324,29 @@ def check_abi_arguments(eng):
     y = Raw(eng, b, work=x.work)
     y.count(400)
     assert y.fill(3) == b"".join(want_rows(b.recs))
+
+
+def item_stream(eng):
+    """600 rows, three blocks of the fill (the smallest count with a block wholly in front of an altered total and one behind
+    it), behind their count call; the scan of the row sizes is the caller's d_row_off"""
+    recs = some(600, 3)
+    a = Arrays(eng, recs)
+    x = Raw(eng, a)
+    want = b"".join(want_rows(recs))
+    assert x.count(len(want)) == len(want)
+
+    def fill(total_bytes, d_out):
+        assert x.call(d_out, total=total_bytes) == total_bytes
+    return ti.Stream(eng, x.row_off, 0, 600, want, fill)
+
+
+def check_abi_fill_short_total(eng):
+    ti.check_short_total(item_stream(eng))
+
+
+def check_abi_fill_scan_one_off(eng):
+    """a d_row_off altered between the calls: kCheckSize keeps the two rows around the altered entry unwritten"""
+    ti.check_scan_one_off(item_stream(eng), size_checked=True)
 
 
 def random_recs(seed):

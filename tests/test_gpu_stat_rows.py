@@ -55,6 +55,14 @@ def test_stat_rows_abi_arguments(eng):
     k33.check_abi_arguments(eng)
 
 
+def test_stat_rows_abi_fill_short_total(eng):
+    k33.check_abi_fill_short_total(eng)
+
+
+def test_stat_rows_abi_fill_row_off_altered(eng):
+    k33.check_abi_fill_scan_one_off(eng)
+
+
 @pytest.mark.parametrize("lo", range(0, 12, 3))
 def test_stat_rows_abi_random_batches(eng, lo):
     k33.check_abi_random(eng, range(lo, lo + 3))

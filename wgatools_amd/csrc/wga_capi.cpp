@@ -262,6 +262,40 @@ static int run_text_items_fill(wga_ctx* c, const F& f, u32 n, const u64* isc, u6
   LAUNCH_CHECK();
   return WGA_OK;
 }
+/* Both calls of a text of one row per record (RECORD ROWS in wga_text_out.h: K33, K34) behind the entry's own argument checks;
+ * the row source's fields of f are the entry's.  d_work in u64 words, n rows: the plan (a row's bytes) [n] | the scan's partials
+ * [n / 1024 + 4].  The count call (d_out null) plans, scans into d_row_off[n + 1] and reads the total back; the fill call writes
+ * the text. */
+static size_t record_rows_work_words(uint64_t n) { return (size_t)n + (size_t)(n / 1024u) + 4; }
+template <typename F>
+static int run_record_rows(wga_ctx* c, F f, u32 n, void* d_work, uint64_t* d_row_off, uint64_t* total_bytes, uint8_t* d_out) {
+  if (!d_out) *total_bytes = 0;
+  if (n == 0 || (d_out && *total_bytes == 0)) return WGA_OK;
+  u64* plan = (u64*)d_work;
+  f.plan = plan;
+  f.n_rec = n;
+  if (d_out) return run_text_items_fill(c, f, n, (const u64*)d_row_off, (u64)*total_bytes, d_out);
+  WGA_LAUNCH(k_record_rows_plan<typename F::Src>, (u32)(((u64)n + 255u) / 256u), WGA_BLOCK, c->stream, f.names, f.n_name_bytes, f.heads, n, f.counts, plan);
+  LAUNCH_CHECK();
+  int rc = run_scan_ws(c, ScanItems<F>{f}, n, (u64*)d_row_off, plan + n);
+  if (rc) return rc;
+  u64 tot = 0;
+  RT_CHECK(rt_d2h(&tot, d_row_off + n, sizeof tot, c->stream));
+  *total_bytes = tot;
+  return WGA_OK;
+}
+/* A formatter alone (k_bits_text: K33's f32, K34's f64) */
+template <typename B, u32 kSlot, void (*kEmit)(TextPut&, B)>
+static int run_bits_text(wga_ctx* c, uint64_t n, const B* d_bits, uint8_t* d_text, uint8_t* d_len) {
+  int rc = ctx_bind(c);
+  if (rc) return rc;
+  if (n == 0) return WGA_OK;
+  if (!d_bits || !d_text || !d_len) return fail(WGA_E_INVALID_ARG, "null array", nullptr);
+  if (n > 0xFFFFFFF0ull) return fail(WGA_E_INVALID_ARG, "too many values", nullptr);
+  WGA_LAUNCH((k_bits_text<B, kSlot, kEmit>), (u32)((n + 255u) / 256u), WGA_BLOCK, c->stream, (u64)n, d_bits, d_text, d_len);
+  LAUNCH_CHECK();
+  return WGA_OK;
+}
 /* What wga_chain_filter and wga_chain2paf do alike behind their own null checks: the checks of the arrays and limits, the count
  * call's zeroed results (n_kept: K25's, else null), the read of the data lines' number and the items of the stream (the plan leads
  * d_work in both layouts).  *n_items == 0 when it returns WGA_OK: nothing is left to do. */

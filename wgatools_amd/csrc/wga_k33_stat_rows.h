@@ -7,7 +7,7 @@
 #ifndef WGA_K33_STAT_ROWS_H
 #define WGA_K33_STAT_ROWS_H
 
-#include "wga_text_out.h" /* the sinks, ScanItems and k_text_items_fill */
+#include "wga_text_out.h" /* the sinks, ScanItems, k_text_items_fill and the record rows' skeleton */
 #include "wga_paf_head.h" /* csv_field_emit, name_span_len */
 #include "wga_f32_text.h" /* f32_text_emit: an f32 as ryu prints it */
 
@@ -20,16 +20,14 @@
  *   <inv_ins_event> <inv_ins_size> <inv_del_event> <inv_del_size>
  * with tabs between them and "\n" behind.  The sums are mod 2^64, the three f32 columns IEEE single precision: u64 -> f32
  * rounds to nearest even, the division is the correctly rounded one (no fast-math, no reciprocal).
- *   plan   one thread per row: the row's emitter into a TextCount.
- *   scan   the exclusive scan of the plan (ScanItems<StatRowsFmt>: item x is row x) into the caller's row_off[n + 1].
- *   fill   k_text_items_fill<StatRowsFmt> (wga_text_out.h): 256 consecutive rows per block are one contiguous stretch, staged
- *          in LDS and flushed in 16-byte stores.  A row without its names is at most 17 x 20 + 3 x 16 + 22 = 410 bytes, but a
- *          stage for that many (102.5 KiB) would leave a CU one block; rows of real files are 110 to 140 bytes (names of a few
+ * Plan, scan and fill are the record rows' of wga_text_out.h (k_record_rows_plan<StatRowSrc>, ScanItems<StatRowsFmt>,
+ * k_text_items_fill<StatRowsFmt>).
+ *   stage  256 consecutive rows per block are one contiguous stretch, staged in LDS and flushed in 16-byte stores.  A row
+ *          without its names is at most 17 x 20 + 3 x 16 + 22 = 410 bytes, but a stage for that many (102.5 KiB) would leave a CU one block; rows of real files are 110 to 140 bytes (names of a few
  *          letters, numbers of up to 9 digits, floats of 9 to 11 bytes: 112 and 115 bytes measured on the two shapes of
  *          profiles/r07_stat_rows_e2e.txt).  The stage is 256 x 156 bytes: with the 32 bytes of alignment slack and the fill's two
  *          words 39 984 bytes of LDS, so that FOUR blocks (16 waves) share the 160 KiB of a CU.  A block whose stretch is longer
- *          (names of kilobytes, or every number at its widest) writes its rows directly.  kCheckSize is on and costs one load:
- *          the size of a row is its plan, so a row_off that is not this plan's scan is not written into. */
+ *          (names of kilobytes, or every number at its widest) writes its rows directly. */
 #define WGA_STAT_ROWS_STAGE (WGA_TEXT_ITEMS * 156u)
 
 /* the three f32 columns of a record (the bits: the formatter is a function of those) */
@@ -57,13 +55,13 @@ __device__ __forceinline__ void stat_row_emit(S& s, const wga_stat_row_head& H, 
   const u32 rl = name_span_len(H.rname_off, H.rname_len, n_name_bytes), ql = name_span_len(H.qname_off, H.qname_len, n_name_bytes);
   const u64 aligned = c.match + c.mismatch + c.del_bp + c.inv_del_bp;
   const StatRowF32 f = stat_row_f32(c, aligned);
-  csv_field_emit(s, names + (rl ? H.rname_off : 0u), rl, (u8)'\t');
+  csv_field_emit<(u8)'\t'>(s, names + (rl ? H.rname_off : 0u), rl);
   s.c((u8)'\t');
   s.dec(H.ref_size);
   s.c((u8)'\t');
   s.dec(H.ref_start);
   s.c((u8)'\t');
-  csv_field_emit(s, names + (ql ? H.qname_off : 0u), ql, (u8)'\t');
+  csv_field_emit<(u8)'\t'>(s, names + (ql ? H.qname_off : 0u), ql);
   s.c((u8)'\t');
   s.dec(H.query_size);
   s.c((u8)'\t');
@@ -93,43 +91,18 @@ __device__ __forceinline__ void stat_row_emit(S& s, const wga_stat_row_head& H, 
   s.c((u8)'\n');
 }
 
-/* plan[r] = the bytes of row r */
-__global__ __launch_bounds__(256) void k_stat_rows_plan(const u8* __restrict__ names, u64 n_name_bytes,
-                                                        const wga_stat_row_head* __restrict__ heads, u32 n,
-                                                        const wga_cigar_counts* __restrict__ counts, u64* __restrict__ plan) {
-  const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
-  if (r >= (u64)n) return;
-  TextCount t;
-  stat_row_emit(t, heads[r], names, n_name_bytes, counts[r]);
-  plan[r] = t.n;
-}
-
-/* K33's format (wga_text_out.h): item x is row x of record x */
-struct StatRowsFmt {
+/* K33's row source and format (RECORD ROWS in wga_text_out.h): item x is row x of record x */
+struct StatRowSrc {
   static constexpr u32 kStage = WGA_STAT_ROWS_STAGE;
-  static constexpr bool kCheckSize = true;
   const u8* names;
   u64 n_name_bytes;
   const wga_stat_row_head* heads;
   const wga_cigar_counts* counts;
-  const u64* plan;
-  u32 n_rec;
-  __device__ __forceinline__ u32 rec(u64 x, u32, u32) const { return (u32)x; }
-  __device__ __forceinline__ u64 size(u64, u32 r) const { return plan[r]; }
   template <typename S>
-  __device__ __forceinline__ void emit(S& s, u64, u32 r) const {
+  __device__ __forceinline__ void emit(S& s, u32 r) const {
     stat_row_emit(s, heads[r], names, n_name_bytes, counts[r]);
   }
 };
-
-/* the formatter alone: text[16 i ..) = the text of the f32 with the bits bits[i], len[i] its length; the bytes behind a text are
- * left as they were */
-__global__ __launch_bounds__(256) void k_f32_text(u64 n, const u32* __restrict__ bits, u8* __restrict__ text, u8* __restrict__ len) {
-  const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
-  if (i >= n) return;
-  TextPut w = {text + 16u * i};
-  f32_text_emit(w, bits[i]);
-  len[i] = (u8)(w.p - (text + 16u * i));
-}
+struct StatRowsFmt : RecordRowsFmt<StatRowSrc> {};
 
 #endif /* WGA_K33_STAT_ROWS_H */

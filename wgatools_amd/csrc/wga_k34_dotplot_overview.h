@@ -6,7 +6,7 @@
 #ifndef WGA_K34_DOTPLOT_OVERVIEW_H
 #define WGA_K34_DOTPLOT_OVERVIEW_H
 
-#include "wga_text_out.h" /* the sinks, ScanItems and k_text_items_fill */
+#include "wga_text_out.h" /* the sinks, ScanItems, k_text_items_fill and the record rows' skeleton */
 #include "wga_paf_head.h" /* csv_field_emit, name_span_len */
 #include "wga_f64_text.h" /* f64_text_emit: an f64 as ryu prints it */
 
@@ -18,27 +18,18 @@
  * identity = (double)match / (double)align_size in IEEE double precision: u64 -> f64 rounds to nearest even, the division is the
  * correctly rounded one (no fast-math, no reciprocal), 0 / 0 is NaN and x / 0 inf; under no_identity the column is "1.0" and the
  * counters are not read (they may be absent).
- *   plan   one thread per row: the row's emitter into a TextCount.
- *   scan   the exclusive scan of the plan (ScanItems<DotplotOvFmt>: item x is row x) into the caller's row_off[n + 1].
- *   fill   k_text_items_fill<DotplotOvFmt> (wga_text_out.h): 256 consecutive rows per block are one contiguous stretch, staged
- *          in LDS and flushed in 16-byte stores.  A row without its names is at most 4 x 20 + 24 + 7 = 111 bytes; rows of real
- *          files are 40 to 70 bytes (coordinates of up to 9 digits, an identity of 3 to 20 bytes, names of a few letters).  The
+ * Plan, scan and fill are the record rows' of wga_text_out.h (k_record_rows_plan<DotplotOvSrc>, ScanItems<DotplotOvFmt>,
+ * k_text_items_fill<DotplotOvFmt>).
+ *   stage  256 consecutive rows per block are one contiguous stretch, staged in LDS and flushed in 16-byte stores.  A row
+ *          without its names is at most 4 x 20 + 24 + 7 = 111 bytes; rows of real files are 40 to 70 bytes (coordinates of up to 9 digits, an identity of 3 to 20 bytes, names of a few letters).  The
  *          stage is 256 x 112 bytes: a block stages its stretch whenever its rows AVERAGE 112 bytes, which leaves a real row 40
  *          bytes and more for longer names, and holds 256 rows of the widest numbers with empty names.  With the 32 bytes of
  *          alignment slack and the fill's two words that is 28 720 bytes of LDS, so that FIVE blocks (20 waves, 5 per SIMD) share
  *          the 160 KiB of a CU (the fill takes 67 VGPRs and no scratch: registers would admit 7).  A thread's work is integer
  *          arithmetic on registers between one read of its head and one write of its row into LDS, so the waves hide each
  *          other's loads, and more of them per CU (a smaller stage) would buy nothing the stage's misses would not cost.  A block whose stretch is longer (names of kilobytes) writes its rows directly.
- *          kCheckSize is on and costs one load: the size of a row is its plan, so a row_off that is not this plan's scan is not
- *          written into.
  * Not tuned past the staged fill: the rows are a few tens of MB against the GB of ops that K1 / K3 read for the counters. */
 #define WGA_DOTPLOT_OV_STAGE (WGA_TEXT_ITEMS * 112u)
-
-/* K34's sinks are types of their own, so that csv_field_emit<S> is instantiated apart from the instances of K27, K28 and K33:
- * every caller of those passes a tab, the compiler folds that constant into them, and a second delimiter in the same instance
- * changes those kernels' instructions (scripts/kernel_isa_diff.py) */
-struct DotplotOvCount : TextCount {};
-struct DotplotOvPut : TextPut {};
 
 /* the identity column's bits: the formatter is a function of those */
 __device__ __forceinline__ u64 dotplot_ov_identity(u64 match, u64 align_size) {
@@ -62,52 +53,24 @@ __device__ __forceinline__ void dotplot_ov_row_emit(S& s, const wga_dotplot_ov_h
   if (counts) f64_text_emit(s, dotplot_ov_identity(counts[r].match, H.align_size));
   else s.c((u8)'1'), s.c((u8)'.'), s.c((u8)'0');
   s.c((u8)',');
-  csv_field_emit(s, names + (rl ? H.rname_off : 0u), rl, (u8)',');
+  csv_field_emit<(u8)','>(s, names + (rl ? H.rname_off : 0u), rl);
   s.c((u8)',');
-  csv_field_emit(s, names + (ql ? H.qname_off : 0u), ql, (u8)',');
+  csv_field_emit<(u8)','>(s, names + (ql ? H.qname_off : 0u), ql);
   s.c((u8)'\n');
 }
 
-/* plan[r] = the bytes of row r */
-__global__ __launch_bounds__(256) void k_dotplot_ov_plan(const u8* __restrict__ names, u64 n_name_bytes,
-                                                         const wga_dotplot_ov_head* __restrict__ heads, u32 n,
-                                                         const wga_cigar_counts* __restrict__ counts, u64* __restrict__ plan) {
-  const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
-  if (r >= (u64)n) return;
-  DotplotOvCount t;
-  dotplot_ov_row_emit(t, heads[r], names, n_name_bytes, counts, (u32)r);
-  plan[r] = t.n;
-}
-
-/* K34's format (wga_text_out.h): item x is row x of record x */
-struct DotplotOvFmt {
+/* K34's row source and format (RECORD ROWS in wga_text_out.h): item x is row x of record x */
+struct DotplotOvSrc {
   static constexpr u32 kStage = WGA_DOTPLOT_OV_STAGE;
-  static constexpr bool kCheckSize = true;
   const u8* names;
   u64 n_name_bytes;
   const wga_dotplot_ov_head* heads;
   const wga_cigar_counts* counts; /* or nullptr: no_identity */
-  const u64* plan;
-  u32 n_rec;
-  __device__ __forceinline__ u32 rec(u64 x, u32, u32) const { return (u32)x; }
-  __device__ __forceinline__ u64 size(u64, u32 r) const { return plan[r]; }
   template <typename S>
-  __device__ __forceinline__ void emit(S& s, u64, u32 r) const { /* S = TextPut: the fill's */
-    DotplotOvPut w;
-    w.p = s.p;
-    dotplot_ov_row_emit(w, heads[r], names, n_name_bytes, counts, r);
-    s.p = w.p;
+  __device__ __forceinline__ void emit(S& s, u32 r) const {
+    dotplot_ov_row_emit(s, heads[r], names, n_name_bytes, counts, r);
   }
 };
-
-/* the formatter alone: text[32 i ..) = the text of the f64 with the bits bits[i], len[i] its length; the bytes behind a text are
- * left as they were */
-__global__ __launch_bounds__(256) void k_f64_text(u64 n, const u64* __restrict__ bits, u8* __restrict__ text, u8* __restrict__ len) {
-  const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
-  if (i >= n) return;
-  TextPut w = {text + 32u * i};
-  f64_text_emit(w, bits[i]);
-  len[i] = (u8)(w.p - (text + 32u * i));
-}
+struct DotplotOvFmt : RecordRowsFmt<DotplotOvSrc> {};
 
 #endif /* WGA_K34_DOTPLOT_OVERVIEW_H */

@@ -7,12 +7,12 @@
 
 /* a field as the csv writer writes it under QuoteStyle::Necessary: as it is, unless it holds the delimiter, a quote, CR or LF;
  * then between quotes with every quote inside doubled */
-template <typename S>
-__device__ __forceinline__ void csv_field_emit(S& s, const u8* __restrict__ p, u32 len, u8 delim) {
+template <u8 kDelim, typename S>
+__device__ __forceinline__ void csv_field_emit(S& s, const u8* __restrict__ p, u32 len) {
   bool need = false;
   for (u32 k = 0; k < len && !need; k++) {
     const u8 b = p[k];
-    need = b == delim || b == (u8)'"' || b == (u8)'\n' || b == (u8)'\r';
+    need = b == kDelim || b == (u8)'"' || b == (u8)'\n' || b == (u8)'\r';
   }
   if (!need) {
     s.str(p, len);
@@ -33,7 +33,7 @@ template <bool kNm = false, typename S>
 __device__ __forceinline__ void paf_head_emit(S& s, const u8* __restrict__ qname, u32 qname_len, const u64* q, bool neg,
                                               const u8* __restrict__ tname, u32 tname_len, const u64* t, u64 matches,
                                               u64 block_length, u64 mapq) {
-  csv_field_emit(s, qname, qname_len, (u8)'\t');
+  csv_field_emit<(u8)'\t'>(s, qname, qname_len);
   for (u32 k = 0; k < 3u; k++) {
     s.c((u8)'\t');
     s.dec(q[k]);
@@ -41,7 +41,7 @@ __device__ __forceinline__ void paf_head_emit(S& s, const u8* __restrict__ qname
   s.c((u8)'\t');
   s.c(neg ? (u8)'-' : (u8)'+');
   s.c((u8)'\t');
-  csv_field_emit(s, tname, tname_len, (u8)'\t');
+  csv_field_emit<(u8)'\t'>(s, tname, tname_len);
   for (u32 k = 0; k < 3u; k++) {
     s.c((u8)'\t');
     s.dec(t[k]);

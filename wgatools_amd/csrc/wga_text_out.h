@@ -1,7 +1,7 @@
 /*
  * wga_text_out.h — what the kernels that write text share: decimal numbers, the count / put sink pair, the staged stretch and
- * its flush, the bisection that finds an element's record, and the fill kernel of the texts that are a stream of items (at the
- * end of the file).  Nothing here knows a format.
+ * its flush, the bisection that finds an element's record, the fill kernel of the texts that are a stream of items, and the
+ * skeleton of the texts that are one row per record (both at the end of the file).  Nothing here knows a format.
  *
  * ONE EMITTER, TWO SINKS.  A format is one function template `xxx_emit(S& s, ...)` that names its bytes in order through
  * s.c / s.dec / s.str.  Run into a TextCount it is the size the scan adds up, run into a TextPut it is the text: what the count
@@ -184,6 +184,53 @@ __global__ __launch_bounds__(256) void k_text_items_fill(F f, u64 n_items, const
     }
   }
   st.flush_block(tid);
+}
+
+/* RECORD ROWS.  A text of one row per record (K33's TSV rows, K34's csv rows) is the item stream whose item x is row x of record
+ * x.  The row source R is a plain struct passed by value:
+ *   static constexpr u32 kStage            as above
+ *   names, n_name_bytes, heads, counts     what the rows are made of (four fields: the kernel arguments' layout hangs on it)
+ *   void emit(S& s, u32 r) const           row r's emitter
+ *   plan   k_record_rows_plan<R>: one thread per row, the emitter into a TextCount.
+ *   scan   ScanItems<F> over the plan, F a struct derived from RecordRowsFmt<R>, into the caller's row_off[n + 1].
+ *   fill   k_text_items_fill<F>.  kCheckSize is on and costs one load: the size of a row is its plan, so a row_off that is not
+ *          this plan's scan is not written into. */
+template <typename R>
+struct RecordRowsFmt : R {
+  using Src = R;
+  static constexpr bool kCheckSize = true;
+  const u64* plan;
+  u32 n_rec;
+  __device__ __forceinline__ u32 rec(u64 x, u32, u32) const { return (u32)x; }
+  __device__ __forceinline__ u64 size(u64, u32 r) const { return plan[r]; }
+  template <typename S>
+  __device__ __forceinline__ void emit(S& s, u64, u32 r) const {
+    R::emit(s, r);
+  }
+};
+
+/* plan[r] = the bytes of row r; the source's four fields as arguments of their own */
+template <typename R>
+__global__ __launch_bounds__(256) void k_record_rows_plan(const u8* __restrict__ names, u64 n_name_bytes,
+                                                          decltype(R::heads) __restrict__ heads, u32 n,
+                                                          decltype(R::counts) __restrict__ counts, u64* __restrict__ plan) {
+  const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
+  if (r >= (u64)n) return;
+  const R src = {names, n_name_bytes, heads, counts};
+  TextCount t;
+  src.emit(t, (u32)r);
+  plan[r] = t.n;
+}
+
+/* A formatter alone (K33's f32, K34's f64): text[kSlot i ..) = the text of the value with the bits bits[i], len[i] its length; the
+ * bytes behind a text are left as they were */
+template <typename B, u32 kSlot, void (*kEmit)(TextPut&, B)>
+__global__ __launch_bounds__(256) void k_bits_text(u64 n, const B* __restrict__ bits, u8* __restrict__ text, u8* __restrict__ len) {
+  const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  TextPut w = {text + kSlot * i};
+  kEmit(w, bits[i]);
+  len[i] = (u8)(w.p - (text + kSlot * i));
 }
 
 #endif /* WGA_TEXT_OUT_H */

@@ -557,11 +557,12 @@ class Engine:
         self._check(self.lib.wga_chain_line_off_rebase(self.ctx, int(n), _p(line_off), _p(out)))
         return out
 
-    def _count_then_fill(self, name, what, args, n_outs, out_shift, types=None):
+    def _count_then_fill(self, name, what, args, n_outs, out_shift, types=None, fixed=None):
         """both calls of the text writer `name`: args, then n_outs results by reference (*total_bytes first; u64, or the ctypes
         `types`), then d_out.
-        The fill goes into a buffer of 0xA5 and must leave the results (`what` names them) and the bytes around the text alone.
-        Returns (text, the results)."""
+        The fill goes into a buffer of 0xA5 and must leave the results (`what` names them; the first `fixed` of them where the
+        fill call sets the others) and the bytes around the text alone.
+        Returns (text, the results as the fill call leaves them)."""
         fn = getattr(self.lib, name)
         outs = [t(0) for t in (types or [C.c_uint64] * n_outs)]
         refs = [C.byref(o) for o in outs]
@@ -572,12 +573,13 @@ class Engine:
         lead = guard + (-out.ptr) % 64 + int(out_shift)
         self._check(fn(*args, *refs, out.ptr + lead))
         self.sync()
-        if tuple(int(o.value) for o in outs) != first:
+        last = tuple(int(o.value) for o in outs)
+        if last[:fixed] != first[:fixed]:
             raise _lib.WgaError("%s changed its %s in the second call" % (name, what))
         got = out.numpy()
         if not ((got[:lead] == 0xA5).all() and (got[lead + first[0]:] == 0xA5).all()):
             raise _lib.WgaError("%s wrote outside d_out[0 .. total_bytes)" % name)
-        return got[lead:lead + first[0]].tobytes(), first
+        return got[lead:lead + first[0]].tobytes(), last
 
     def chain_filter_count(self, text, n_bytes, heads, n_chains, lines, line_off, work, min_block_size=0, min_query_size=0):
         """K25: the count call of wga_chain_filter alone, (total_bytes, n_kept); it leaves its plan and item scan in `work`"""
@@ -721,21 +723,9 @@ class Engine:
         lay = (self.empty(max(n, 1), np.uint64), self.empty(max(n, 1), np.uint64), self.empty(n + 1, np.uint64))
         args = (self.ctx, n, _p(names), int(n_name_bytes), _p(heads), _p(counts), _p(t_src_len), _p(q_src_len), _p(diag), _p(work),
                 _p(lay[0]), _p(lay[1]), _p(lay[2]))
-        total, good, gb = C.c_uint64(0), C.c_uint32(0), C.c_uint64(0)
-        refs = (C.byref(total), C.byref(good), C.byref(gb))
-        self._check(self.lib.wga_paf2maf_frame(*args, *refs, None))
-        first = int(total.value)
-        guard = 64  # bytes around the text that the fill call must leave alone
-        out = self.upload(np.full(first + 2 * guard + 96, 0xA5, dtype=np.uint8))
-        lead = guard + (-out.ptr) % 64 + int(out_shift)
-        self._check(self.lib.wga_paf2maf_frame(*args, *refs, out.ptr + lead))
-        self.sync()
-        if int(total.value) != first:
-            raise _lib.WgaError("wga_paf2maf_frame changed its total in the second call")
-        got = out.numpy()
-        if not ((got[:lead] == 0xA5).all() and (got[lead + first:] == 0xA5).all()):
-            raise _lib.WgaError("wga_paf2maf_frame wrote outside d_out[0 .. total_bytes)")
-        return got[lead:lead + first].tobytes(), int(good.value), int(gb.value), lay
+        text, (_, good, gb) = self._count_then_fill("wga_paf2maf_frame", "total", args, 3, out_shift,
+                                                    types=(C.c_uint64, C.c_uint32, C.c_uint64), fixed=1)  # the fill finds the bad
+        return text, good, gb, lay
 
     def maf_records(self, batch, names, heads, t_fa, t_fa_bytes, t_src_off, t_src_len, q_fa, q_fa_bytes, q_src_off, q_src_len,
                     out_shift=0):
@@ -789,39 +779,33 @@ class Engine:
             work = self.empty(max(int(self.lib.wga_stat_rows_work_bytes(n)), 16), np.uint8)
         row_off = self.empty(n + 1, np.uint64)
         args = (self.ctx, n, _p(names), int(n_name_bytes), _p(heads), _p(counts), _p(work), _p(row_off))
-        total = C.c_uint64(0)
-        self._check(self.lib.wga_stat_rows(*args, C.byref(total), None))
-        first = int(total.value)
-        guard = 64  # bytes around the text that the calls must leave alone
-        out = self.upload(np.full(first + 2 * guard + 96, 0xA5, dtype=np.uint8))
-        lead = guard + (-out.ptr) % 64 + int(out_shift)
-        self._check(self.lib.wga_stat_rows(*args, C.byref(total), out.ptr + lead))
-        self.sync()
-        if int(total.value) != first:
-            raise _lib.WgaError("wga_stat_rows changed its total in the second call")
-        got = out.numpy()
-        if not ((got[:lead] == 0xA5).all() and (got[lead + first:] == 0xA5).all()):
-            raise _lib.WgaError("wga_stat_rows wrote outside d_out[0 .. total_bytes)")
-        return got[lead:lead + first].tobytes(), (row_off.numpy().copy() if n else np.zeros(1, np.uint64))
+        text = self._count_then_fill("wga_stat_rows", "total", args, 1, out_shift)[0]
+        return text, (row_off.numpy().copy() if n else np.zeros(1, np.uint64))
 
-    def f32_text(self, bits):
-        """K33's formatter alone (wga_f32_text): the texts of the f32s with the bit patterns `bits` (uint32), a list of bytes.
-        The text buffer is filled with 0xA5 first: a text may not reach beyond its length"""
-        bits = np.ascontiguousarray(bits, dtype=np.uint32)
+    def _bits_text(self, name, bits, dtype, slot, longest):
+        """a formatter alone (wga_f32_text, wga_f64_text): the texts of the values with the bit patterns `bits`, a list of bytes.
+        The text buffer, `slot` bytes per value, is filled with 0xA5 first: a text may not reach beyond its length"""
+        fn = getattr(self.lib, name)
+        bits = np.ascontiguousarray(bits, dtype=dtype)
         n = int(bits.size)
         if n == 0:
-            self._check(self.lib.wga_f32_text(self.ctx, 0, None, None, None))
+            self._check(fn(self.ctx, 0, None, None, None))
             return []
         d_bits = self.upload(bits)
-        d_text = self.upload(np.full(16 * n, 0xA5, dtype=np.uint8))
+        d_text = self.upload(np.full(slot * n, 0xA5, dtype=np.uint8))
         d_len = self.upload(np.full(n, 0xFF, dtype=np.uint8))
-        self._check(self.lib.wga_f32_text(self.ctx, n, _p(d_bits), _p(d_text), _p(d_len)))
+        self._check(fn(self.ctx, n, _p(d_bits), _p(d_text), _p(d_len)))
         self.sync()
-        text = d_text.numpy().reshape(n, 16)
+        text = d_text.numpy().reshape(n, slot)
         ln = d_len.numpy()
-        if (ln > 16).any() or not (text[np.arange(16)[None, :] >= ln[:, None]] == 0xA5).all():
-            raise _lib.WgaError("wga_f32_text wrote behind a text's length")
-        return [text[i, :ln[i]].tobytes() for i in range(n)]
+        if (ln > longest).any() or not (text[np.arange(slot)[None, :] >= ln[:, None]] == 0xA5).all():
+            raise _lib.WgaError("%s wrote behind a text's length" % name)
+        flat = text.tobytes()
+        return [flat[slot * i:slot * i + k] for i, k in enumerate(ln.tolist())]
+
+    def f32_text(self, bits):
+        """K33's formatter alone: the texts of the f32s with the bit patterns `bits` (uint32)"""
+        return self._bits_text("wga_f32_text", bits, np.uint32, 16, 16)
 
     def dotplot_overview(self, n, names, n_name_bytes, heads, counts, no_identity=False, work=None, out_shift=0):
         """K34 (dotplot.rs:384-423): the csv rows of `dotplot -m overview` for n records, both calls of wga_dotplot_overview on
@@ -834,44 +818,12 @@ class Engine:
             work = self.empty(max(int(self.lib.wga_dotplot_overview_work_bytes(n)), 16), np.uint8)
         row_off = self.empty(n + 1, np.uint64)
         args = (self.ctx, n, _p(names), int(n_name_bytes), _p(heads), _p(counts), 1 if no_identity else 0, _p(work), _p(row_off))
-        total = C.c_uint64(0)
-        guard = 64  # bytes around the text that the calls must leave alone
-        self._check(self.lib.wga_dotplot_overview(*args, C.byref(total), None))
-        first = int(total.value)
-        out = self.upload(np.full(first + 2 * guard + 96, 0xA5, dtype=np.uint8))
-        lead = guard + (-out.ptr) % 64 + int(out_shift)
-        self._check(self.lib.wga_dotplot_overview(*args, C.byref(total), out.ptr + lead))
-        self.sync()
-        if int(total.value) != first:
-            raise _lib.WgaError("wga_dotplot_overview changed its total in the second call")
-        got = out.numpy()
-        if not ((got[:lead] == 0xA5).all() and (got[lead + first:] == 0xA5).all()):
-            raise _lib.WgaError("wga_dotplot_overview wrote outside d_out[0 .. total_bytes)")
-        return got[lead:lead + first].tobytes(), (row_off.numpy().copy() if n else np.zeros(1, np.uint64))
+        text = self._count_then_fill("wga_dotplot_overview", "total", args, 1, out_shift)[0]
+        return text, (row_off.numpy().copy() if n else np.zeros(1, np.uint64))
 
     def f64_text(self, bits):
-        """K34's formatter alone (wga_f64_text): the texts of the f64s with the bit patterns `bits` (uint64), a list of bytes.
-        The text buffer is filled with 0xA5 first: a text may not reach beyond its length"""
-        bits = np.ascontiguousarray(bits, dtype=np.uint64)
-        n = int(bits.size)
-        if n == 0:
-            self._check(self.lib.wga_f64_text(self.ctx, 0, None, None, None))
-            return []
-        d_bits = self.upload(bits)
-        d_text = self.upload(np.full(32 * n, 0xA5, dtype=np.uint8))
-        d_len = self.upload(np.full(n, 0xFF, dtype=np.uint8))
-        self._check(self.lib.wga_f64_text(self.ctx, n, _p(d_bits), _p(d_text), _p(d_len)))
-        self.sync()
-        text = d_text.numpy().reshape(n, 32)
-        ln = d_len.numpy()
-        if (ln > 24).any() or not (text[np.arange(32)[None, :] >= ln[:, None]] == 0xA5).all():
-            raise _lib.WgaError("wga_f64_text wrote behind a text's length")
-        flat, at = text.tobytes(), 0
-        out = []
-        for k in ln.tolist():
-            out.append(flat[at:at + k])
-            at += 32
-        return out
+        """K34's formatter alone: the texts of the f64s with the bit patterns `bits` (uint64)"""
+        return self._bits_text("wga_f64_text", bits, np.uint64, 32, 24)
 
     def pafpseudo_frame(self, items, pool, pool_bytes, text, text_bytes, out, out_bytes, first_bad=None):
         """K31 (the rows of pseudomaf.rs:98-209 around the segments): writes every FILL / COPY span of `items` (SPAN_ITEM_DTYPE, a

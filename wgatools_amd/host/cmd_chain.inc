@@ -566,14 +566,15 @@ int cmd_chain2paf(const std::string* input, Output& out) {
   ChainInput in = load_chain(d, input, want);
   if (want && chain2paf_device_takes(d, in)) { /* all records are made before the first byte is written, like the host path */
     if (in.n_chains) {
-      void* d_work = d.alloc((size_t)wga_chain2paf_work_bytes(in.n_chains, in.n_data_lines) + 16);
-      uint64_t bytes = 0;
-      d.check(wga_chain2paf(d.ctx, in.d_text, in.n_bytes, in.d_heads, in.n_chains, in.d_lines, in.d_line_off, d_work, &bytes, nullptr));
-      auto* d_out = (uint8_t*)d.alloc((size_t)bytes + 16);
-      d.check(wga_chain2paf(d.ctx, in.d_text, in.n_bytes, in.d_heads, in.n_chains, in.d_lines, in.d_line_off, d_work, &bytes, d_out));
+      const DevText t = two_call_text(
+          d, (size_t)wga_chain2paf_work_bytes(in.n_chains, in.n_data_lines) + 16,
+          [&](void* d_work, uint64_t* bytes, uint8_t* d_out) {
+            return wga_chain2paf(d.ctx, in.d_text, in.n_bytes, in.d_heads, in.n_chains, in.d_lines, in.d_line_off, d_work, bytes, d_out);
+          },
+          true);
       d.check(wga_sync(d.ctx));
       g_timer.mark("chain2paf records (device)");
-      stream_out(d, out, d_out, (size_t)bytes, false);
+      stream_out(d, out, t.d_out, t.bytes, false);
       g_timer.mark("copy out + write");
     }
     out.close();

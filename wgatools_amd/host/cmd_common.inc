@@ -571,6 +571,38 @@ static void download_append(Dev& d, std::string& dst, const uint8_t* d_src, size
   }
 }
 
+/* The two calls of a text entry: call(d_work, &bytes, d_out) counts with d_out == nullptr and writes the text otherwise.  The
+ * work area is work_bytes long (the entry's own plus what the site asks for behind it), the output has 64 bytes of slack behind
+ * the text; the fill call at zero bytes is made only where fill_empty says so.  Both areas stay the caller's to release. */
+struct DevText {
+  void* d_work;
+  uint8_t* d_out;
+  size_t bytes;
+};
+static DevText two_call_text(Dev& d, size_t work_bytes, const std::function<int(void*, uint64_t*, uint8_t*)>& call,
+                             bool fill_empty = false) {
+  void* d_work = d.alloc(work_bytes);
+  uint64_t bytes = 0;
+  d.check(call(d_work, &bytes, nullptr));
+  auto* d_out = (uint8_t*)d.alloc((size_t)bytes + 64);
+  if (bytes || fill_empty) d.check(call(d_work, &bytes, d_out));
+  return {d_work, d_out, (size_t)bytes};
+}
+
+/* The rows of a row writer (K33, K34) for the records of hd (heads of type Head: the rest of hd), appended to `text`:
+ * call(d_heads, d_work, d_row_off, &bytes, d_out) is the entry.  Returns the rows' offsets on the device, n + 1. */
+template <typename Head, typename Call>
+static const uint64_t* record_rows_text(Dev& d, NameSpans& hd, const std::vector<Head>& heads, size_t work_bytes, std::string& text,
+                                        const Call& call) {
+  hd.upload_names(d);
+  const Head* d_heads = d.upload(heads);
+  auto* d_off = (uint64_t*)d.alloc((heads.size() + 1) * 8);
+  const DevText t = two_call_text(
+      d, work_bytes, [&](void* d_work, uint64_t* bytes, uint8_t* d_out) { return call(d_heads, d_work, d_off, bytes, d_out); });
+  download_append(d, text, t.d_out, t.bytes);
+  return d_off;
+}
+
 /* ---- stat --each on the device (K33, wga_stat_rows) ------------------------------------------------------------------------------
  * WGA_STAT_WRITER=host: stat_tsv builds, sorts and prints a Statistic per record on one host thread, as before K33 (measurements,
  * and the cross-check of the device writer: same bytes) */
@@ -618,16 +650,12 @@ struct StatRows {
   /* the rows of the n records noted last, whose counts stand on d (device 0) */
   void piece(Dev& d, StatRowHeads& hd, const wga_cigar_counts* d_counts) {
     const uint32_t n = (uint32_t)hd.heads.size();
-    hd.upload_names(d);
-    const wga_stat_row_head* d_heads = d.upload(hd.heads);
-    void* d_work = d.alloc((size_t)wga_stat_rows_work_bytes(n));
-    auto* d_off = (uint64_t*)d.alloc(((size_t)n + 1) * 8);
-    uint64_t total = 0;
-    d.check(wga_stat_rows(d.ctx, n, hd.d_names, hd.n_name_bytes, d_heads, d_counts, d_work, d_off, &total, nullptr));
-    auto* d_out = (uint8_t*)d.alloc((size_t)total + 64);
-    if (total) d.check(wga_stat_rows(d.ctx, n, hd.d_names, hd.n_name_bytes, d_heads, d_counts, d_work, d_off, &total, d_out));
     text.emplace_back();
-    download_append(d, text.back(), d_out, (size_t)total);
+    const uint64_t* d_off = record_rows_text(
+        d, hd, hd.heads, (size_t)wga_stat_rows_work_bytes(n), text.back(),
+        [&](const wga_stat_row_head* d_heads, void* d_work, uint64_t* d_row_off, uint64_t* total, uint8_t* d_out) {
+          return wga_stat_rows(d.ctx, n, hd.d_names, hd.n_name_bytes, d_heads, d_counts, d_work, d_row_off, total, d_out);
+        });
     std::string offs; /* the offsets through the same pinned buffers */
     download_append(d, offs, (const uint8_t*)d_off, ((size_t)n + 1) * 8);
     row_off.emplace_back((size_t)n + 1);

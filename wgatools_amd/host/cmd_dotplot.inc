@@ -59,15 +59,11 @@ static std::string dotplot_rows(Dev& d, bool base, bool no_identity, uint64_t cu
         /* K26: the rows are written where the segments are and come back as text */
         auto* d_tails = d.upload((const uint8_t*)tails.data(), tails.size());
         auto* d_tail_off = d.upload(tail_off);
-        void* d_work = d.alloc((size_t)wga_dotplot_csv_work_bytes(n_rows) + 16);
-        uint64_t bytes = 0;
-        d.check(wga_dotplot_csv(d.ctx, n, d_segs, d_off, d_tails, d_tail_off, d_work, &bytes, nullptr));
-        if (bytes) {
-          auto* d_out = (uint8_t*)d.alloc((size_t)bytes + 16);
-          d.check(wga_dotplot_csv(d.ctx, n, d_segs, d_off, d_tails, d_tail_off, d_work, &bytes, d_out));
-          text.resize((size_t)bytes);
-          d.download((uint8_t*)&text[0], d_out, (size_t)bytes);
-        }
+        const DevText t = two_call_text(d, (size_t)wga_dotplot_csv_work_bytes(n_rows) + 16, [&](void* d_work, uint64_t* bytes, uint8_t* d_out) {
+          return wga_dotplot_csv(d.ctx, n, d_segs, d_off, d_tails, d_tail_off, d_work, bytes, d_out);
+        });
+        text.resize(t.bytes);
+        if (t.bytes) d.download((uint8_t*)&text[0], t.d_out, t.bytes);
       } else {
         std::vector<uint64_t> off(n + 1);
         d.download(off.data(), d_off, n + 1);
@@ -126,17 +122,11 @@ static std::string dotplot_overview_rows(Dev& d, DotOvHeads& hd, const wga_cigar
   std::string text;
   const uint32_t n = (uint32_t)hd.heads.size();
   if (n == 0) return text;
-  hd.upload_names(d);
-  const wga_dotplot_ov_head* d_heads = d.upload(hd.heads);
-  void* d_work = d.alloc((size_t)wga_dotplot_overview_work_bytes(n));
-  auto* d_off = (uint64_t*)d.alloc(((size_t)n + 1) * 8);
-  const int no_identity = d_counts ? 0 : 1;
-  uint64_t total = 0;
-  d.check(wga_dotplot_overview(d.ctx, n, hd.d_names, hd.n_name_bytes, d_heads, d_counts, no_identity, d_work, d_off, &total, nullptr));
-  if (total == 0) return text;
-  auto* d_out = (uint8_t*)d.alloc((size_t)total + 64);
-  d.check(wga_dotplot_overview(d.ctx, n, hd.d_names, hd.n_name_bytes, d_heads, d_counts, no_identity, d_work, d_off, &total, d_out));
-  download_append(d, text, d_out, (size_t)total);
+  record_rows_text(d, hd, hd.heads, (size_t)wga_dotplot_overview_work_bytes(n), text,
+                   [&](const wga_dotplot_ov_head* d_heads, void* d_work, uint64_t* d_row_off, uint64_t* total, uint8_t* d_out) {
+                     return wga_dotplot_overview(d.ctx, n, hd.d_names, hd.n_name_bytes, d_heads, d_counts, d_counts ? 0 : 1, d_work,
+                                                 d_row_off, total, d_out);
+                   });
   return text;
 }
 /* records [lo, hi) of a PAF piece: the counters stay where K1 left them, only the diagnostics come back; the names are read in

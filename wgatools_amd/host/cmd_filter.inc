@@ -354,17 +354,16 @@ int chain_filter_path(const std::string* input) { /* `__chain_filter_path` */
 
 static int filter_chain_device(Dev& d, const ChainInput& in, uint64_t min_block, uint64_t min_query, Output& out) {
   const wga_chain_filter_params par = {min_block, min_query};
-  void* d_work = d.alloc((size_t)wga_chain_filter_work_bytes(in.n_chains, in.n_data_lines) + 16);
-  uint64_t bytes = 0, kept = 0;
-  d.check(wga_chain_filter(d.ctx, in.d_text, in.n_bytes, in.d_heads, in.n_chains, in.d_lines, in.d_line_off, &par, d_work, &bytes,
-                           &kept, nullptr));
-  if (bytes) {
-    auto* d_out = (uint8_t*)d.alloc((size_t)bytes + 16);
-    d.check(wga_chain_filter(d.ctx, in.d_text, in.n_bytes, in.d_heads, in.n_chains, in.d_lines, in.d_line_off, &par, d_work, &bytes,
-                             &kept, d_out));
+  uint64_t kept = 0;
+  const DevText t = two_call_text(
+      d, (size_t)wga_chain_filter_work_bytes(in.n_chains, in.n_data_lines) + 16, [&](void* d_work, uint64_t* bytes, uint8_t* d_out) {
+        return wga_chain_filter(d.ctx, in.d_text, in.n_bytes, in.d_heads, in.n_chains, in.d_lines, in.d_line_off, &par, d_work, bytes, &kept,
+                                d_out);
+      });
+  if (t.bytes) {
     d.check(wga_sync(d.ctx));
     g_timer.mark("device text");
-    stream_out(d, out, d_out, (size_t)bytes, false);
+    stream_out(d, out, t.d_out, t.bytes, false);
     g_timer.mark("copy out + write");
   }
   out.close();

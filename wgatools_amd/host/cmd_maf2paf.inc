@@ -16,16 +16,11 @@ static std::string maf2paf_rows(Dev& d, const MafRows& p, const MafRecord* const
     RecordHeads hd(n, &p);
     for (uint32_t k = 0; k < n; k++) hd.add(*recs[k]);
     hd.upload(d);
-    void* d_work = d.alloc((size_t)wga_maf2paf_work_bytes(n, R.n_runs));
-    uint64_t total = 0;
-    d.check(wga_maf2paf(d.ctx, n, hd.d_names, hd.n_name_bytes, hd.d_heads, R.d_counts, R.d_runs, R.d_roff, p.d_c, d_work, &total,
-                        nullptr));
-    auto* d_out = (uint8_t*)d.alloc(total + 64);
-    if (total)
-      d.check(wga_maf2paf(d.ctx, n, hd.d_names, hd.n_name_bytes, hd.d_heads, R.d_counts, R.d_runs, R.d_roff, p.d_c, d_work, &total,
-                          d_out));
-    text.resize((size_t)total);
-    if (total) d.download((uint8_t*)&text[0], d_out, total);
+    const DevText t = two_call_text(d, (size_t)wga_maf2paf_work_bytes(n, R.n_runs), [&](void* d_work, uint64_t* total, uint8_t* d_out) {
+      return wga_maf2paf(d.ctx, n, hd.d_names, hd.n_name_bytes, hd.d_heads, R.d_counts, R.d_runs, R.d_roff, p.d_c, d_work, total, d_out);
+    });
+    text.resize(t.bytes);
+    if (t.bytes) d.download((uint8_t*)&text[0], t.d_out, t.bytes);
     return text;
   }
   std::vector<uint64_t> roff(n + 1);

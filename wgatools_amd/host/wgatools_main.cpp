@@ -1237,19 +1237,14 @@ static MafRowTable<Row> maf_row_table(Dev& d, const MafInput& in, bool in_place,
   return t;
 }
 
-/* One window through a command's two-call entry: call(d_work, &bytes, d_out) counts with d_out == nullptr and writes the text
- * otherwise.  d_window (the window's uploaded blocks or hits) and the work area are released behind the fill call; the sink
- * gets the text. */
+/* One window through a command's two-call entry (two_call_text).  d_window (the window's uploaded blocks or hits) and the work
+ * area are released behind the fill call; the sink gets the text. */
 static void maf_window_call(Dev& d, size_t work_bytes, void* d_window, const std::function<int(void*, uint64_t*, uint8_t*)>& call,
                             const MafSink& sink) {
-  void* d_work = d.alloc(work_bytes);
-  uint64_t bytes = 0;
-  d.check(call(d_work, &bytes, nullptr));
-  auto* d_out = (uint8_t*)d.alloc((size_t)bytes + 16);
-  d.check(call(d_work, &bytes, d_out));
-  d.release(d_work);
+  const DevText t = two_call_text(d, work_bytes, call, true);
+  d.release(t.d_work);
   d.release(d_window);
-  sink(d, d_out, (size_t)bytes);
+  sink(d, t.d_out, t.bytes);
 }
 
 /* The driver of chunk, filter and rename: the input piece by piece (MafChunks: device splitter or host reader; the records in
