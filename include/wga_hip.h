@@ -51,7 +51,8 @@ enum wga_status {
   WGA_E_NO_DEVICE = -2,
   WGA_E_HIP = -3, /* a HIP runtime call failed; see wga_last_error() */
   WGA_E_OOM = -4,
-  WGA_E_TOO_SMALL = -5 /* caller buffer too small (host packer) */
+  WGA_E_TOO_SMALL = -5, /* caller buffer too small (host packer) */
+  WGA_E_FALLBACK = -6   /* wga_maf_index: the line table holds a WGA_MAF_FALLBACK line, the piece is the host reader's */
 };
 
 /* ---- packed op codes ---------------------------------------------------------------------- */
@@ -1173,6 +1174,60 @@ int wga_dotplot_overview(wga_ctx*, uint32_t n, const uint8_t* d_names, uint64_t 
  *   -5 < kk <= 0       : "0.", -kk zeros, digits       else         : d[.ddd]e<kk - 1>
  * n == 0 is valid; WGA_E_INVALID_ARG: a null array with n > 0, n > 0xFFFFFFF0. */
 int wga_f64_text(wga_ctx*, uint64_t n, const uint64_t* d_bits, uint8_t* d_text /* 32 n bytes */, uint8_t* d_len);
+
+/* ---- K35: `maf-index` — block offsets, name groups and the JSON interval text (replaces, for a piece the device splitter took,
+ *      the second walk over the file for the blocks' offsets, the host records and the per-s-line map lookup and append of
+ *      cmd_maf_index, wgatools_amd/host/cmd_ext.inc; in the reference tools/index.rs:14-94) ------------------------------------
+ * d_text, n_bytes, d_lines[n_lines]: the arguments and the result of wga_maf_split, with its limits.  skip = 0, or 2 for a piece
+ * that starts with the dummy line "#\n"; base = the file position of d_text[skip]; carry_offset = the position behind the last
+ * record-ending line seen before this piece.
+ * Blocks and offsets.  A block is a maximal run of WGA_MAF_SLINE lines.  Its offset is the file position behind the '\n' of the line
+ * that ended the run in front of it (the first line behind that run that is not an s-line; lines skipped in front of a run's first
+ * s-line lie inside the block's span); a record-ending line without a final '\n' ends at n_bytes.  The piece's first block takes the
+ * end of the piece's first line when skip == 0 (the file's header line, whatever it starts with), otherwise carry_offset.
+ * *next_offset = the carry for the next piece: the position behind the last line of the piece that ended a run — where the piece's
+ * last run has no ending line, or the piece has no run, the value its last block took or would have taken (so carry_offset itself
+ * for a piece with skip == 2 that ends no run).
+ * Name groups.  Two s-lines belong to the same group exactly when their name bytes are equal: a hash only places a name in the
+ * table, the bytes decide.  Groups are numbered by ascending first s-line.  Context parameter "maf_index_hash_bits" (1 .. 64,
+ * default 64): the hash is cut to that many low bits, so that a test makes every name collide.  Within a group the intervals stand
+ * in file order: a stable LSD radix sort of the s-lines by group number, in as many passes as the group count has digits of
+ * "maf_index_sort_bits" bits (1 .. 8, default 8; any width gives the same order).
+ * Errors of the reference, as line indices (WGA_NONE when absent; both by atomicMin, so runs agree):
+ *   *first_dup_line       the lowest s-line whose name occurs earlier in the same block (index.rs:33-37)
+ *   *first_conflict_line  the lowest s-line whose isref — being the first line of its run — differs from that of its group's
+ *                         first line (index.rs:54-58)
+ * Output.  d_names[*n_names + 1]: one entry per group — the name's span in d_text, size (num[2] of the group's first line),
+ * first_line, isref, n_ivls and text_off, the place of the group's text in d_out — and a closing entry with text_off =
+ * *text_bytes and zeros.  d_out[0 .. *text_bytes): the interval text group after group, a group's intervals joined by ',' and
+ * without brackets, an interval
+ *   {"start":S,"end":E,"strand":"+","offset":O}            ("-" for a line on the '-' strand)
+ * with S = num[0], E = num[0] + num[1] mod 2^64 and O the block's offset, in canonical decimal.
+ *   d_names == NULL and d_out == NULL: everything but the table and the text; *n_names, *n_blocks, *n_slines, *text_bytes,
+ *                  the two error lines and *next_offset are host values (the call synchronises).
+ *   otherwise    : the table and the text.  d_out may have any alignment, the caller leaves 16 bytes of slack behind the text; no
+ *                  byte in front of d_out and none from d_out + *text_bytes on is written.  The counts and d_work are read as
+ *                  the first call left them, so the two calls take the same arguments.
+ * All places are 64-bit.  n_lines == 0 or a table without an s-line: the counts are zero, the call succeeds, nothing is written.
+ * WGA_E_FALLBACK: the table holds a WGA_MAF_FALLBACK line (the caller reads the piece with its host reader).  WGA_E_INVALID_ARG:
+ * a null d_work or host pointer, whatever n_lines; a null array or n_bytes == 0 with n_lines > 0; n_lines that is not the text's
+ * line count; a text beyond wga_maf_split's limits; skip other than 0 and 2; a second call with a null d_names or d_out.
+ * d_work: wga_maf_index_work_bytes(n_lines) bytes of device memory, 8-byte aligned, shared by the two calls. */
+typedef struct {
+  uint64_t name_off;    /* the name's span in d_text */
+  uint64_t size;        /* num[2] of the group's first line */
+  uint64_t first_line;  /* the group's first s-line: an index into d_lines */
+  uint64_t n_ivls;
+  uint64_t text_off;    /* the group's text is d_out[text_off, the next entry's text_off) */
+  uint32_t name_len;
+  uint32_t isref;
+} wga_maf_index_name;   /* 48 bytes */
+
+uint64_t wga_maf_index_work_bytes(uint64_t n_lines);
+int wga_maf_index(wga_ctx*, const uint8_t* d_text, uint64_t n_bytes, const wga_maf_line* d_lines, uint64_t n_lines, uint32_t skip,
+                  uint64_t base, uint64_t carry_offset, void* d_work, uint64_t* n_names, uint64_t* n_blocks, uint64_t* n_slines,
+                  uint64_t* text_bytes, uint64_t* first_dup_line, uint64_t* first_conflict_line, uint64_t* next_offset,
+                  wga_maf_index_name* d_names /* *n_names + 1, device */, uint8_t* d_out);
 
 #ifdef __cplusplus
 }

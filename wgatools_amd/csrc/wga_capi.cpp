@@ -57,6 +57,8 @@
 #include "wga_k32_maf_frame.h" /* K32: the MAF record frames of paf2maf and chain2maf */
 #include "wga_k33_stat_rows.h" /* K33: the TSV rows of stat --each, the f32 text */
 #include "wga_k34_dotplot_overview.h" /* K34: the csv rows of dotplot -m overview, the f64 text */
+#include "wga_sort.h"          /* the stable key sort (run_sort_u32) */
+#include "wga_k35_maf_index.h" /* K35: maf-index: block offsets, name groups, the JSON interval text */
 
 /* A grow-only device buffer of a context.  reserve() leaves it with room for `need` bytes: one that is too small is freed
  * behind the work of the context's stream and allocated anew with `grow` (>= need) bytes — every site has its own growth rule —,
@@ -121,6 +123,8 @@ struct wga_ctx {
   uint64_t maf_long_cols = 32768;  /* MAF blocks beyond this many columns are walked piece by piece ... */
   uint64_t maf_piece_cols = 16384; /* ... of this many columns, one wave each (test knobs: "maf_long_cols", "maf_piece_cols") */
   unsigned paf_pair_hash_bits = 64; /* K24: the low bits of the pair hash that pick a slot (test knob "paf_pair_hash_bits": few bits make the pairs collide) */
+  unsigned maf_index_hash_bits = 64; /* K35: the low bits of the name hash that pick a slot (test knob "maf_index_hash_bits") */
+  unsigned maf_index_sort_bits = 8;  /* K35: the digit width of the sort by group (test knob "maf_index_sort_bits": any width gives the same order) */
   unsigned maf_group = 0;          /* blocks per wave of the MAF stream kernels, 1 .. 8 ("maf_group"; 0 = by the number of blocks) */
   DevBuf maf_tab;                  /* K3 / K4: the table of a call's long blocks (header, list, pieces) */
   bool maf_hdr_clean = false;      /* the header's append counters are zero (the plan kernel leaves them so) */
@@ -253,6 +257,33 @@ static int run_scan(wga_ctx* c, F f, u32 n, u64* d_out /* n+1 */) {
   int rc = ctx_scratch(c, ((size_t)(n + 1023u) / 1024u + 1) * sizeof(u64), &ws);
   if (rc) return rc;
   return run_scan_ws(c, f, n, d_out, (u64*)ws);
+}
+/* The stable sort of the n payloads in buf[0] by key(payload), a key of key_bits bits, in passes of digit_bits bits (wga_sort.h):
+ * *where = the one of buf[0] / buf[1] that holds the result (buf[0] when there is nothing to sort by).  cnt: sort_cnt_words(n) words
+ * for the digit counts and their scan, partial: that scan's partials (sort_cnt_words(n) / 1024 + 2 words). */
+static size_t sort_blocks(uint64_t n) { return (size_t)((n + WGA_SORT_ITEMS - 1u) / WGA_SORT_ITEMS); }
+static size_t sort_cnt_words(uint64_t n) { return ((size_t)1 << WGA_SORT_MAX_BITS) * sort_blocks(n) + 1; }
+template <typename K>
+static int run_sort_u32(wga_ctx* c, K key, u32 n, unsigned key_bits, unsigned digit_bits, u32* const buf[2], u64* cnt, u64* partial,
+                        int* where) {
+  *where = 0;
+  if (n == 0) return WGA_OK;
+  const u32 nblk = (u32)sort_blocks(n);
+  for (unsigned shift = 0; shift < key_bits; shift += digit_bits) {
+    const u32 bits = std::min(digit_bits, key_bits - shift);
+    const u32* in = buf[*where];
+    u32* out = buf[*where ^ 1];
+    WGA_LAUNCH(k_sort_hist<K>, nblk, WGA_BLOCK, c->stream, key, in, n, (u32)shift, bits, nblk, cnt);
+    LAUNCH_CHECK();
+    ScanPlain f;
+    f.in = cnt;
+    int rc = run_scan_ws(c, f, (u32)(((size_t)1 << bits) * nblk), cnt, partial); /* in place, as delim_lists does */
+    if (rc) return rc;
+    WGA_LAUNCH(k_sort_scatter<K>, nblk, WGA_BLOCK, c->stream, key, in, n, (u32)shift, bits, nblk, (const u64*)cnt, out);
+    LAUNCH_CHECK();
+    *where ^= 1;
+  }
+  return WGA_OK;
 }
 /* the text of a stream of n items of format f behind isc, the scan of their sizes over ScanItems<F> (wga_text_out.h) */
 template <typename F>
@@ -456,6 +487,16 @@ int wga_ctx_set_param(wga_ctx* c, const char* name, int64_t value) {
     c->paf_pair_hash_bits = (unsigned)value;
     return WGA_OK;
   }
+  if (strcmp(name, "maf_index_hash_bits") == 0) { /* wga_maf_index: the hash is cut to this many low bits before it picks a place */
+    if (value < 1 || value > 64) return fail(WGA_E_INVALID_ARG, "maf_index_hash_bits: 1 .. 64", nullptr);
+    c->maf_index_hash_bits = (unsigned)value;
+    return WGA_OK;
+  }
+  if (strcmp(name, "maf_index_sort_bits") == 0) { /* wga_maf_index: the digit width of its sort by group */
+    if (value < 1 || value > (int64_t)WGA_SORT_MAX_BITS) return fail(WGA_E_INVALID_ARG, "maf_index_sort_bits: 1 .. 8", nullptr);
+    c->maf_index_sort_bits = (unsigned)value;
+    return WGA_OK;
+  }
   if (strcmp(name, "expand_variant") == 0) {
     if (value != -1 && value != 0 && value != 3) return fail(WGA_E_INVALID_ARG, "expand_variant: -1 (the library's choice), 0, 3", nullptr);
     c->expand_variant = (int)value;
@@ -597,6 +638,14 @@ int wga_ctx_get_param(wga_ctx* c, const char* name, int64_t* value) {
     *value = (int64_t)c->paf_pair_hash_bits;
     return WGA_OK;
   }
+  if (strcmp(name, "maf_index_hash_bits") == 0) {
+    *value = (int64_t)c->maf_index_hash_bits;
+    return WGA_OK;
+  }
+  if (strcmp(name, "maf_index_sort_bits") == 0) {
+    *value = (int64_t)c->maf_index_sort_bits;
+    return WGA_OK;
+  }
   if (strcmp(name, "expand_job_tiles") == 0) {
     *value = (int64_t)c->expand_job_tiles;
     return WGA_OK;
@@ -640,6 +689,7 @@ int wga_ctx_get_param(wga_ctx* c, const char* name, int64_t* value) {
 #include "capi_stat_rows.inc"
 #include "capi_dotplot_overview.inc"
 #include "capi_dotplot_csv.inc"
+#include "capi_maf_index.inc"
 #include "capi_pafcov.inc"
 #include "capi_pafpseudo.inc"
 #include "capi_multigpu.inc"

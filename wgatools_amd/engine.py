@@ -58,6 +58,11 @@ DOTPLOT_OV_HEAD_DTYPE = np.dtype([("ref_start", "<u8"), ("ref_end", "<u8"), ("q_
                                   ("align_size", "<u8"), ("rname_off", "<u8"), ("qname_off", "<u8"), ("rname_len", "<u4"),
                                   ("qname_len", "<u4")])
 assert DOTPLOT_OV_HEAD_DTYPE.itemsize == 64
+# K35 (include/wga_hip.h wga_maf_index_name, WGA_E_FALLBACK)
+MAF_INDEX_NAME_DTYPE = np.dtype([("name_off", "<u8"), ("size", "<u8"), ("first_line", "<u8"), ("n_ivls", "<u8"), ("text_off", "<u8"),
+                                 ("name_len", "<u4"), ("isref", "<u4")])
+assert MAF_INDEX_NAME_DTYPE.itemsize == 48
+E_FALLBACK = -6
 # K32 (include/wga_hip.h wga_maf_frame_head)
 MAF_FRAME_HEAD_DTYPE = np.dtype([("score", "<u8"), ("t", np.uint64, 3), ("q", np.uint64, 3), ("tname_off", "<u8"),
                                  ("qname_off", "<u8"), ("tname_len", "<u4"), ("qname_len", "<u4"), ("t_neg", np.uint8),
@@ -539,6 +544,44 @@ class Engine:
         cap = 0 if lines is None else (lines.numel() if hasattr(lines, "numel") else lines.size)
         self._check(self.lib.wga_maf_split(self.ctx, _p(text), int(n_bytes), C.byref(nl), _p(lines), int(cap)))
         return int(nl.value)
+
+    def maf_index(self, text, n_bytes, lines, n_lines, skip=0, base=0, carry_offset=0, work=None, out_shift=0):
+        """K35 (index.rs:14-94): the blocks' offsets, the name groups and the JSON interval text of a piece, both calls of
+        wga_maf_index on wga_maf_split's table.  Returns a dict: n_names, n_blocks, n_slines, first_dup_line and
+        first_conflict_line (None when absent), next_offset, names (numpy MAF_INDEX_NAME_DTYPE, n_names + 1 entries) and text —
+        or None for a table with a WGA_MAF_FALLBACK line (WGA_E_FALLBACK).  The 64 bytes in front of and behind the text and the
+        entry behind the table are checked to be left alone, after the count call and after the fill; the counts must stay.
+        work: a device buffer to use; out_shift: d_out starts that many bytes behind a 64-byte aligned address"""
+        n_lines = int(n_lines)
+        if work is None:
+            work = self.empty(max(int(self.lib.wga_maf_index_work_bytes(n_lines)), 16), np.uint8)
+        host = [C.c_uint64(7) for _ in range(7)]
+        args = (self.ctx, _p(text), int(n_bytes), _p(lines), n_lines, int(skip), int(base), int(carry_offset), _p(work)) + \
+            tuple(C.byref(v) for v in host)
+        rc = self.lib.wga_maf_index(*args, None, None)
+        if rc == E_FALLBACK:
+            return None
+        self._check(rc)
+        first = [int(v.value) for v in host]
+        n_names, n_blocks, n_slines, total, dup, conflict, nxt = first
+        guard = 64
+        out = self.upload(np.full(total + 2 * guard + 32, 0xA5, dtype=np.uint8))
+        names = self.upload(np.full((n_names + 2) * 48, 0xA5, dtype=np.uint8))
+        self._check(self.lib.wga_maf_index(*args, names.ptr, out.ptr + guard + int(out_shift)))
+        self.sync()
+        if [int(v.value) for v in host] != first:
+            raise _lib.WgaError("wga_maf_index changed its counts in the second call")
+        got, lead = out.numpy(), guard + int(out_shift)
+        tab = names.numpy()
+        if not ((got[:lead] == 0xA5).all() and (got[lead + total:] == 0xA5).all()):
+            raise _lib.WgaError("wga_maf_index wrote outside d_out[0 .. text_bytes)")
+        used = (n_names + 1) * 48 if n_slines else 0
+        if not (tab[used:] == 0xA5).all():
+            raise _lib.WgaError("wga_maf_index wrote behind its table")
+        none = int(NONE)
+        return dict(n_names=n_names, n_blocks=n_blocks, n_slines=n_slines, next_offset=nxt,
+                    first_dup_line=None if dup == none else dup, first_conflict_line=None if conflict == none else conflict,
+                    names=tab[:used].view(MAF_INDEX_NAME_DTYPE).copy(), text=got[lead:lead + total].tobytes())
 
     def chain_split(self, text, n_bytes, heads=None, lines=None, line_off=None):
         """K23: (n_chains, n_data_lines, status, first bad line or None); the count call when the three arrays are None,

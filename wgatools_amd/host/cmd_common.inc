@@ -102,8 +102,13 @@ struct MafInput {
   bool on_device = false;
   uint8_t* d_text = nullptr;
   std::string error; /* keep_going: the host reader's error behind the records (they come first) */
+  wga_maf_line* d_lines = nullptr; /* lines_only: the splitter's table stays on the device, n_lines entries; no records are built */
+  uint64_t n_lines = 0;
 };
-MafInput maf_from_text(Dev& d, std::string&& whole_text, bool keep_going = false) {
+/* lines_only (maf-index): a piece the device splitter can be asked about keeps its line table on the device and gets no host
+ * records — the table is not even looked at here, so a WGA_MAF_FALLBACK line in it is the caller's to find (wga_maf_index
+ * refuses such a table) and to read with parse_maf. */
+MafInput maf_from_text(Dev& d, std::string&& whole_text, bool keep_going = false, bool lines_only = false) {
   MafInput in;
   *in.text = std::move(whole_text);
   const std::string& text = *in.text;
@@ -119,6 +124,17 @@ MafInput maf_from_text(Dev& d, std::string&& whole_text, bool keep_going = false
     d.check(wga_maf_split(d.ctx, in.d_text, text.size(), &n_lines, nullptr, 0));
     auto* d_lines = (wga_maf_line*)d.alloc((size_t)(n_lines + 1) * sizeof(wga_maf_line));
     d.check(wga_maf_split(d.ctx, in.d_text, text.size(), &n_lines, d_lines, n_lines));
+    if (lines_only) {
+      g_timer.mark("device split");
+      in.on_device = true;
+      in.d_lines = d_lines;
+      in.n_lines = n_lines;
+      size_t he = text.find('\n');
+      if (he == std::string::npos) he = text.size();
+      if (he > 0 && text[he - 1] == '\r') he--;
+      in.header.assign(text, 0, he);
+      return in;
+    }
     std::vector<wga_maf_line> lines((size_t)n_lines);
     if (n_lines) d.download(lines.data(), d_lines, (size_t)n_lines);
     d.release(d_lines);
@@ -199,6 +215,7 @@ struct MafChunks {
   std::string header;
   std::unique_ptr<BgzfDeviceSource> bgzf; /* a bgzipped input: inflated on the device */
   bool keep_going = false; /* a piece whose host reader fails returns its records in front of the error (MafInput::error) */
+  bool lines_only = false; /* maf-index: next() hands out EVERY piece, a device-split one with its line table and without records */
   std::function<void(const std::string&)> on_piece; /* sees every piece's text, the ones without a block too (maf-index: file offsets) */
   explicit MafChunks(const std::string* input) {
     bgzf.reset(new BgzfDeviceSource());
@@ -282,10 +299,10 @@ struct MafChunks {
       if (in.text && in.text.use_count() == 1) rd.recycle(std::move(*in.text)); /* nobody else holds the piece the caller is done with */
       read_ahead();
       if (on_piece) on_piece(a.text);
-      in = maf_from_text(d, std::move(a.text), keep_going);
+      in = maf_from_text(d, std::move(a.text), keep_going, lines_only);
       if (first_seen) header = in.header;
       first_seen = false;
-      if (!in.recs.empty() || !in.error.empty()) return true;
+      if (lines_only || !in.recs.empty() || !in.error.empty()) return true;
       if (in.d_text) d.release(in.d_text);
     }
   }

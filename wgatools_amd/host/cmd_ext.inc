@@ -61,10 +61,75 @@ int cmd_maf_index(const std::string* input, const std::string& outfile) {
   MafOffsetWalk walk;
   MafInput min;
   std::vector<uint64_t> offsets;
-  chunks.on_piece = [&](const std::string& text) { walk.piece(text, offsets); }; /* pieces without a block are walked too */
+  static const char* kConflict = "Same sequence cannot be both reference and query!";
+  /* WGA_MAF_INDEX_WRITER=host: every piece through the host loop below, as before K35.  Otherwise a piece the device splitter took
+   * goes through wga_maf_index: no record is built and no second walk over its text runs for it; the offset walk runs only over the
+   * pieces the host reader reads and hands its state to the device pieces and takes it back. */
+  const bool host_writer = env_is("WGA_MAF_INDEX_WRITER", "host");
+  chunks.lines_only = !host_writer;
+  if (host_writer) chunks.on_piece = [&](const std::string& text) { walk.piece(text, offsets); }; /* pieces without a block are walked too */
   for (;;) {
     offsets.clear();
     if (!chunks.next(d, min)) break;
+    if (!host_writer && min.d_lines) {
+      const uint32_t skip = walk.first_piece ? 0u : 2u;
+      const size_t n_bytes = min.text->size();
+      void* d_work = d.alloc((size_t)wga_maf_index_work_bytes(min.n_lines));
+      uint64_t n_names = 0, n_blocks = 0, n_slines = 0, text_bytes = 0, dup = WGA_NONE, conflict = WGA_NONE, next_offset = walk.cur;
+      auto call = [&](wga_maf_index_name* d_names, uint8_t* d_out) {
+        return wga_maf_index(d.ctx, min.d_text, n_bytes, min.d_lines, min.n_lines, skip, walk.file_pos, walk.cur, d_work, &n_names,
+                             &n_blocks, &n_slines, &text_bytes, &dup, &conflict, &next_offset, d_names, d_out);
+      };
+      const int rc = call(nullptr, nullptr);
+      if (rc != WGA_E_FALLBACK) {
+        d.check(rc);
+        std::vector<wga_maf_index_name> names((size_t)n_names + 1);
+        std::string ivl_text((size_t)text_bytes, '\0');
+        if (n_slines) {
+          auto* d_names = (wga_maf_index_name*)d.alloc(names.size() * sizeof(wga_maf_index_name));
+          auto* d_out = (uint8_t*)d.alloc((size_t)text_bytes + 16);
+          d.check(call(d_names, d_out));
+          d.download(names.data(), d_names, names.size());
+          d.download((uint8_t*)&ivl_text[0], d_out, (size_t)text_bytes);
+        }
+        /* the piece's names -> the global entries: one lookup per distinct name of the piece.  The error is the one at the lowest
+         * line: the device's two, or the first line of a group whose isref is not its entry's; a duplicate goes first on the same
+         * line (index.rs:32-56) */
+        const std::string& text = *min.text;
+        std::vector<size_t> entry_of((size_t)n_names);
+        for (size_t g = 0; g < (size_t)n_names; g++) {
+          const wga_maf_index_name& N = names[g];
+          std::string name(text, (size_t)N.name_off, N.name_len);
+          auto it = by_name.find(name);
+          if (it == by_name.end()) {
+            it = by_name.emplace(name, entries.size()).first;
+            entries.push_back(Entry{std::move(name), std::string(), N.size, N.isref != 0});
+          } else if (entries[it->second].isref != (N.isref != 0)) {
+            conflict = std::min(conflict, N.first_line);
+          }
+          entry_of[g] = it->second;
+        }
+        if (dup != WGA_NONE && dup <= conflict) {
+          wga_maf_line L;
+          d.download(&L, (const wga_maf_line*)min.d_lines + dup, 1);
+          fail("Duplicate name `" + std::string(text, (size_t)L.name_off, L.name_len) + "` in a record not allowed, please check or use `rename`");
+        }
+        if (conflict != WGA_NONE) fail(kConflict);
+        for (size_t g = 0; g < (size_t)n_names; g++) {
+          std::string& v = entries[entry_of[g]].ivls;
+          if (!v.empty()) v.push_back(',');
+          v.append(ivl_text, (size_t)names[g].text_off, (size_t)(names[g + 1].text_off - names[g].text_off));
+        }
+        walk.file_pos += n_bytes - skip;
+        walk.cur = next_offset;
+        walk.first_piece = walk.first_line = walk.in_run = false;
+        d.release_all();
+        g_timer.mark("maf-index entries (device)");
+        continue;
+      }
+      min.recs = parse_maf(*min.text, &min.header); /* a line the splitter does not take: the host reader's records, or its error */
+    }
+    if (!host_writer) walk.piece(*min.text, offsets);
     if (offsets.size() != min.recs.size()) fail("internal error: maf-index lost track of the blocks' offsets");
     for (size_t b = 0; b < min.recs.size(); b++) {
       const MafRecord& r = min.recs[b];
@@ -92,6 +157,7 @@ int cmd_maf_index(const std::string* input, const std::string& outfile) {
       }
     }
     if (d.ctx) d.release_all();
+    g_timer.mark("maf-index entries (host)");
   }
   if (entries.empty()) fail("Empty record");
   std::string js = "{";
