@@ -1229,6 +1229,58 @@ int wga_maf_index(wga_ctx*, const uint8_t* d_text, uint64_t n_bytes, const wga_m
                   uint64_t* text_bytes, uint64_t* first_dup_line, uint64_t* first_conflict_line, uint64_t* next_offset,
                   wga_maf_index_name* d_names /* *n_names + 1, device */, uint8_t* d_out);
 
+/* ---- K36: `stat` — the merged table (replaces, without `-e`, the download of every record's counters, the two strings per record
+ *      kept to the end of the file, the map lookup per record and the thirteen additions per record of stat_tsv,
+ *      wgatools_amd/host/wga_host.cpp; in the reference the Pair aggregation of merge_final_from_pair stat.rs:167-223) -----------
+ * wga_stat_pairs takes wga_stat_rows' inputs: d_heads[n] with the four numbers as printed and the spans of the two names inside
+ * d_names[0 .. n_name_bytes) (a span that does not lie inside counts as the empty name), d_counts[n] wga_cigar_stat's or
+ * wga_maf_pair_stat's counters.
+ * Pairs.  Two records are one pair exactly when their ref_name bytes, ref_size, query_name bytes and query_size agree: a hash only
+ * places a record in the table, the bytes and the two sizes decide (("ab","c") and ("a","bc") are two pairs, and so are equal names
+ * with different sizes).  Pairs are numbered by ascending first_rec, the first-appearance order.  Context parameter
+ * "stat_pair_hash_bits" (1 .. 64, default 64): the hash is cut to that many low bits, so that a test makes every pair collide.
+ * Of pair p, with all integer arithmetic mod 2^64:
+ *   first_rec, n_recs        its lowest record (whose head holds the names and sizes) and how many it has
+ *   ref_start, query_start   min(ref_size, min ref_start), min(query_size, min query_start): stat.rs:186-213
+ *   sum                      each of the eleven counters, summed (stat.rs:194-205; aligned_size is match + mismatch + del_bp +
+ *                            inv_del_bp of the sums)
+ *   inv_size_bits            the bits of an f32: the left fold, in ascending record order, of the values
+ *                            (float)(aligned + query_align) / (float)(inv_ev + 1) (wga_stat_rows' inv_size) of the pair's records
+ *                            with inv_ev != 0, from the start value d_inv_in[p] (an f32's bits; d_inv_in == NULL: +0.0).  This
+ *                            is stat.rs:206 in input order: adding the other records' +0.0 changes nothing.
+ *   d_pairs == NULL and d_pair_of_rec == NULL: the grouping is built in d_work and *n_pairs, a host value, is set (the call
+ *                  synchronises).
+ *   otherwise    : d_pair_of_rec[n] and d_pairs[*n_pairs] are written; cap_pairs >= *n_pairs (WGA_E_TOO_SMALL otherwise).
+ *                  *n_pairs and d_work are read as the first call left them, so the two calls take the same arguments.  The call
+ *                  may be repeated on the same outputs with another d_inv_in: it then rewrites inv_size_bits alone.
+ * n == 0: *n_pairs = 0, nothing is written.  WGA_E_INVALID_ARG: a null d_work or n_pairs, whatever n; a null array with n > 0
+ * (d_names only when n_name_bytes > 0; one of the two outputs without the other); n > 0xFFFFFFF0; an *n_pairs that is not the first
+ * call's.
+ * d_work: wga_stat_pairs_work_bytes(n) bytes of device memory, 8-byte aligned, shared by the calls
+ * = 8 * (8 + M + 2 * (n + 1) + C + n / 1024 + C / 1024 + 8) + 4 * (6 * n + 2), rounded up to a multiple of 8, with M the table's
+ * slots (the power of two from 16 to 2^32 that first reaches 2 n) and C = 256 * ((n + 1023) / 1024) + 1 the sort's counters. */
+typedef struct {
+  uint64_t first_rec, n_recs;        /* lowest record of the pair (its head holds names and sizes); how many */
+  uint64_t ref_start, query_start;   /* min(ref_size, min ref_start), min(query_size, min query_start): stat.rs:186-213 */
+  wga_cigar_counts sum;              /* each of the 11 counters, summed mod 2^64 */
+  uint32_t inv_size_bits, pad;       /* f32, see above */
+} wga_stat_pair;                     /* 128 bytes */
+
+uint64_t wga_stat_pairs_work_bytes(uint64_t n);
+int wga_stat_pairs(wga_ctx*, uint32_t n, const uint8_t* d_names, uint64_t n_name_bytes, const wga_stat_row_head* d_heads,
+                   const wga_cigar_counts* d_counts, void* d_work, uint64_t* n_pairs,
+                   uint32_t* d_pair_of_rec, const uint32_t* d_inv_in, wga_stat_pair* d_pairs, uint64_t cap_pairs);
+
+/* the pairs' rows (stat.rs:216-218 through the csv writer of stat.rs:117-123): wga_stat_rows over d_sums[n], with its protocol,
+ * limits, errors and d_work (wga_stat_rows_work_bytes(n)), d_heads[r] holding pair r's two sizes, its two minima and its names.
+ * Row r has wga_stat_rows' 22 columns with two differences: column 8 (unaligned_size) is ref_size - aligned_size mod 2^64, the
+ * release build's wrapping difference, and column 18 (inv_size) is the f32 with the bits d_inv_bits[r].  identity and similarity
+ * come from the sums by wga_stat_rows' formulas; 0 / 0 prints "NaN".  d_inv_bits is one of the arrays that may not be null
+ * with n > 0. */
+int wga_stat_pair_rows(wga_ctx*, uint32_t n, const uint8_t* d_names, uint64_t n_name_bytes, const wga_stat_row_head* d_heads,
+                       const wga_cigar_counts* d_sums, const uint32_t* d_inv_bits, void* d_work,
+                       uint64_t* d_row_off /* n + 1, device */, uint64_t* total_bytes, uint8_t* d_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -127,6 +127,9 @@ PROTOTYPES = {
     "wga_maf_index_work_bytes": (C.c_uint64, [C.c_uint64]),
     "wga_maf_index": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, vp] +
                       [C.POINTER(C.c_uint64)] * 7 + [vp, vp]),
+    "wga_stat_pairs_work_bytes": (C.c_uint64, [C.c_uint64]),
+    "wga_stat_pairs": (C.c_int, [vp, C.c_uint32, vp, C.c_uint64, vp, vp, vp, C.POINTER(C.c_uint64), vp, vp, vp, C.c_uint64]),
+    "wga_stat_pair_rows": (C.c_int, [vp, C.c_uint32, vp, C.c_uint64, vp, vp, vp, vp, vp, C.POINTER(C.c_uint64), vp]),
     "wga_dotplot_csv_work_bytes": (C.c_uint64, [C.c_uint64]),
     "wga_dotplot_csv": (C.c_int, [vp, C.c_uint32, vp, vp, vp, vp, vp, C.POINTER(C.c_uint64), vp]),
     "wga_pafcov_finalize": (C.c_int, [vp, C.c_uint32, vp, vp, vp]),

@@ -59,6 +59,8 @@
 #include "wga_k34_dotplot_overview.h" /* K34: the csv rows of dotplot -m overview, the f64 text */
 #include "wga_sort.h"          /* the stable key sort (run_sort_u32) */
 #include "wga_k35_maf_index.h" /* K35: maf-index: block offsets, name groups, the JSON interval text */
+#include "wga_group.h"         /* group-by on the device (run_group) */
+#include "wga_k36_stat_pairs.h" /* K36: stat's merged table: pair groups, sums, the pairs' rows */
 
 /* A grow-only device buffer of a context.  reserve() leaves it with room for `need` bytes: one that is too small is freed
  * behind the work of the context's stream and allocated anew with `grow` (>= need) bytes — every site has its own growth rule —,
@@ -125,6 +127,7 @@ struct wga_ctx {
   unsigned paf_pair_hash_bits = 64; /* K24: the low bits of the pair hash that pick a slot (test knob "paf_pair_hash_bits": few bits make the pairs collide) */
   unsigned maf_index_hash_bits = 64; /* K35: the low bits of the name hash that pick a slot (test knob "maf_index_hash_bits") */
   unsigned maf_index_sort_bits = 8;  /* K35: the digit width of the sort by group (test knob "maf_index_sort_bits": any width gives the same order) */
+  unsigned stat_pair_hash_bits = 64; /* K36: the low bits of the pair hash that pick a slot (test knob "stat_pair_hash_bits") */
   unsigned maf_group = 0;          /* blocks per wave of the MAF stream kernels, 1 .. 8 ("maf_group"; 0 = by the number of blocks) */
   DevBuf maf_tab;                  /* K3 / K4: the table of a call's long blocks (header, list, pieces) */
   bool maf_hdr_clean = false;      /* the header's append counters are zero (the plan kernel leaves them so) */
@@ -283,6 +286,45 @@ static int run_sort_u32(wga_ctx* c, K key, u32 n, unsigned key_bits, unsigned di
     LAUNCH_CHECK();
     *where ^= 1;
   }
+  return WGA_OK;
+}
+/* The groups of n items by key (wga_group.h): rounds of claim and settle until every item has its group's lowest member in rep[],
+ * then the scan that numbers the groups.  It leaves *n_groups (a host value: the call synchronises), every item's group number in
+ * `start` (the start slots are done with) and the items 0 .. n - 1 in list[0], ready for run_sort_u32.  slots: group_slots(n) words;
+ * rep, start, list[0], list[1]: n each; gidx: n + 1; partial: the scan's (n / 1024 + 2 words). */
+template <typename K>
+static int run_group(wga_ctx* c, K key, u32 n, unsigned hash_bits, GroupHdr* hdr, u64* slots, u32* rep, u32* start, u32* const list[2],
+                     u64* gidx, u64* partial, u64* n_groups) {
+  *n_groups = 0;
+  if (n == 0) return WGA_OK;
+  const u64 M = group_slots(n);
+  const u32 slot_mask = (u32)(M - 1u);
+  const u64 hash_mask = hash_bits >= 64u ? ~0ull : (1ull << hash_bits) - 1ull;
+  const u32 grid = (u32)(((u64)n + 255u) / 256u);
+  RT_CHECK(rt_memset(slots, 0xFF, (size_t)M * sizeof(u64), c->stream));
+  WGA_LAUNCH(k_group_init<K>, grid, WGA_BLOCK, c->stream, key, (u64)n, hash_mask, slot_mask, start, rep, list[0]);
+  LAUNCH_CHECK();
+  u64 m = n;
+  for (u64 r = 0; m; r++) { /* every round gives the lowest item of each start slot's class a group, or steps over a taken slot */
+    if (m > n || r > 2u * M + 64u) return fail(WGA_E_HIP, "the group table did not settle", nullptr);
+    const u32 g = (u32)((m + 255u) / 256u);
+    WGA_LAUNCH(k_group_claim, g, WGA_BLOCK, c->stream, (const u32*)list[r & 1u], m, r, slot_mask, (const u32*)start, slots, hdr);
+    LAUNCH_CHECK();
+    WGA_LAUNCH(k_group_settle<K>, g, WGA_BLOCK, c->stream, key, (const u32*)list[r & 1u], m, (u64)n, r, slot_mask, (const u32*)start,
+               (const u64*)slots, rep, list[(r + 1u) & 1u], hdr);
+    LAUNCH_CHECK();
+    RT_CHECK(rt_d2h(&m, &hdr->cnt[(r + 1u) & 1u], sizeof m, c->stream));
+  }
+  ScanGroupRep fr;
+  fr.rep = rep;
+  int rc = run_scan_ws(c, fr, n, gidx, partial);
+  if (rc) return rc;
+  u64 ng = 0;
+  RT_CHECK(rt_d2h(&ng, gidx + n, sizeof ng, c->stream));
+  if (ng == 0 || ng > n) return fail(WGA_E_HIP, "the groups' scan is not a scan", nullptr);
+  WGA_LAUNCH(k_group_number, grid, WGA_BLOCK, c->stream, (u64)n, (const u32*)rep, (const u64*)gidx, start, list[0]);
+  LAUNCH_CHECK();
+  *n_groups = ng;
   return WGA_OK;
 }
 /* the text of a stream of n items of format f behind isc, the scan of their sizes over ScanItems<F> (wga_text_out.h) */
@@ -492,6 +534,11 @@ int wga_ctx_set_param(wga_ctx* c, const char* name, int64_t value) {
     c->maf_index_hash_bits = (unsigned)value;
     return WGA_OK;
   }
+  if (strcmp(name, "stat_pair_hash_bits") == 0) { /* wga_stat_pairs: the hash is cut to this many low bits before it picks a place */
+    if (value < 1 || value > 64) return fail(WGA_E_INVALID_ARG, "stat_pair_hash_bits: 1 .. 64", nullptr);
+    c->stat_pair_hash_bits = (unsigned)value;
+    return WGA_OK;
+  }
   if (strcmp(name, "maf_index_sort_bits") == 0) { /* wga_maf_index: the digit width of its sort by group */
     if (value < 1 || value > (int64_t)WGA_SORT_MAX_BITS) return fail(WGA_E_INVALID_ARG, "maf_index_sort_bits: 1 .. 8", nullptr);
     c->maf_index_sort_bits = (unsigned)value;
@@ -646,6 +693,10 @@ int wga_ctx_get_param(wga_ctx* c, const char* name, int64_t* value) {
     *value = (int64_t)c->maf_index_sort_bits;
     return WGA_OK;
   }
+  if (strcmp(name, "stat_pair_hash_bits") == 0) {
+    *value = (int64_t)c->stat_pair_hash_bits;
+    return WGA_OK;
+  }
   if (strcmp(name, "expand_job_tiles") == 0) {
     *value = (int64_t)c->expand_job_tiles;
     return WGA_OK;
@@ -690,6 +741,7 @@ int wga_ctx_get_param(wga_ctx* c, const char* name, int64_t* value) {
 #include "capi_dotplot_overview.inc"
 #include "capi_dotplot_csv.inc"
 #include "capi_maf_index.inc"
+#include "capi_stat_pairs.inc"
 #include "capi_pafcov.inc"
 #include "capi_pafpseudo.inc"
 #include "capi_multigpu.inc"

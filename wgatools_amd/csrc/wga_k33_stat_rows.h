@@ -49,9 +49,11 @@ __device__ __forceinline__ StatRowF32 stat_row_f32(const wga_cigar_counts& c, u6
   return f;
 }
 
-template <typename S>
+/* kPair: a row of the merged table (K36, StatPairRowSrc in wga_k36_stat_pairs.h): c holds a pair's sums, column 8 is ref_size -
+ * aligned_size (mod 2^64, stat.rs:216) and column 18 the f32 with the bits inv_bits, the fold over the pair's records */
+template <bool kPair = false, typename S>
 __device__ __forceinline__ void stat_row_emit(S& s, const wga_stat_row_head& H, const u8* __restrict__ names, u64 n_name_bytes,
-                                              const wga_cigar_counts& c) {
+                                              const wga_cigar_counts& c, u32 inv_bits = 0u) {
   const u32 rl = name_span_len(H.rname_off, H.rname_len, n_name_bytes), ql = name_span_len(H.qname_off, H.qname_len, n_name_bytes);
   const u64 aligned = c.match + c.mismatch + c.del_bp + c.inv_del_bp;
   const StatRowF32 f = stat_row_f32(c, aligned);
@@ -69,7 +71,8 @@ __device__ __forceinline__ void stat_row_emit(S& s, const wga_stat_row_head& H, 
   s.c((u8)'\t');
   s.dec(aligned);
   s.c((u8)'\t');
-  s.c((u8)'0'); /* unaligned_size: split_final leaves it 0 */
+  if (kPair) s.dec(H.ref_size - aligned);
+  else s.c((u8)'0'); /* unaligned_size: split_final leaves it 0 */
   s.c((u8)'\t');
   f32_text_emit(s, f.identity);
   s.c((u8)'\t');
@@ -81,7 +84,7 @@ __device__ __forceinline__ void stat_row_emit(S& s, const wga_stat_row_head& H, 
     s.dec(a[k]);
     s.c((u8)'\t');
   }
-  f32_text_emit(s, f.inv_size);
+  f32_text_emit(s, kPair ? inv_bits : f.inv_size);
   const u64 b[4] = {c.inv_ins_ev, c.inv_ins_bp, c.inv_del_ev, c.inv_del_bp};
 #pragma unroll
   for (u32 k = 0; k < 4u; k++) {

@@ -63,6 +63,10 @@ MAF_INDEX_NAME_DTYPE = np.dtype([("name_off", "<u8"), ("size", "<u8"), ("first_l
                                  ("name_len", "<u4"), ("isref", "<u4")])
 assert MAF_INDEX_NAME_DTYPE.itemsize == 48
 E_FALLBACK = -6
+# K36 (include/wga_hip.h wga_stat_pair)
+STAT_PAIR_DTYPE = np.dtype([("first_rec", "<u8"), ("n_recs", "<u8"), ("ref_start", "<u8"), ("query_start", "<u8"),
+                            ("sum", COUNTS_DTYPE), ("inv_size_bits", "<u4"), ("pad", "<u4")])
+assert STAT_PAIR_DTYPE.itemsize == 128
 # K32 (include/wga_hip.h wga_maf_frame_head)
 MAF_FRAME_HEAD_DTYPE = np.dtype([("score", "<u8"), ("t", np.uint64, 3), ("q", np.uint64, 3), ("tname_off", "<u8"),
                                  ("qname_off", "<u8"), ("tname_len", "<u4"), ("qname_len", "<u4"), ("t_neg", np.uint8),
@@ -849,6 +853,44 @@ class Engine:
     def f32_text(self, bits):
         """K33's formatter alone: the texts of the f32s with the bit patterns `bits` (uint32)"""
         return self._bits_text("wga_f32_text", bits, np.uint32, 16, 16)
+
+    def stat_pairs(self, n, names, n_name_bytes, heads, counts, inv_in=None, work=None):
+        """K36 (stat.rs:167-223): the pairs of n records, both calls of wga_stat_pairs on wga_stat_rows' inputs.  Returns
+        (pairs: STAT_PAIR_DTYPE[n_pairs], pair_of_rec: uint32[n]); the words around both outputs are guards and are checked.
+        inv_in: a device array of f32 bit patterns, the folds' start values; work: a device buffer to use"""
+        n = int(n)
+        if work is None:
+            work = self.empty(max(int(self.lib.wga_stat_pairs_work_bytes(n)), 16), np.uint8)
+        args = (self.ctx, n, _p(names), int(n_name_bytes), _p(heads), _p(counts), _p(work))
+        n_pairs = C.c_uint64(0)
+        self._check(self.lib.wga_stat_pairs(*args, C.byref(n_pairs), None, None, None, 0))
+        np_ = int(n_pairs.value)
+        guard = 2
+        d_pairs = self.upload(np.full((np_ + 2 * guard) * 32, 0xA5A5A5A5, dtype=np.uint32))
+        d_por = self.upload(np.full(n + 2 * guard * 32, 0xA5A5A5A5, dtype=np.uint32))
+        self._check(self.lib.wga_stat_pairs(*args, C.byref(n_pairs), d_por.ptr + guard * 128, _p(inv_in), d_pairs.ptr + guard * 128,
+                                            np_))
+        self.sync()
+        if int(n_pairs.value) != np_:
+            raise _lib.WgaError("wga_stat_pairs changed its n_pairs in the second call")
+        gp, gr = d_pairs.numpy(), d_por.numpy()
+        lead = guard * 32
+        if not ((gp[:lead] == 0xA5A5A5A5).all() and (gp[lead + np_ * 32:] == 0xA5A5A5A5).all() and
+                (gr[:lead] == 0xA5A5A5A5).all() and (gr[lead + n:] == 0xA5A5A5A5).all()):
+            raise _lib.WgaError("wga_stat_pairs wrote outside d_pairs[0 .. n_pairs) or d_pair_of_rec[0 .. n)")
+        return gp[lead:lead + np_ * 32].copy().view(STAT_PAIR_DTYPE), gr[lead:lead + n].copy()
+
+    def stat_pair_rows(self, n, names, n_name_bytes, heads, sums, inv_bits, work=None, out_shift=0):
+        """K36 (stat.rs:216-218): the TSV rows of the merged table for n pairs, both calls of wga_stat_pair_rows on the pairs'
+        heads (STAT_ROW_HEAD_DTYPE: sizes, minima, names), sums (COUNTS_DTYPE) and inv_size bit patterns (uint32).  Returns
+        (text, row_off), checked as stat_rows checks"""
+        n = int(n)
+        if work is None:
+            work = self.empty(max(int(self.lib.wga_stat_rows_work_bytes(n)), 16), np.uint8)
+        row_off = self.empty(n + 1, np.uint64)
+        args = (self.ctx, n, _p(names), int(n_name_bytes), _p(heads), _p(sums), _p(inv_bits), _p(work), _p(row_off))
+        text = self._count_then_fill("wga_stat_pair_rows", "total", args, 1, out_shift)[0]
+        return text, (row_off.numpy().copy() if n else np.zeros(1, np.uint64))
 
     def dotplot_overview(self, n, names, n_name_bytes, heads, counts, no_identity=False, work=None, out_shift=0):
         """K34 (dotplot.rs:384-423): the csv rows of `dotplot -m overview` for n records, both calls of wga_dotplot_overview on

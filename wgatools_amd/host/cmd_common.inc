@@ -718,3 +718,111 @@ struct StatRows {
     g_timer.mark("stat rows gathered + written");
   }
 };
+
+/* ---- stat's merged table on the device (K36, wga_stat_pairs and wga_stat_pair_rows) -------------------------------------------------
+ * Per piece the device groups the records into pairs (ref_name, ref_size, query_name, query_size), sums the counters and folds
+ * inv_size; only the piece's pairs come back.  The host keeps ONE table of global pairs in first-appearance order — a map over
+ * pairs, not records, looked up through the head of a piece pair's first record — adds the piece's sums mod 2^64 and takes the
+ * minima.  inv_size is an f32 sum in record order (stat.rs:206), so a pair that already carries a non-zero value and gets
+ * inverted records again has its fold repeated from the carried value (the second call again, with d_inv_in).  After the last
+ * piece the pairs are ordered stably by the natural order of ref_name (stat.rs:116) and their rows are written on the device.
+ * WGA_STAT_WRITER=host keeps stat_tsv's path. */
+struct StatTable {
+  struct Pair {
+    std::string ref_name, query_name;
+    uint64_t ref_size, query_size, ref_start, query_start;
+    wga_cigar_counts sum;
+    uint32_t inv_bits;
+  };
+  std::vector<Pair> pairs; /* first-appearance order */
+  std::map<std::tuple<std::string, uint64_t, std::string, uint64_t>, size_t> index;
+  /* the n records of hd, whose counts stand on d; names_of(k) = record k's (ref_name, query_name) */
+  template <typename NamesOf>
+  void piece(Dev& d, StatRowHeads& hd, const wga_cigar_counts* d_counts, const NamesOf& names_of) {
+    const uint32_t n = (uint32_t)hd.heads.size();
+    if (n == 0) return;
+    hd.upload_names(d);
+    const wga_stat_row_head* d_heads = d.upload(hd.heads);
+    void* d_work = d.alloc((size_t)wga_stat_pairs_work_bytes(n));
+    uint64_t np = 0;
+    d.check(wga_stat_pairs(d.ctx, n, hd.d_names, hd.n_name_bytes, d_heads, d_counts, d_work, &np, nullptr, nullptr, nullptr, 0));
+    auto* d_por = (uint32_t*)d.alloc((size_t)n * 4);
+    auto* d_pairs = (wga_stat_pair*)d.alloc((size_t)np * sizeof(wga_stat_pair));
+    d.check(wga_stat_pairs(d.ctx, n, hd.d_names, hd.n_name_bytes, d_heads, d_counts, d_work, &np, d_por, nullptr, d_pairs, np));
+    std::vector<wga_stat_pair> got((size_t)np);
+    d.download(got.data(), d_pairs, (size_t)np);
+    std::vector<size_t> global((size_t)np);
+    std::vector<uint32_t> carried((size_t)np);
+    bool refold = false;
+    for (size_t p = 0; p < (size_t)np; p++) {
+      if (got[p].first_rec >= n) fail("GPU engine: a pair's first record lies outside the piece");
+      const wga_stat_row_head& H = hd.heads[(size_t)got[p].first_rec];
+      const auto names = names_of((size_t)got[p].first_rec);
+      auto key = std::make_tuple(*names.first, H.ref_size, *names.second, H.query_size);
+      auto it = index.find(key);
+      if (it == index.end()) {
+        Pair q;
+        q.ref_name = *names.first, q.query_name = *names.second;
+        q.ref_size = q.ref_start = H.ref_size; /* minima start from the sizes, stat.rs:186,189 */
+        q.query_size = q.query_start = H.query_size;
+        memset(&q.sum, 0, sizeof q.sum);
+        q.inv_bits = 0;
+        it = index.emplace(std::move(key), pairs.size()).first;
+        pairs.push_back(std::move(q));
+      }
+      global[p] = it->second;
+      carried[p] = pairs[it->second].inv_bits;
+      /* a fold from +0.0 that is not +0.0: the piece adds something to this pair's inv_size */
+      if (got[p].inv_size_bits != 0 && carried[p] != 0) refold = true;
+    }
+    if (refold) { /* rare: the folds again, from what the pairs carry */
+      const uint32_t* d_inv = d.upload(carried);
+      d.check(wga_stat_pairs(d.ctx, n, hd.d_names, hd.n_name_bytes, d_heads, d_counts, d_work, &np, d_por, d_inv, d_pairs, np));
+      d.download(got.data(), d_pairs, (size_t)np);
+    }
+    for (size_t p = 0; p < (size_t)np; p++) {
+      Pair& q = pairs[global[p]];
+      const uint64_t* a = (const uint64_t*)&got[p].sum;
+      uint64_t* b = (uint64_t*)&q.sum;
+      for (int k = 0; k < 11; k++) b[k] += a[k];
+      q.ref_start = std::min(q.ref_start, got[p].ref_start);
+      q.query_start = std::min(q.query_start, got[p].query_start);
+      if (refold || got[p].inv_size_bits != 0) q.inv_bits = got[p].inv_size_bits;
+    }
+    g_timer.mark("stat table (device)");
+  }
+  /* the header (only in front of a row) and the rows */
+  void write(Dev& d, Output& out) {
+    const uint32_t n = (uint32_t)pairs.size();
+    if (n == 0) return;
+    std::vector<uint32_t> order(n);
+    for (uint32_t k = 0; k < n; k++) order[k] = k;
+    std::stable_sort(order.begin(), order.end(),
+                     [&](uint32_t a, uint32_t b) { return natord_compare(pairs[a].ref_name, pairs[b].ref_name) < 0; });
+    d.init();
+    StatRowHeads hd(n);
+    std::vector<wga_cigar_counts> sums;
+    std::vector<uint32_t> inv;
+    sums.reserve(n), inv.reserve(n);
+    for (uint32_t k : order) {
+      const Pair& q = pairs[k];
+      hd.add(q.ref_name, 0, q.ref_size, q.ref_start, q.query_name, 0, q.query_size, q.query_start);
+      sums.push_back(q.sum);
+      inv.push_back(q.inv_bits);
+    }
+    const wga_cigar_counts* d_sums = d.upload(sums);
+    const uint32_t* d_inv = d.upload(inv);
+    std::string text =
+        "ref_name\tref_size\tref_start\tquery_name\tquery_size\tquery_start\taligned_size\t"
+        "unaligned_size\tidentity\tsimilarity\tmatched\tmismatched\tins_event\tdel_event\tins_size\t"
+        "del_size\tinv_event\tinv_size\tinv_ins_event\tinv_ins_size\tinv_del_event\tinv_del_size\n";
+    record_rows_text(d, hd, hd.heads, (size_t)wga_stat_rows_work_bytes(n), text,
+                     [&](const wga_stat_row_head* d_heads, void* d_work, uint64_t* d_row_off, uint64_t* total, uint8_t* d_out) {
+                       return wga_stat_pair_rows(d.ctx, n, hd.d_names, hd.n_name_bytes, d_heads, d_sums, d_inv, d_work, d_row_off, total,
+                                                 d_out);
+                     });
+    out.write(text);
+    d.release_all();
+    g_timer.mark("stat table (device)");
+  }
+};

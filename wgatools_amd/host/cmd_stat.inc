@@ -58,12 +58,14 @@ static void stat_piece_multi(std::vector<std::unique_ptr<Dev>>& devs, const PafI
 /* `stat -e` with the device writer (K33): per piece the counters stay on device 0 where K1 left them (--gpus N: they meet on the
  * host as for the merged table and are uploaded there), the host fills one head per record, and the piece's rows come back as
  * text (StatRows, cmd_common.inc).  Buffered driver: nothing is written before the last piece's records are counted. */
-static int stat_paf_rows_device(const std::string* input, Output& out) {
+/* Without -e the same loop feeds the merged table (K36, StatTable): the piece's pairs come back instead of its rows. */
+static int stat_paf_rows_device(const std::string* input, bool each, Output& out) {
   Dev d;
   PafChunks chunks(input, false);
   PafInput pin;
   WorkerDevices wd(d); /* --gpus N */
   StatRows rows;
+  StatTable table;
   while (chunks.next(d, pin)) {
     const std::vector<PafRecord>& recs = pin.recs;
     const uint32_t n = (uint32_t)recs.size();
@@ -86,19 +88,21 @@ static int stat_paf_rows_device(const std::string* input, Output& out) {
     in_piece.n_row_bytes = pin.text.size();
     StatRowHeads hd(n, &in_piece);
     for (const PafRecord& r : recs) {
-      rows.note(r.target_name);
+      if (each) rows.note(r.target_name);
       hd.add(r.target_name, r.tname_off, r.target_length, r.target_start, r.query_name, r.qname_off, r.query_length, r.query_start);
     }
-    rows.piece(d, hd, d_counts);
+    if (each) rows.piece(d, hd, d_counts);
+    else table.piece(d, hd, d_counts, [&](size_t k) { return std::make_pair(&recs[k].target_name, &recs[k].query_name); });
     d.release_all();
   }
-  rows.write(out);
+  if (each) rows.write(out);
+  else table.write(d, out);
   out.close();
   return leave(0);
 }
 
 int cmd_stat_paf(const std::string* input, bool each, Output& out) {
-  if (each && !stat_host_writer()) return stat_paf_rows_device(input, out);
+  if (!stat_host_writer()) return stat_paf_rows_device(input, each, out);
   Dev d;
   PafChunks chunks(input, false);
   std::vector<StatInput> in;
@@ -126,25 +130,31 @@ int cmd_stat_paf(const std::string* input, bool each, Output& out) {
     d.release_all();
   }
   out.write(stat_tsv(in, each));
-  if (each) g_timer.mark("stat rows (host)");
+  g_timer.mark(each ? "stat rows (host)" : "stat table (host)");
   out.close();
   return leave(0);
 }
 
 /* `stat -e` on MAF with the device writer: as stat_paf_rows_device, over K3's counters.  One device: they stay where K3 left them
  * and the names are read in the uploaded piece; --gpus N: they arrive on the host and are uploaded to device 0 with the names. */
-static int stat_maf_rows_device(const std::string* input, const std::string* query_name, Output& out) {
+static int stat_maf_rows_device(const std::string* input, bool each, const std::string* query_name, Output& out) {
   Dev d;
   MafDevices md(d);
   MafChunks chunks(input);
   MafInput min;
   StatRows rows;
+  StatTable table;
   while (chunks.next(d, min)) {
     std::vector<MafRecord>& recs = min.recs;
     select_query(recs, query_name);
     const uint32_t n = (uint32_t)recs.size();
     if (n) {
-      for (const MafRecord& r : recs) rows.note(r.t().name);
+      if (each)
+        for (const MafRecord& r : recs) rows.note(r.t().name);
+      auto piece = [&](Dev& dg, StatRowHeads& hd, const wga_cigar_counts* d_counts) {
+        if (each) rows.piece(dg, hd, d_counts);
+        else table.piece(dg, hd, d_counts, [&](size_t k) { return std::make_pair(&recs[k].t().name, &recs[k].q().name); });
+      };
       auto heads = [&](StatRowHeads& hd) {
         for (const MafRecord& r : recs)
           hd.add(r.t().name, r.t().name_off, r.t().size, r.t().start, r.q().name, r.q().name_off, r.q().size, r.query_start());
@@ -158,24 +168,25 @@ static int stat_maf_rows_device(const std::string* input, const std::string* que
         }
         StatRowHeads hd(n, &p);
         heads(hd);
-        rows.piece(dg, hd, R.d_counts);
+        piece(dg, hd, R.d_counts);
       });
       if (md.count() > 1) {
         d.init();
         StatRowHeads hd(n);
         heads(hd);
-        rows.piece(d, hd, d.upload(counts));
+        piece(d, hd, d.upload(counts));
       }
     }
     md.release_all();
   }
-  rows.write(out);
+  if (each) rows.write(out);
+  else table.write(d, out);
   out.close();
   return leave(0);
 }
 
 int cmd_stat_maf(const std::string* input, bool each, const std::string* query_name, Output& out) {
-  if (each && !stat_host_writer()) return stat_maf_rows_device(input, query_name, out);
+  if (!stat_host_writer()) return stat_maf_rows_device(input, each, query_name, out);
   Dev d;
   MafDevices md(d);
   MafChunks chunks(input);
@@ -200,7 +211,7 @@ int cmd_stat_maf(const std::string* input, bool each, const std::string* query_n
     md.release_all();
   }
   out.write(stat_tsv(in, each));
-  if (each) g_timer.mark("stat rows (host)");
+  g_timer.mark(each ? "stat rows (host)" : "stat table (host)");
   out.close();
   return leave(0);
 }

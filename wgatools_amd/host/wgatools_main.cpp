@@ -22,10 +22,12 @@
 #include <array>
 #include <condition_variable>
 #include <functional>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <regex>
 #include <thread>
+#include <tuple>
 
 #include "wga_host.hpp"
 
